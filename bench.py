@@ -5,13 +5,25 @@
 
 A step = forward + label-smoothing CE + backward + gradient all-reduce (N>1) + SGD(momentum)
 over one synthetic batch resident in HBM: 3x224x224, uniform [0,1) images, random-init weights.
+The SGD step size is `--lr`, 0 by default (see below): the step does all its work, the weights stay put.
 N = 1 runs BASELINE.json configs[1] (batch 256 on one GPU); N > 1 runs configs[2] (data parallel, 128 images
 per GPU = global 128*N, 1024 on 8 GPUs: the reference recipe's global batch, data.py:65-66) -- weak scaling at
-128 per GPU, whose 1-GPU denominator the N = 1 line carries as `n1_same_per_gpu_batch_ms`.  `--batch` overrides.
-Rank 0 prints ONE JSON line with the metric, the roofline of the dominant kernel
-(measured live, IN SITU: HIP events around that layer's launches inside the step's own forward
-list, on the launch stream) and the CPU baseline (the oracle, timed on the host cores on a
-bounded sample).
+128 per GPU, whose 1-GPU denominator the N = 1 `--full` line carries as `n1_same_per_gpu_batch_ms`.  `--batch` overrides.
+Rank 0 prints ONE JSON line with the metric (`value`, `ms_per_step` of the K timed steps).
+
+A plain run sets up, warms up, times the K steps (and writes their outputs with `--dump-outputs DIR`) and prints
+that line.  `--full` adds everything else to it: the roofline of the dominant kernel (measured live, IN SITU: HIP
+events around that layer's launches inside the step's own forward list, on the launch stream), the per-layer and
+HBM-bound rows, the rocprofv3 counter runs, the secondary configs, the CPU baseline (the oracle, timed on the host
+cores on a bounded sample) and, for N > 1, the single-GPU denominators, the exposed exchange and configs[2].
+
+`--dump-outputs DIR` writes what the last timed step hands its caller as float32 .npy files (see dump_outputs); the
+inputs (weights, images, labels) are seeded, so two runs or two builds with the same arguments can be compared file by
+file.  The step adds its filter gradients with float atomics, so one step reproduces to rounding only (gradients ~1e-9
+apart).  With a nonzero `--lr` that difference moves the weights the next step reads, and over tens of steps of this
+one-batch training it grows into different parameters and logits from run to run; at the default `--lr 0` every step
+starts from the same weights and the last one reproduces to rounding like the first.  (`--deterministic`, ~10 %
+slower, makes the step itself bit-identical at any `--lr`.)
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts its own N
 ranks (fresh child processes, one per GPU, rendezvous on 127.0.0.1) the way Lightning spawns the
@@ -291,14 +303,14 @@ def hbm_layers_insitu(ts, batch):
     return out
 
 
-def time_train_step(model, batch, image_size, steps, warmup, dev, keep=False):
+def time_train_step(model, batch, image_size, steps, warmup, dev, keep=False, lr=0.0):
     """ms per fused train step of `model` at per-GPU batch `batch` on this GPU alone (data_parallel=False: the
-    single-GPU program even when this process is a rank of a larger job)"""
+    single-GPU program even when this process is a rank of a larger job); `lr` as --lr"""
     from vision_toolbox import backbones
     from vision_toolbox.trainer import TrainStep
 
     torch.manual_seed(0)
-    ts = TrainStep(getattr(backbones, model)(), 1000, batch, image_size, torch.bfloat16, lr=0.05, momentum=0.9,
+    ts = TrainStep(getattr(backbones, model)(), 1000, batch, image_size, torch.bfloat16, lr=lr, momentum=0.9,
                    weight_decay=2e-5, label_smoothing=0.1, device=dev, use_graphs=False, process_group=None,
                    data_parallel=False)
     g = torch.Generator(device=dev)
@@ -340,13 +352,13 @@ def layer_rows(ts, batch, shapes):
     return rows
 
 
-def secondary_configs(dev):
+def secondary_configs(dev, lr=0.0):
     """BASELINE.json configs[3] and configs[4] in the driver-timed line (secondary numbers)"""
     from vision_toolbox import backbones
 
     out = []
     # configs[3]: VoVNet-39 forward+backward bf16, batch 256 (the same fused train step); 3 x 15.530 GFLOP per image
-    ms, loss, ts = time_train_step("vovnet39", 256, 224, 8, 3, dev, keep=True)
+    ms, loss, ts = time_train_step("vovnet39", 256, 224, 8, 3, dev, keep=True, lr=lr)
     ts.step()  # (creates the side stream the in-situ pieces run on)
     # VoVNet-39's dominant layer (128 -> 128 3x3 @56x56, five per step, 29.8 % of its MACs) and the first concat 1x1
     vrows = layer_rows(ts, 256, [(128, 128, 9, 56, 1, 5, ("fwd", "dgrad", "wgrad")),
@@ -624,6 +636,118 @@ def cpu_baseline(budget_s: float = 75.0):
                       f"{time.perf_counter() - t_start:.0f}s of CPU work in all"}
 
 
+def roofline_measurements(ts, args, world: int) -> dict:
+    """(--full) `roofline`, `roofline_layers` and `roofline_hbm_layers` of the result line: in-situ layer times inside
+    the lists of the step just timed, one standalone launch series of the dominant layer and, on one GPU, the
+    rocprofv3 child runs"""
+    from vision_toolbox import _native as N
+
+    # Dominant kernel: the two-group + loader-wave span kernel (vt_igemm_span6.hip) on the stride-1 3x3 convs and
+    # their data gradients.  Every roofline entry of the three dominant 3x3 shapes (SURVEY 8d: 128 -> 128 @28x28 x8,
+    # 256 -> 256 @14x14 x8, 512 -> 512 @7x7 x4) is measured IN SITU: events around those launches inside the step's own
+    # forward / backward lists, for the forward conv, the data gradient and the filter gradient.
+    scale = args.image_size / 224.0
+    shapes = [(128, 128, 9, int(round(28 * scale)), 8), (256, 256, 9, int(round(14 * scale)), 8),
+              (512, 512, 9, int(round(7 * scale)), 4)] if args.model in ("cspdarknet53", "darknet53") else []
+    layers, tot_fl, tot_ms, insitu = [], 0.0, 0.0, None
+    for (ci, co, nt, hw, cnt) in shapes:
+        fl = 2.0 * args.batch * hw * hw * co * nt * ci
+        row = {"layer": f"conv3x3 s1 {ci}->{co} @{hw}x{hw} B={args.batch} (M={args.batch * hw * hw} N={co} K={nt * ci})",
+               "launches_per_step": cnt, "gflop": round(fl / 1e9, 2)}
+        for which in ("fwd", "dgrad", "wgrad"):
+            ms_l, n_l, kname = insitu_layer_times(ts, ci, co, nt, hw, reps=3, which=which)
+            if not ms_l:
+                continue
+            row[which] = {"ms": round(ms_l, 4), "tflops": round(fl / ms_l / 1e9, 1),
+                          "frac": round(fl / ms_l / 1e9 / PEAK_BF16_TFLOPS, 4), "kernel": kname, "launches_timed": n_l}
+            tot_fl += cnt * fl
+            tot_ms += cnt * ms_l
+            if which == "fwd" and insitu is None:
+                insitu = {"ms": ms_l, "n": n_l, "kernel": kname, "tflops": fl / ms_l / 1e9, "flops": fl, "shape": row["layer"]}
+        layers.append(row)
+    if args.model == "cspdarknet53" and args.image_size == 224:
+        # the stride-2 3x3 convs that open the stages (24.8 % of the MACs): forward and filter gradient in situ
+        layers += layer_rows(ts, args.batch, [(32, 64, 9, 224, 2, 1, ("fwd", "wgrad")), (64, 128, 9, 112, 2, 1, ("fwd", "wgrad")),
+                                              (128, 256, 9, 56, 2, 1, ("fwd", "wgrad")), (256, 512, 9, 28, 2, 1, ("fwd", "wgrad")),
+                                              (512, 1024, 9, 14, 2, 1, ("fwd", "wgrad"))])
+    standalone = conv_roofline(args.batch, 128, 28, N.VT_BF16)
+    standalone_name = N.last_kernel_name()
+    dom = insitu or {"ms": standalone["ms"], "n": 30, "kernel": standalone_name, "tflops": standalone["tflops"],
+                     "flops": standalone["flops"], "shape": standalone["shape"]}
+    traffic = None
+    if world == 1 and not args.no_pmc:
+        # (the rocprof rows are matched by the name the dispatcher reported for this layer, e.g. "span6_kernel")
+        traffic = pmc_traffic_live("128,128,3,1,28", (standalone_name or dom["kernel"]).split("<")[0])
+    rocprof_avg = None
+    if world == 1 and not args.no_pmc and insitu is not None and args.model == "cspdarknet53" and args.batch == 256:
+        # (MODE 1 = the statistics epilogue = the forward launches; 8 DarknetBlock.conv2 units of stage 2 per step)
+        rocprof_avg = rocprof_launch_avg_live("span6_kernel<1,", 8)
+    # HBM-bound layers of stages 0-1 as the step runs them, in situ (SURVEY 8d: HBM fraction on the early-stage convs)
+    hbm_layers = hbm_layers_insitu(ts, args.batch) if args.model == "cspdarknet53" and args.image_size == 224 else []
+    return {
+        "roofline": {"bound": "mfma", "achieved": round(dom["tflops"], 1), "peak": PEAK_BF16_TFLOPS,
+                     "unit": "TFLOP/s", "frac": round(dom["tflops"] / PEAK_BF16_TFLOPS, 4),
+                     # MAC-weighted over the three dominant 3x3 shapes x {forward, data gradient, filter gradient}:
+                     # total FLOPs of those launches / their total in-situ time / peak -- not the best case
+                     "frac_fwd_dgrad_wgrad": round(tot_fl / tot_ms / 1e9 / PEAK_BF16_TFLOPS, 4) if tot_ms else None,
+                     "traffic": traffic["bytes"] if traffic else None,
+                     "traffic_source": ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, FETCH x2 on gfx950) "
+                                        "run by this bench on tools/bench_conv.py: STANDALONE launches of this layer "
+                                        "back to back (x and the filter re-read from the memory-side cache where the step's "
+                                        "own launch finds what the previous kernels left), while launch_ms / frac are in situ"
+                                        if traffic else None),
+                     "algorithmic_bytes": 2.0 * (args.batch * 28 * 28 * 256 + 128 * 1152),
+                     "kernel": dom["kernel"], "launch_ms": round(dom["ms"], 4), "launches_timed": dom["n"],
+                     # the same launches as rocprofv3's kernel trace of the step sees them (kernel start to end,
+                     # without the launch boundary the in-situ HIP events include) and the fraction that follows
+                     "launch_ms_rocprof": round(rocprof_avg["ms"], 4) if rocprof_avg else None,
+                     "frac_rocprof": round(dom["flops"] / (rocprof_avg["ms"] * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4)
+                     if rocprof_avg else None,
+                     "rocprof_source": ({k: rocprof_avg[k] for k in ("launches", "kernel_symbol", "lds_bytes")}
+                                        if rocprof_avg else None),
+                     "measured": "in situ (events around the layer's launches inside the step's forward list)"
+                     if insitu else "standalone", "layer": dom["shape"]},
+        "roofline_layers": layers,
+        "roofline_hbm_layers": hbm_layers,
+    }
+
+
+DUMP_PARAMS = 1 << 22  # parameters (and momenta) written by --dump-outputs: 16 MiB each (a fixed, seeded sample when there are more)
+
+
+def dump_outputs(ts, out_dir: str) -> dict:
+    """What the last step handed its caller, as float32 `out_dir/<name>.npy`: `loss` (the step's mean loss, shape [1]),
+    `logits` ([batch, classes]), `params` (the f32 master parameters in named_parameters() order, each flattened in its
+    own index order, concatenated; DUMP_PARAMS of them drawn by numpy's default_rng(0), kept in ascending order, when
+    the model has more), `momentum` (the SGD momentum buffer at the same positions: the step's gradients, weight decay
+    included, accumulated) and `bn_running_stats` (every floating-point buffer, running means and variances,
+    concatenated the same way).  Returns {name: shape}."""
+    import numpy as np
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    torch.cuda.synchronize()
+    pflat, mflat = ts.store.pflat, ts.mflat
+    plist = [p.detach() for _, p in ts.model.named_parameters()]
+    # (each parameter is a view into the flat f32 store; the momentum buffer has the same layout)
+    mlist = [mflat.as_strided(p.shape, p.stride(), mflat.storage_offset() + (p.data_ptr() - pflat.data_ptr()) // 4)
+             for p in plist]
+    params = torch.cat([p.reshape(-1).float().cpu() for p in plist])
+    momentum = torch.cat([m.reshape(-1).float().cpu() for m in mlist])
+    if params.numel() > DUMP_PARAMS:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(params.numel(), DUMP_PARAMS, replace=False)))
+        params, momentum = params[idx], momentum[idx]
+    stats = [b.detach().reshape(-1).float().cpu() for _, b in ts.model.named_buffers() if b.is_floating_point()]
+    arrays = {"loss": np.array([ts.loss()], dtype=np.float32),
+              "logits": ts.logits().float().cpu().numpy(),
+              "params": params.numpy(),
+              "momentum": momentum.numpy(),
+              "bn_running_stats": (torch.cat(stats) if stats else torch.zeros(0)).numpy()}
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float32))
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -633,9 +757,15 @@ def main():
                     help="per-GPU batch; default 256 for every N (BASELINE configs[1] at N = 1; N > 1 is its WEAK scaling: the "
                          "per-GPU work of the N = 1 line, global batch 256*N)")
     ap.add_argument("--config3-batch", type=int, default=None,
-                    help="N > 1: per-GPU batch of the additional BASELINE configs[2] measurement carried by the same line "
+                    help="(--full) N > 1: per-GPU batch of the additional BASELINE configs[2] measurement carried by the same line "
                          "(`config3`; default 128 = global batch 1024 on 8 GPUs when --batch is left at its default, else off; 0: off)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip configs[3] / configs[4] and the batch-128 step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need (roofline in situ, rocprofv3 counters, "
+                         "secondary configs, CPU baseline; N > 1: single-GPU denominators, exposed exchange, configs[2])")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, logits, parameters, momentum, "
+                         "BatchNorm running statistics) as float32 DIR/<name>.npy")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip configs[3] / configs[4] and the batch-128 step")
     ap.add_argument("--exchange", default="allreduce", choices=["allreduce", "sharded"],
                     help="gradient exchange: f32 all-reduce per bucket (default) or reduce-scatter -> sharded SGD -> "
                          "bf16 all-gather of the weights (SURVEY 8e)")
@@ -649,7 +779,7 @@ def main():
                     help="replay captured hipGraphs (default: native executor with the filter gradients on a "
                          "side stream, which measured faster: hipGraph serialises the forked branches)")
     ap.add_argument("--no-graphs", action="store_true", help="(default) kept for compatibility")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--bucket-mb", type=float, default=16.0)
     ap.add_argument("--sync-bn", action="store_true",
                     help="SyncBatchNorm as in the reference recipe (configs/base.yaml:22); off for the headline "
@@ -660,7 +790,13 @@ def main():
                          "21.86 -> 21.71 and 22.14 -> 22.00 ms on two boxes), 0 with --gpus N > 1, where the RCCL "
                          "kernels of the gradient exchange run on normal-priority streams and must not be starved "
                          "by the step (not measurable on a one-GPU box)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 child runs that measure `traffic`")
+    ap.add_argument("--no-pmc", action="store_true", help="(--full) skip the rocprofv3 child runs (`traffic`, `launch_ms_rocprof`)")
+    ap.add_argument("--lr", type=float, default=0.0,
+                    help="SGD step size of the timed steps.  Default 0: every launch, byte and FLOP of the step (the SGD "
+                         "kernel still reads the gradients and momentum and writes parameters, momentum and bf16 mirror), but "
+                         "the weights stay put, so the float-atomic order noise of one step does not feed the next and a run "
+                         "reproduces its outputs to rounding.  The reference recipe's 0.05 trains this one batch; its outputs "
+                         "then drift from run to run over tens of steps")
     ap.add_argument("--deterministic", action="store_true",
                     help="bit-identical parameter updates (two-stage filter gradients, fixed-point bias sums): ~3 %% slower")
     ap.add_argument("--steps-only", action="store_true",
@@ -670,6 +806,8 @@ def main():
                     help="(tests) build the launch lists and the bucket plan on the CPU, run the first collectives "
                          "over the given backend and exit: exercises the N>1 launch path without a GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.config3_batch is None:
         args.config3_batch = 128 if args.batch is None else 0
     if args.batch is None:
@@ -774,7 +912,7 @@ def main():
                     N.lib().vt_comm_destroy()
                 except Exception:  # noqa: BLE001
                     pass
-    ts = TrainStep(bb, 1000, args.batch, args.image_size, torch.bfloat16, lr=0.05, momentum=0.9, weight_decay=2e-5,
+    ts = TrainStep(bb, 1000, args.batch, args.image_size, torch.bfloat16, lr=args.lr, momentum=0.9, weight_decay=2e-5,
                    label_smoothing=0.1, device=dev, bucket_mb=args.bucket_mb, use_graphs=args.graphs,
                    sync_bn=args.sync_bn, deterministic=True if args.deterministic else None, exchange=args.exchange,
                    collectives=coll)
@@ -816,10 +954,16 @@ def main():
         elapsed = float(t.item())
     loss = ts.loss()
     assert N.launch_count() > launches0 and loss == loss, "HIP path did not run / loss is NaN"
+    dumped = None
+    if args.dump_outputs:  # (before anything below runs the step's lists again)
+        if ts.exchange == "sharded":
+            ts.gather_master()  # (a collective: every rank)
+        if rank == 0:
+            dumped = dump_outputs(ts, args.dump_outputs)
 
     # ---- N > 1: the line carries its own denominators (no RCCL N > 1 run exists on a one-GPU box: DESIGN 6) ---------
     exposed_ms = n1_ms = None
-    if world > 1 and not args.steps_only:
+    if world > 1 and args.full and not args.steps_only:
         # (a) what the gradient exchange leaves exposed: the same data-parallel schedule (cut lists, stream ordering)
         #     with the collectives not issued, every rank, max over ranks
         with ts.exchange_skipped():  # (restores parameters / momentum / BatchNorm state afterwards: ADVICE r04)
@@ -838,16 +982,16 @@ def main():
         # (b) the weak-scaling denominator: rank 0 alone times the single-GPU program at the same per-GPU batch (same
         #     stream priority as the run above) while the other ranks wait at the barrier
         if rank == 0:
-            n1_ms, _ = time_train_step(args.model, args.batch, args.image_size, args.steps, args.warmup, dev)
+            n1_ms, _ = time_train_step(args.model, args.batch, args.image_size, args.steps, args.warmup, dev, lr=args.lr)
         barrier()
 
     # ---- N > 1: BASELINE configs[2] itself (128 images per GPU: global batch 1024 on 8 GPUs) in the same run ---------------
     config3 = None
-    if world > 1 and not args.steps_only and args.config3_batch > 0 and args.config3_batch != args.batch:
+    if world > 1 and args.full and not args.steps_only and args.config3_batch > 0 and args.config3_batch != args.batch:
         b3 = args.config3_batch
         k3, w3 = min(args.steps, 50), min(args.warmup, 10)
         torch.manual_seed(0)
-        ts3 = TrainStep(getattr(backbones, args.model)(), 1000, b3, args.image_size, torch.bfloat16, lr=0.05, momentum=0.9,
+        ts3 = TrainStep(getattr(backbones, args.model)(), 1000, b3, args.image_size, torch.bfloat16, lr=args.lr, momentum=0.9,
                         weight_decay=2e-5, label_smoothing=0.1, device=dev, bucket_mb=args.bucket_mb, use_graphs=args.graphs,
                         sync_bn=args.sync_bn, deterministic=True if args.deterministic else None, exchange=args.exchange,
                         collectives=coll)
@@ -871,7 +1015,7 @@ def main():
         torch.cuda.empty_cache()
         n1_3 = None
         if rank == 0:
-            n1_3, _ = time_train_step(args.model, b3, args.image_size, k3, w3, dev)
+            n1_3, _ = time_train_step(args.model, b3, args.image_size, k3, w3, dev, lr=args.lr)
         barrier()
         if rank == 0:
             v3 = b3 * world * k3 / el3
@@ -895,48 +1039,6 @@ def main():
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         value = args.batch * world * args.steps / elapsed
-        # Dominant kernel: the two-group + loader-wave span kernel (vt_igemm_span6.hip) on the stride-1 3x3 convs and
-        # their data gradients.  Every roofline entry of the three dominant 3x3 shapes (128 -> 128 @28x28 x8,
-        # 256 -> 256 @14x14 x8, 512 -> 512 @7x7 x4) is measured IN SITU: events around those launches inside the step's own
-        # forward / backward lists, for the forward conv, the data gradient and the filter gradient.
-        scale = args.image_size / 224.0
-        shapes = [(128, 128, 9, int(round(28 * scale)), 8), (256, 256, 9, int(round(14 * scale)), 8),
-                  (512, 512, 9, int(round(7 * scale)), 4)] if args.model in ("cspdarknet53", "darknet53") else []
-        layers, tot_fl, tot_ms, insitu = [], 0.0, 0.0, None
-        for (ci, co, nt, hw, cnt) in shapes:
-            fl = 2.0 * args.batch * hw * hw * co * nt * ci
-            row = {"layer": f"conv3x3 s1 {ci}->{co} @{hw}x{hw} B={args.batch} (M={args.batch * hw * hw} N={co} K={nt * ci})",
-                   "launches_per_step": cnt, "gflop": round(fl / 1e9, 2)}
-            for which in ("fwd", "dgrad", "wgrad"):
-                ms_l, n_l, kname = insitu_layer_times(ts, ci, co, nt, hw, reps=3, which=which)
-                if not ms_l:
-                    continue
-                row[which] = {"ms": round(ms_l, 4), "tflops": round(fl / ms_l / 1e9, 1),
-                              "frac": round(fl / ms_l / 1e9 / PEAK_BF16_TFLOPS, 4), "kernel": kname, "launches_timed": n_l}
-                tot_fl += cnt * fl
-                tot_ms += cnt * ms_l
-                if which == "fwd" and insitu is None:
-                    insitu = {"ms": ms_l, "n": n_l, "kernel": kname, "tflops": fl / ms_l / 1e9, "flops": fl, "shape": row["layer"]}
-            layers.append(row)
-        if args.model == "cspdarknet53" and args.image_size == 224:
-            # the stride-2 3x3 convs that open the stages (24.8 % of the MACs): forward and filter gradient in situ
-            layers += layer_rows(ts, args.batch, [(32, 64, 9, 224, 2, 1, ("fwd", "wgrad")), (64, 128, 9, 112, 2, 1, ("fwd", "wgrad")),
-                                                  (128, 256, 9, 56, 2, 1, ("fwd", "wgrad")), (256, 512, 9, 28, 2, 1, ("fwd", "wgrad")),
-                                                  (512, 1024, 9, 14, 2, 1, ("fwd", "wgrad"))])
-        standalone = conv_roofline(args.batch, 128, 28, N.VT_BF16)
-        standalone_name = N.last_kernel_name()
-        dom = insitu or {"ms": standalone["ms"], "n": 30, "kernel": standalone_name, "tflops": standalone["tflops"],
-                         "flops": standalone["flops"], "shape": standalone["shape"]}
-        traffic = None
-        if world == 1 and not args.no_pmc:
-            # (the rocprof rows are matched by the name the dispatcher reported for this layer, e.g. "span6_kernel")
-            traffic = pmc_traffic_live("128,128,3,1,28", (standalone_name or dom["kernel"]).split("<")[0])
-        rocprof_avg = None
-        if world == 1 and not args.no_pmc and insitu is not None and args.model == "cspdarknet53" and args.batch == 256:
-            # (MODE 1 = the statistics epilogue = the forward launches; 8 DarknetBlock.conv2 units of stage 2 per step)
-            rocprof_avg = rocprof_launch_avg_live("span6_kernel<1,", 8)
-        # HBM-bound layers of stages 0-1 as the step runs them, in situ (HBM fraction on the early-stage convs)
-        hbm_layers = hbm_layers_insitu(ts, args.batch) if args.model == "cspdarknet53" and args.image_size == 224 else []
         cfg = ("BASELINE configs[1]" if (world == 1 and args.batch == 256) else
                (f"weak scaling of BASELINE configs[1]: data parallel over RCCL, {args.batch} images per GPU, global batch "
                 f"{args.batch * world}; BASELINE configs[2] ({args.config3_batch} per GPU) in `config3`" if config3 else
@@ -963,38 +1065,18 @@ def main():
                        "gradient_exchange": args.exchange if world > 1 else None,
                        "collectives": (ts_collectives if world > 1 else None),
                        "hip_graphs": bool(args.graphs), "main_stream_priority": args.main_priority,
-                       "sync_bn": bool(args.sync_bn), "deterministic": bool(ts.deterministic),
+                       "sync_bn": bool(args.sync_bn), "deterministic": bool(ts.deterministic), "lr": args.lr,
                        "final_loss": round(loss, 4)},
-            "roofline": {"bound": "mfma", "achieved": round(dom["tflops"], 1), "peak": PEAK_BF16_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(dom["tflops"] / PEAK_BF16_TFLOPS, 4),
-                         # MAC-weighted over the three dominant 3x3 shapes x {forward, data gradient, filter gradient}:
-                         # total FLOPs of those launches / their total in-situ time / peak -- not the best case
-                         "frac_fwd_dgrad_wgrad": round(tot_fl / tot_ms / 1e9 / PEAK_BF16_TFLOPS, 4) if tot_ms else None,
-                         "traffic": traffic["bytes"] if traffic else None,
-                         "traffic_source": ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, FETCH x2 on gfx950) "
-                                            "run by this bench on tools/bench_conv.py: STANDALONE launches of this layer "
-                                            "back to back (x and the filter re-read from the memory-side cache where the step's "
-                                            "own launch finds what the previous kernels left), while launch_ms / frac are in situ"
-                                            if traffic else None),
-                         "algorithmic_bytes": 2.0 * (args.batch * 28 * 28 * 256 + 128 * 1152),
-                         "kernel": dom["kernel"], "launch_ms": round(dom["ms"], 4), "launches_timed": dom["n"],
-                         # the same launches as rocprofv3's kernel trace of the step sees them (kernel start to end,
-                         # without the launch boundary the in-situ HIP events include) and the fraction that follows
-                         "launch_ms_rocprof": round(rocprof_avg["ms"], 4) if rocprof_avg else None,
-                         "frac_rocprof": round(dom["flops"] / (rocprof_avg["ms"] * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4)
-                         if rocprof_avg else None,
-                         "rocprof_source": ({k: rocprof_avg[k] for k in ("launches", "kernel_symbol", "lds_bytes")}
-                                            if rocprof_avg else None),
-                         "measured": "in situ (events around the layer's launches inside the step's forward list)"
-                         if insitu else "standalone", "layer": dom["shape"]},
-            "roofline_layers": layers,
             "ms_per_step_p10_p50_p90": [round(float(v), 3) for v in
                                         _percentiles([marks[i].elapsed_ms(marks[i + 1]) for i in range(args.steps)])],
-            "roofline_hbm_layers": hbm_layers,
             "train_step_tflops": round(28.0e9 * (args.batch / 1.0) * world / (ms * 1e-3) / 1e12, 1)
             if args.model == "cspdarknet53" and args.image_size == 224 else None,
         }
-        if world > 1:
+        if dumped is not None:
+            out["dump_outputs"] = dumped
+        if args.full:
+            out.update(roofline_measurements(ts, args, world))
+        if world > 1 and args.full:
             n1_ips = args.batch / n1_ms * 1e3
             out["n1_same_per_gpu_batch_ms"] = round(n1_ms, 3)
             out["n1_same_per_gpu_batch_images_per_sec"] = round(n1_ips, 1)
@@ -1004,17 +1086,17 @@ def main():
                                             "not issued (max over ranks); the N = 1 figures are rank 0 alone, same per-GPU batch")
             if config3:
                 out["config3"] = config3
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             del ts
             torch.cuda.empty_cache()
             if args.batch != 128:
                 # the weak-scaling denominator of configs[2]: the same step at 128 images on this one GPU (and the
                 # place where host-issue limits would show: half the GPU time per step, the same 600 launches)
-                ms128, _ = time_train_step(args.model, 128, args.image_size, args.steps, args.warmup, dev)
+                ms128, _ = time_train_step(args.model, 128, args.image_size, args.steps, args.warmup, dev, lr=args.lr)
                 out["n1_same_per_gpu_batch_ms"] = round(ms128, 3)
                 out["n1_same_per_gpu_batch_images_per_sec"] = round(128 / ms128 * 1e3, 1)
-            out["secondary"] = secondary_configs(dev)
-        if world == 1 and not args.no_cpu_baseline:
+            out["secondary"] = secondary_configs(dev, args.lr)
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     barrier()

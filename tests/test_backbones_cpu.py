@@ -218,9 +218,9 @@ def test_config1_darknet19_forward_on_cpu(golden_dir):
 @pytest.mark.parametrize("mode", ["train", "eval"])
 def test_necks_cpu_vs_reference(golden_dir, mode):
     """FPN / PAN on CPU tensors (same dispatch rule) against the unmodified reference's fixtures"""
-    from test_necks import CASES, _case, _inputs, _loss, _make  # same case table as the oracle / GPU tests
+    from test_necks import CASES, _case, _inputs, _loss, _make, load_fixtures  # same case table as the oracle / GPU tests
 
-    g = np.load(golden_dir / "necks.npz")
+    g = load_fixtures(golden_dir)
     for name in CASES:  # (round 6: fuse_fn="concat" and interpolation_mode="bilinear" cases too)
         kind, ins, outc, td, sizes, B, fuse, interp = _case(name)
         m = _make(necks, name)

@@ -1,18 +1,19 @@
 """Checkpoint interop: the YOLOv5 key grammar of scripts/convert_yolov5_weights.py:6-52,
-extras.extract_backbone_weights (extras.py:112-128), and save -> reference format -> load round trips."""
+extras.extract_backbone_weights (extras.py:112-128), and save -> reference format -> load round trips.
+
+What the unmodified reference makes of the files this package writes (its converter's output keys, its backbones'
+state_dict and feature maps after loading them) is recorded by tools/gen_golden_checkpoint.py in
+tests/golden/checkpoint_*.npz."""
 import hashlib
-import importlib.util
 import json
-import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 import torch
 
 from oracle import filler
 from vision_toolbox import backbones, checkpoint
-
-REF = Path("/root/reference")
 
 
 @pytest.fixture(scope="module")
@@ -20,15 +21,13 @@ def manifest(golden_dir):
     return json.loads((golden_dir / "manifest.json").read_text())
 
 
-def _reference_converter():
-    spec = importlib.util.spec_from_file_location("ref_convert", REF / "scripts" / "convert_yolov5_weights.py")
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+def _gold(golden_dir, stem):
+    with np.load(golden_dir / f"checkpoint_{stem}.npz") as z:
+        return {k: z[k] for k in z.files}
 
 
 @pytest.mark.parametrize("variant", ["n", "x"])
-def test_yolov5_key_grammar(variant, manifest, tmp_path):
+def test_yolov5_key_grammar(variant, manifest, tmp_path, golden_dir):
     keys = [k for k, _ in manifest[f"darknet_yolov5{variant}"]["keys"]]
     mapped = [checkpoint.toolbox_to_yolov5_key(k) for k in keys]
     assert len(set(mapped)) == len(keys)
@@ -42,17 +41,17 @@ def test_yolov5_key_grammar(variant, manifest, tmp_path):
         assert checkpoint.toolbox_to_yolov5_key(k) == v and checkpoint.yolov5_to_toolbox_key(v) == k
     with pytest.raises(ValueError, match="Unexpected weight name"):
         checkpoint.toolbox_to_yolov5_key("head.weight")
-    if REF.exists():  # build container only: the unmodified script must produce the same file
-        m = getattr(backbones, f"darknet_yolov5{variant}")()
-        src, a, b = tmp_path / "src.pth", tmp_path / "a.pth", tmp_path / "b.pth"
-        checkpoint.save_backbone(m, src)
-        _reference_converter().convert_weights(str(src), str(a))
-        checkpoint.convert_yolov5_weights(src, b, verbose=False)
-        sa, sb = torch.load(a), torch.load(b)
-        assert list(sa) == list(sb) and all(torch.equal(sa[k], sb[k]) for k in sa)
-        checkpoint.convert_yolov5_weights(b, tmp_path / "c.pth", to="toolbox", verbose=False)
-        sc, ss = torch.load(tmp_path / "c.pth"), torch.load(src)
-        assert list(sc) == list(ss) and all(torch.equal(sc[k], ss[k]) for k in ss)
+    # the unmodified script must produce the same file: its keys, in its order, and every tensor passed through as is
+    m = getattr(backbones, f"darknet_yolov5{variant}")()
+    src, b = tmp_path / "src.pth", tmp_path / "b.pth"
+    checkpoint.save_backbone(m, src)
+    checkpoint.convert_yolov5_weights(src, b, verbose=False)
+    ss, sb = torch.load(src), torch.load(b)
+    assert list(sb) == [str(k) for k in _gold(golden_dir, "convert")[f"convert/{variant}/keys"]]
+    assert len(sb) == len(ss) and all(torch.equal(sb[k], ss[k0]) for k, k0 in zip(sb, ss))
+    checkpoint.convert_yolov5_weights(b, tmp_path / "c.pth", to="toolbox", verbose=False)
+    sc = torch.load(tmp_path / "c.pth")
+    assert list(sc) == list(ss) and all(torch.equal(sc[k], ss[k]) for k in ss)
 
 
 def test_extract_backbone_weights(tmp_path):
@@ -74,12 +73,9 @@ def test_extract_backbone_weights(tmp_path):
         torch.testing.assert_close(fresh(x), bb(x))
 
 
-@pytest.mark.skipif(not REF.exists(), reason="the reference checkout exists only in the build container")
 @pytest.mark.parametrize("name", ["cspdarknet53", "darknet_yolov5n", "vovnet19_slim_ese"])
-def test_saved_checkpoint_loads_into_the_unmodified_reference(name, tmp_path):
-    sys.path.insert(0, str(Path(__file__).resolve().parents[1] / "tools"))
-    import gen_golden as G  # imports the unmodified reference behind the torchvision shim
-
+def test_saved_checkpoint_loads_into_the_unmodified_reference(name, tmp_path, golden_dir, manifest):
+    gold = _gold(golden_dir, name)
     ours = getattr(backbones, name)()
     filler.fill_module(ours, "rt.")
     ours._vt_runner().store.ensure(torch.device("cpu"))  # flat channels_last storage, as after a GPU run
@@ -87,16 +83,22 @@ def test_saved_checkpoint_loads_into_the_unmodified_reference(name, tmp_path):
     checkpoint.save_backbone(ours, path)
     sd = torch.load(path)
     assert all(v.is_contiguous() for v in sd.values())
-    ref = G.FACTORIES[name]()
-    ref.load_state_dict(sd)  # strict: same keys, same OIHW shapes
+    # what the reference's strict load_state_dict() checks: same keys, same OIHW shapes as its own state_dict
+    ref_keys = [str(k) for k in gold[f"rt/{name}/keys"]]
+    assert sorted(sd) == sorted(ref_keys)
+    assert {k: list(sh) for k, sh in manifest[name]["keys"]} == {k: list(v.shape) for k, v in sd.items()}
     x = filler.images(2, 64)
-    ours.eval(), ref.eval()
+    ours.eval()
     with torch.no_grad():
-        a, b = ours.get_feature_maps(x), ref.get_feature_maps(x)
+        a = ours.get_feature_maps(x)
+    b = [torch.from_numpy(gold[f"rt/{name}/map{i}"]) for i in range(len(a))]  # the reference on the loaded file
+    assert f"rt/{name}/map{len(a)}" not in gold
     for u, v in zip(a, b):
+        assert u.shape == v.shape
         assert ((u - v).norm() / v.norm()).item() < 1e-5  # (channels_last filter strides pick another ATen kernel)
-    # and back: a file written by the reference loads here
-    torch.save(ref.state_dict(), tmp_path / "ref.pth")
+    # and back: a file written by the reference (its state_dict: its key order and dtypes, the values it loaded) loads here
+    dtypes = dict(zip(ref_keys, (str(d) for d in gold[f"rt/{name}/dtypes"])))
+    torch.save({k: sd[k].to(getattr(torch, dtypes[k].split(".")[-1])) for k in ref_keys}, tmp_path / "ref.pth")
     again = getattr(backbones, name)()
     again.load_state_dict(torch.load(tmp_path / "ref.pth"))
     with torch.no_grad():

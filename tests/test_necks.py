@@ -1,7 +1,7 @@
 """FPN / PAN necks.
 
 CPU: the oracle's restatement (oracle/torch_ref.py fpn / pan) against fixtures produced by the
-unmodified reference (tools/gen_golden_necks.py -> tests/golden/necks.npz), and the state_dict
+unmodified reference (tools/gen_golden_necks.py -> tests/golden/necks_<case>.npz), and the state_dict
 contract of the shipped modules.  GPU: the shipped modules against the same fixtures (f32 kernels:
 5e-5 / 2e-4; bf16 kernels: 3e-2 relative L2 against the f32 reference values)."""
 from pathlib import Path
@@ -13,7 +13,7 @@ import torch
 from oracle import filler
 from oracle import torch_ref as R
 
-GOLDEN = Path(__file__).parent / "golden" / "necks.npz"
+GOLDEN = Path(__file__).parent / "golden"  # necks_<case>.npz: one file per entry of CASES
 CASES = {  # must match tools/gen_golden_necks.py
     "fpn_td": ("fpn", (16, 32, 64), 32, True, (16, 8, 4), 2),
     "fpn_bu": ("fpn", (16, 32, 64), 32, False, (16, 8, 4), 2),
@@ -41,9 +41,18 @@ def _make(necks, name):
     return necks.PAN(list(ins), outc, fuse_fn=fuse, interpolation_mode=interp)
 
 
+def load_fixtures(golden_dir=GOLDEN):
+    """every case's arrays in one mapping, keyed "<case>/..." """
+    out = {}
+    for name in CASES:
+        with np.load(golden_dir / f"necks_{name}.npz") as z:
+            out.update({k: z[k] for k in z.files})
+    return out
+
+
 @pytest.fixture(scope="module")
 def gold():
-    return np.load(GOLDEN)
+    return load_fixtures()
 
 
 def rel(a, b):

@@ -270,7 +270,7 @@ def test_bench_n2_falls_back_together_when_the_library_communicator_cannot_be_ma
     """`bench.py --gpus 2` takes the in-list collectives (the library's own RCCL communicator) on the nccl backend; when the
     communicator cannot be made the ranks AGREE on that and run the torch.distributed form instead.  Two ranks on this one GPU
     over gloo with the rccl branch forced (VT_BENCH_AUTO_RCCL=1): RCCL refuses two ranks on one device (`vt_comm_init: invalid
-    usage` on both), both report the fall-back, and the JSON line of the run says `"collectives": "torch"` and carries the
+    usage` on both), both report the fall-back, and the JSON line of the `--full` run says `"collectives": "torch"` and carries the
     self-contained N > 1 keys."""
     import json
     import os
@@ -288,7 +288,7 @@ def test_bench_n2_falls_back_together_when_the_library_communicator_cannot_be_ma
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), str(root / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup",
-                        "1", "--batch", "16", "--config3-batch", "8"], capture_output=True, text=True, timeout=900, env=env,
+                        "1", "--batch", "16", "--config3-batch", "8", "--full"], capture_output=True, text=True, timeout=900, env=env,
                        cwd=str(root))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     assert r.stderr.count("falling back to torch.distributed") == 2, r.stderr[-3000:]

@@ -1,4 +1,4 @@
-"""Generate tests/golden/necks.npz by running the UNMODIFIED reference necks (FPN / PAN,
+"""Generate tests/golden/necks_<case>.npz (one file per case) by running the UNMODIFIED reference necks (FPN / PAN,
 vision_toolbox/necks.py) on CPU.  Same shim as tools/gen_golden.py; run in the build container.
 
     python tools/gen_golden_necks.py
@@ -70,8 +70,9 @@ def main():
                 for k, v in m.state_dict().items():
                     if k.endswith(("running_mean", "running_var", "num_batches_tracked")):
                         out[f"{name}/train/state/{k}"] = np_(v)
-    np.savez_compressed(GOLDEN / "necks.npz", **out)
-    print(f"wrote {GOLDEN / 'necks.npz'}: {len(out)} arrays")
+    for name in CASES:  # one file per case: each stays well under the size limit of a committed file
+        np.savez_compressed(GOLDEN / f"necks_{name}.npz", **{k: v for k, v in out.items() if k.startswith(name + "/")})
+    print(f"wrote {GOLDEN}/necks_<case>.npz: {len(out)} arrays in {len(CASES)} files")
 
 
 if __name__ == "__main__":

@@ -24,5 +24,5 @@ timeout -k 10 400 python3 tools/profile_ops.py vovnet39 256 40 > "$OUT/${TAG}_op
 echo "ops profile vovnet exit $?"
 bash tools/span6_phases.sh "$TAG" > "$OUT/${TAG}_phases.log" 2>&1
 echo "phases exit $?"
-timeout -k 10 900 python3 bench.py > "$OUT/${TAG}_bench_line.json" 2> "$OUT/${TAG}_bench_stderr.log"
+timeout -k 10 900 python3 bench.py --full > "$OUT/${TAG}_bench_line.json" 2> "$OUT/${TAG}_bench_stderr.log"
 echo "bench exit $?"; cut -c1-1500 "$OUT/${TAG}_bench_line.json"

@@ -15,7 +15,7 @@ done
 cat "$OUT/conv.log"
 for rep in 1 2; do
   for m in 1 2; do
-    VT_SPAN6_MASK=$m timeout -k 10 400 python3 bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-secondary > "$OUT/bench_m${m}_$rep.json" 2>/dev/null
+    VT_SPAN6_MASK=$m timeout -k 10 400 python3 bench.py --steps 40 --warmup 10 --full --no-cpu-baseline --no-secondary > "$OUT/bench_m${m}_$rep.json" 2>/dev/null
     python3 - "$OUT/bench_m${m}_$rep.json" $m <<'EOF'
 import json,sys
 d=json.load(open(sys.argv[1])); r=d["roofline"]
