@@ -149,6 +149,34 @@ int vt_dwconv_dgrad(const void* dz, int32_t lddz, const float* w, void* dx, int3
 int vt_dwconv_wgrad(const void* x, int32_t ldx, const void* dz, int32_t lddz, float* dw, int32_t B, int32_t Hi, int32_t Wi,
                     int32_t C, int32_t k, int32_t s, int32_t pad, int32_t dil, int32_t dtype, void* stream);
 
+/* LayerNorm over the channel axis of an NHWC map and LayerScale + residual (ConvNeXt: reference backbones/convnext.py:48,
+ * 53, 58, 74, 84, 101 -- nn.LayerNorm(C) on (B, H, W, C), `x + gamma * layers(x)`).  Operands are [M][C] rows with a pixel
+ * stride ld >= C (channel slices work), C a multiple of 8 (bf16) / 4 (f32) and at most 6144 (bf16) / 3072 (f32); gamma / beta /
+ * pre_bias are f32 masters.  Streaming kernels: a row is owned by a group of lanes of one wave, statistics in f32, two-pass
+ * over the row held in registers (mean, then sum (u - mean)^2; biased variance).
+ *   vt_layernorm_fwd:  y = (u - mean) rstd gamma + beta, u = x (+ pre_bias: the bias of the convolution in front, which the
+ *                      depthwise kernels do not add themselves)
+ *   vt_layernorm_bwd:  dx = rstd (g - mean_c(g) - xhat mean_c(g xhat)) (+ residual, which may alias dx), g = dy gamma; mean
+ *                      and rstd are recomputed from x.  `sums` (VT_CHANNEL_SUMS_BYTES(3, C) bytes, zeroed by the caller):
+ *                      row 0 += sum_m dy xhat (d gamma), row 1 += sum_m dy (d beta), row 2 += sum_m dx without the
+ *                      residual (d pre_bias; only when pre_bias is given)
+ *   vt_scale_residual_fwd:  y = residual + gamma t (gamma NULL: y = residual + t)
+ *   vt_scale_residual_bwd:  dt = dy gamma; `sums` (VT_CHANNEL_SUMS_BYTES(1, C)): row 0 += sum_m dy t (d gamma)
+ *   vt_channel_sums_to_f32: dst_k[c] += sum over the replicas of row k (k < rows <= 3; a NULL dst_k is skipped)
+ * A channel-sums buffer is int64[VT_STAT_REPLICAS][rows][C][2], the fixed-point format of the statistics buffers
+ * (VT_STAT_REPLICAS): integer atomics, so these parameter gradients are bit-identical from run to run. */
+#define VT_CHANNEL_SUMS_BYTES(rows, C) ((int64_t)VT_STAT_REPLICAS * (rows) * (C) * 16)
+int vt_layernorm_fwd(const void* x, int32_t ldx, const float* pre_bias, const float* gamma, const float* beta, void* y,
+                     int32_t ldy, int64_t M, int32_t C, float eps, int32_t dtype, void* stream);
+int vt_layernorm_bwd(const void* dy, int32_t lddy, const void* x, int32_t ldx, const float* pre_bias, const float* gamma,
+                     void* dx, int32_t lddx, const void* residual, int32_t ldr, float* sums, int64_t M, int32_t C, float eps,
+                     int32_t dtype, void* stream);
+int vt_scale_residual_fwd(const void* t, int32_t ldt, const float* gamma, const void* residual, int32_t ldr, void* y,
+                          int32_t ldy, int64_t M, int32_t C, int32_t dtype, void* stream);
+int vt_scale_residual_bwd(const void* dy, int32_t lddy, const void* t, int32_t ldt, const float* gamma, void* dt,
+                          int32_t lddt, float* sums, int64_t M, int32_t C, int32_t dtype, void* stream);
+int vt_channel_sums_to_f32(const float* sums, int32_t rows, int32_t C, float* dst0, float* dst1, float* dst2, void* stream);
+
 /* Filter gradient: dw[n][t][c] += sum_pixels dz(pix,n) * x_gathered(pix,t,c),
  * fp32 accumulation straight into the (channels_last) .grad of the weight.
  * `d` is the forward descriptor (ldy = pixel stride of dz).  Replaces the
@@ -558,6 +586,11 @@ enum vt_op_kind {
     VT_OP_DWCONV_WGRAD,     /* vt_dwconv_wgrad */
     VT_OP_PW_APPLY_FIN,      /* vt_pw_fwd_apply_finalize */
     VT_OP_PW_BWD_FIN,        /* vt_pw_bwd_apply_finalize */
+    VT_OP_LAYERNORM_FWD,     /* vt_layernorm_fwd */
+    VT_OP_LAYERNORM_BWD,     /* vt_layernorm_bwd */
+    VT_OP_SCALE_RES_FWD,     /* vt_scale_residual_fwd */
+    VT_OP_SCALE_RES_BWD,     /* vt_scale_residual_bwd */
+    VT_OP_CHANNEL_SUMS,      /* vt_channel_sums_to_f32 */
     VT_OP_KIND_END
 };
 

@@ -218,6 +218,19 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
                                    I[10], I[11], st);
         case VT_OP_DWCONV_WGRAD:  // ptr: x dz dw | i: ldx lddz _ B Hi Wi C k s pad dil dtype
             return vt_dwconv_wgrad(P[0], I[0], P[1], I[1], (float*)P[2], I[3], I[4], I[5], I[6], I[7], I[8], I[9], I[10], I[11], st);
+        case VT_OP_LAYERNORM_FWD:  // ptr: x pre_bias gamma beta y | i: ldx ldy C dtype | f: M eps
+            return vt_layernorm_fwd(P[0], I[0], (const float*)P[1], (const float*)P[2], (const float*)P[3], P[4], I[1],
+                                    (int64_t)F[0], I[2], (float)F[1], I[3], st);
+        case VT_OP_LAYERNORM_BWD:  // ptr: dy x pre_bias gamma dx residual sums | i: lddy ldx lddx ldr C dtype | f: M eps
+            return vt_layernorm_bwd(P[0], I[0], P[1], I[1], (const float*)P[2], (const float*)P[3], P[4], I[2], P[5], I[3],
+                                    (float*)P[6], (int64_t)F[0], I[4], (float)F[1], I[5], st);
+        case VT_OP_SCALE_RES_FWD:  // ptr: t gamma residual y | i: ldt ldr ldy C dtype | f: M
+            return vt_scale_residual_fwd(P[0], I[0], (const float*)P[1], P[2], I[1], P[3], I[2], (int64_t)F[0], I[3], I[4], st);
+        case VT_OP_SCALE_RES_BWD:  // ptr: dy t gamma dt sums | i: lddy ldt lddt C dtype | f: M
+            return vt_scale_residual_bwd(P[0], I[0], P[1], I[1], (const float*)P[2], P[3], I[2], (float*)P[4], (int64_t)F[0],
+                                         I[3], I[4], st);
+        case VT_OP_CHANNEL_SUMS:  // ptr: sums dst0 dst1 dst2 | i: rows C
+            return vt_channel_sums_to_f32((const float*)P[0], I[0], I[1], (float*)P[1], (float*)P[2], (float*)P[3], st);
         case VT_OP_BN_FIN_APPLY:  // ptr: stats gamma beta rm rv nbt scale shift mean invstd z residual y | i: C ldz ldr ldy relu dtype | f: count eps momentum M
             return vt_bn_finalize_apply((const float*)P[0], I[0], F[0], (const float*)P[1], (const float*)P[2], (float)F[1], (float)F[2],
                                         (float*)P[3], (float*)P[4], (int64_t*)P[5], (float*)P[6], (float*)P[7], (float*)P[8],

@@ -27,6 +27,11 @@ def stat_floats(C_: int) -> int:
     return VT_STAT_REPLICAS * 2 * C_ * 4
 
 
+def channel_sums_floats(rows: int, C_: int) -> int:
+    """size of a channel-sums buffer (int64[VT_STAT_REPLICAS][rows][C][2]) in 4-byte units (VT_CHANNEL_SUMS_BYTES / 4)"""
+    return VT_STAT_REPLICAS * rows * C_ * 4
+
+
 def stats_buffer(C_: int, device="cuda"):
     """a zeroed statistics buffer for C channels"""
     import torch
@@ -101,7 +106,12 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_DWCONV_WGRAD,
     OP_PW_APPLY_FIN,
     OP_PW_BWD_FIN,
-) = range(1, 49)
+    OP_LAYERNORM_FWD,
+    OP_LAYERNORM_BWD,
+    OP_SCALE_RES_FWD,
+    OP_SCALE_RES_BWD,
+    OP_CHANNEL_SUMS,
+) = range(1, 54)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -133,6 +143,11 @@ OP_NAMES = {
     OP_DWCONV_WGRAD: "dwconv_wgrad",
     OP_PW_APPLY_FIN: "pw_apply_fin",
     OP_PW_BWD_FIN: "pw_bwd_fin",
+    OP_LAYERNORM_FWD: "layernorm_fwd",
+    OP_LAYERNORM_BWD: "layernorm_bwd",
+    OP_SCALE_RES_FWD: "scale_residual_fwd",
+    OP_SCALE_RES_BWD: "scale_residual_bwd",
+    OP_CHANNEL_SUMS: "channel_sums",
     OP_SGD: "sgd",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
@@ -244,6 +259,11 @@ SYMBOLS = {
     "vt_dwconv_fwd": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp] + [_i32] * 9 + [_vp]),
     "vt_dwconv_dgrad": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _i32] + [_i32] * 9 + [_vp]),
     "vt_dwconv_wgrad": (_i32, [_vp, _i32, _vp, _i32, _vp] + [_i32] * 9 + [_vp]),
+    "vt_layernorm_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _f32, _i32, _vp]),
+    "vt_layernorm_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i64, _i32, _f32, _i32, _vp]),
+    "vt_scale_residual_fwd": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _i32, _i64, _i32, _i32, _vp]),
+    "vt_scale_residual_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _vp]),
+    "vt_channel_sums_to_f32": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "vt_bn_act_bwd_fused": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, C.c_int64, _i32, _i32, _i32, _f64, _f64, _i32, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _i32, _vp]),
     "vt_bn_bwd_fused_timeouts": (_i32, [C.POINTER(C.c_uint32)]),

@@ -1,12 +1,14 @@
-"""Backbones of the MI355X hot path: Darknet / CSPDarknet / DarknetYOLOv5 / VoVNet.
+"""Backbones of the MI355X hot path: Darknet / CSPDarknet / DarknetYOLOv5 / VoVNet / ConvNeXt.
 
 Both surfaces the reference snapshot exposes are exported: the classes with
 `from_config` (reference backbones/__init__.py:3,10, tests/test_backbones.py:25-30) and the
 named factories that classifier.py:58 / README.md:27 / the checkpoint file names use.
-The reference's other backbones (ViT, Swin, ConvNeXt, torchvision extractors, ...) are
-outside this build's scope.
+ConvNeXt (V1 on the GPU; V2's GlobalResponseNorm on CPU tensors only) is exported as the class with
+`from_config`, as the reference does (backbones/convnext.py:112).  The reference's other backbones
+(ViT, Swin, torchvision extractors, ...) are outside this build's scope.
 """
 from .base import BaseBackbone
+from .convnext import ConvNeXt, ConvNeXtBlock, GlobalResponseNorm
 from .darknet import (
     CSPDarknetStage,
     Darknet,

@@ -22,7 +22,7 @@ from typing import Optional
 import torch
 from torch import Tensor, nn
 
-__all__ = ["ConvNormAct", "HipModule"]
+__all__ = ["ConvNormAct", "HipModule", "Permute", "StochasticDepth", "LayerScale"]
 
 _RUNNERS: "weakref.WeakKeyDictionary[nn.Module, object]" = weakref.WeakKeyDictionary()
 
@@ -141,3 +141,54 @@ class ConvNormAct(nn.Sequential, HipModule):
 
     def forward(self, x: Tensor) -> Tensor:
         return HipModule.forward(self, x)
+
+
+# -- small modules of the reference's components.py that ConvNeXt's state_dict layout and CPU path need -----------------
+# (on the GPU a ConvNeXt block is a launch list -- backbones/convnext.py -- and these are never called)
+class Permute(nn.Module):
+    def __init__(self, *dims: int) -> None:
+        super().__init__()
+        self.dims = tuple(dims)
+
+    def forward(self, x: Tensor) -> Tensor:
+        return x.permute(*self.dims)
+
+    def extra_repr(self) -> str:
+        return ", ".join(str(d) for d in self.dims)
+
+
+class StochasticDepth(nn.Module):
+    """drops the whole residual branch of a sample with probability p (training only), rescaling the survivors"""
+
+    def __init__(self, p: float) -> None:
+        super().__init__()
+        p = float(p)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"p must be in [0, 1], got {p}")
+        self.p = p
+
+    def forward(self, x: Tensor) -> Tensor:
+        if not self.training or self.p == 0.0:
+            return x
+        keep = 1.0 - self.p
+        if keep == 0.0:
+            return torch.zeros_like(x)
+        mask = torch.empty((x.shape[0],) + (1,) * (x.dim() - 1), dtype=x.dtype, device=x.device).bernoulli_(keep)
+        return x * (mask / keep)
+
+    def extra_repr(self) -> str:
+        return f"p={self.p}"
+
+
+class LayerScale(nn.Module):
+    """per-channel scale over the last axis; the parameter is called `gamma`"""
+
+    def __init__(self, dim: int, init: float) -> None:
+        super().__init__()
+        self.gamma = nn.Parameter(torch.full((dim,), float(init)))
+
+    def forward(self, x: Tensor) -> Tensor:
+        return x * self.gamma
+
+    def extra_repr(self) -> str:
+        return f"dim={self.gamma.numel()}"

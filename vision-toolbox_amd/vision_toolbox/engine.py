@@ -1461,6 +1461,105 @@ class Builder:
             self.nodes.append(bwd)
         return y
 
+    # -- ConvNeXt pieces (reference backbones/convnext.py:44-58): vt_layernorm.hip ----------------------
+    def linear_unit(self, x: TRef, linear: nn.Linear, act: int = 0, name: str = "linear") -> TRef:
+        """nn.Linear over the channel axis of an NHWC map = a biased 1x1 convolution (+ activation code `act`)."""
+        import types
+
+        conv = types.SimpleNamespace(
+            kernel_size=(1, 1), stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1, in_channels=linear.in_features,
+            out_channels=linear.out_features, weight=linear.weight, bias=linear.bias)
+        return self.conv_unit(x, conv, None, act, name=name)
+
+    def depthwise_no_bias(self, x: TRef, conv: nn.Conv2d, name: str = "dwconv") -> TRef:
+        """a depthwise nn.Conv2d emitted WITHOUT its bias: the LayerNorm behind it adds the bias while it reads the row
+        (layer_norm(pre_bias=conv.bias)) instead of one more read + write pass over the map."""
+        import types
+
+        if conv.groups != conv.in_channels or conv.in_channels != conv.out_channels:
+            raise NotImplementedError("depthwise_no_bias: groups = in_channels = out_channels")
+        ns = types.SimpleNamespace(
+            kernel_size=conv.kernel_size, stride=conv.stride, padding=conv.padding, dilation=conv.dilation, groups=conv.groups,
+            in_channels=conv.in_channels, out_channels=conv.out_channels, weight=conv.weight, bias=None)
+        return self.conv_unit(x, ns, None, 0, name=name)
+
+    def layer_norm(self, x: TRef, ln: nn.LayerNorm, pre_bias: Optional[nn.Parameter] = None, out: Optional[TRef] = None,
+                   name: str = "ln") -> TRef:
+        """y = LayerNorm_C(x + pre_bias) over the channel axis of every pixel (vt_layernorm_fwd); backward in one launch
+        (vt_layernorm_bwd: statistics recomputed from x, d gamma / d beta / d pre_bias through a fixed-point channel-sums
+        buffer that vt_channel_sums_to_f32 adds to the gradients)."""
+        if tuple(ln.normalized_shape) != (x.C,) or not ln.elementwise_affine or ln.bias is None:
+            raise NotImplementedError(f"{name}: LayerNorm({ln.normalized_shape}) over a {x.C}-channel map with weight and bias")
+        if getattr(x, "logical_C", x.C) != x.C:
+            raise NotImplementedError(f"{name}: LayerNorm over a channel-padded map")
+        if x.C % _EPC[self.dtype]:
+            raise NotImplementedError(f"{name}: {x.C} channels must be a multiple of {_EPC[self.dtype]} for dtype {self.dtype}")
+        self.tag += 1
+        dt = self.dtype
+        y = out if out is not None else self.act(x.B, x.H, x.W, x.C, name + ".y")
+        assert y.same_geom(x), "out geometry mismatch"
+        pb = self.pref(pre_bias) if pre_bias is not None else None
+        gm = self.pref(ln.weight)
+        self.emit(N.OP_LAYERNORM_FWD, [x.addr(), pb, gm, self.pref(ln.bias), y.addr()], [x.ld, y.ld, x.C, dt], [x.M, ln.eps])
+        if self.need_grad:
+            tag = self.tag
+
+            def bwd():
+                self.tag = tag
+                dy = self.grad_read(y)
+                if dy is None:
+                    return
+                sums = self.zeroed_f32(N.channel_sums_floats(3, x.C), "lnsums")
+                if x.needs_grad:
+                    gx, res = self.grad_target(x)
+                else:
+                    gx, res = self.act(x.B, x.H, x.W, x.C, name + ".dx"), None
+                self.emit(N.OP_LAYERNORM_BWD,
+                          [dy.addr(), x.addr(), pb, gm, gx.addr(), res.addr() if res is not None else None, self.bp(sums)],
+                          [dy.ld, x.ld, gx.ld, res.ld if res is not None else 0, x.C, dt], [x.M, ln.eps])
+                if x.needs_grad:
+                    self.grad_written(x)
+                dsts = [self.pgrad(ln.weight), self.pgrad(ln.bias), self.pgrad(pre_bias) if pre_bias is not None else None]
+                if any(d is not None for d in dsts):
+                    self.emit(N.OP_CHANNEL_SUMS, [self.bp(sums)] + dsts, [3, x.C])
+
+            self.nodes.append(bwd)
+        return y
+
+    def scale_residual(self, t: TRef, gamma: Optional[nn.Parameter], residual: TRef, out: Optional[TRef] = None,
+                       name: str = "scale_residual") -> TRef:
+        """y = residual + gamma * t (LayerScale + shortcut; gamma None: the plain add).  Backward: the shortcut's gradient is
+        d(y) itself (grad_add), d(t) = d(y) * gamma and d gamma = sum_pixels d(y) * t in one launch (vt_scale_residual_bwd)."""
+        assert t.same_geom(residual)
+        self.tag += 1
+        dt = self.dtype
+        y = out if out is not None else self.act(t.B, t.H, t.W, t.C, name + ".y")
+        gm = self.pref(gamma) if gamma is not None else None
+        self.emit(N.OP_SCALE_RES_FWD, [t.addr(), gm, residual.addr(), y.addr()], [t.ld, residual.ld, y.ld, t.C, dt], [t.M])
+        if self.need_grad:
+            tag = self.tag
+
+            def bwd():
+                self.tag = tag
+                dy = self.grad_read(y)
+                if dy is None:
+                    return
+                self.grad_add(residual, dy)
+                if gamma is None:
+                    self.grad_add(t, dy)
+                    return
+                sums = self.zeroed_f32(N.channel_sums_floats(1, t.C), "lssums")
+                gt, res = self.grad_target(t)
+                assert res is None, "a LayerScale input has one consumer"
+                self.emit(N.OP_SCALE_RES_BWD, [dy.addr(), t.addr(), gm, gt.addr(), self.bp(sums)],
+                          [dy.ld, t.ld, gt.ld, t.C, dt], [t.M])
+                self.grad_written(t)
+                if self.pgrad(gamma) is not None:
+                    self.emit(N.OP_CHANNEL_SUMS, [self.bp(sums), self.pgrad(gamma)], [1, t.C])
+
+            self.nodes.append(bwd)
+        return y
+
     # -- ESE gate (reference vovnet.py:20-28) ---------------------------------------------
     def ese(self, x: TRef, linear: nn.Conv2d, residual: Optional[TRef] = None,
             out: Optional[TRef] = None, name="ese") -> TRef:
