@@ -513,6 +513,20 @@ int vt_mix_nchw_to_nhwc(const float* x, void* y, int32_t B, int32_t C, int32_t H
 int vt_sgd_momentum(float* p, const float* g, float* m, void* mirror, int32_t mirror_dtype,
                     int64_t n, float lr, float momentum, float weight_decay,
                     float grad_scale, const float* lr_dev, void* stream);
+/* torch.optim.AdamW (decoupled != 0) / torch.optim.Adam (decoupled == 0), single tensor, amsgrad = False, over the same
+ * flat buffers plus the second moment v; g' = g*grad_scale:
+ *   AdamW: p *= 1 - lr*wd            Adam: g' += wd*p
+ *   m = beta1*m + (1-beta1)*g';  v = beta2*v + (1-beta2)*g'*g'
+ *   p -= (lr / (1-beta1^t)) * m / (sqrt(v) / sqrt(1-beta2^t) + eps);  mirror = cast(p)
+ * `hyper` (required, device float[8], 16-byte aligned like every buffer here): [0] the learning rate, [4] the step
+ * count t as an int32, [5] 1-beta1^t, [6] sqrt(1-beta2^t).  vt_adam_tick advances t by one and refreshes [5] and [6]
+ * (in double, one thread); it runs ONCE per step in front of that step's vt_adamw launches, which only read the
+ * three values -- so every segment of a step sees the same t, and a replayed hipGraph counts by itself.  The betas
+ * are doubles because 1-beta is rounded to f32 from the double value, as torch does. */
+int vt_adam_tick(float* hyper, double beta1, double beta2, void* stream);
+int vt_adamw(float* p, const float* g, float* m, float* v, void* mirror, int32_t mirror_dtype,
+             int64_t n, double beta1, double beta2, float eps, float weight_decay,
+             float grad_scale, int32_t decoupled, const float* hyper, void* stream);
 
 /* ---- layout / precision plumbing ---------------------------------------- */
 /* rows x cols block copy with dtype conversion: dst (=|+=) src */
@@ -591,6 +605,8 @@ enum vt_op_kind {
     VT_OP_SCALE_RES_FWD,     /* vt_scale_residual_fwd */
     VT_OP_SCALE_RES_BWD,     /* vt_scale_residual_bwd */
     VT_OP_CHANNEL_SUMS,      /* vt_channel_sums_to_f32 */
+    VT_OP_ADAM_TICK,         /* vt_adam_tick (the optimiser step count, once per step) */
+    VT_OP_ADAMW,             /* vt_adamw */
     VT_OP_KIND_END
 };
 

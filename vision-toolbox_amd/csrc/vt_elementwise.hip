@@ -1403,6 +1403,87 @@ sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict
 }
 
 // ---------------------------------------------------------------------------------
+// Adam / AdamW (torch.optim, single tensor, amsgrad=False) over flat f32 buffers (+ optional mirror)
+// ---------------------------------------------------------------------------------
+// The step count lives in the HYPER buffer beside the learning rate: hyper[4] holds t as an int32, hyper[5] and
+// hyper[6] the two bias-correction scalars of that t.  One step issues several vt_adamw launches (one per
+// weight-decay segment, more under a sharded exchange) and all of them must see the same t, so a one-thread
+// launch at the head of the optimiser list advances it and the streaming kernel only reads.
+__global__ void __launch_bounds__(64)
+adam_tick_kernel(float* __restrict__ hyper, double beta1, double beta2) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    int* tp = (int*)(hyper + 4);
+    const int t = *tp + 1;
+    double p1 = 1.0, p2 = 1.0, b1 = beta1, b2 = beta2;
+    for (int e = t; e > 0; e >>= 1) {  // beta^t by squaring: a handful of double roundings, no libm call
+        if (e & 1) p1 *= b1, p2 *= b2;
+        b1 *= b1, b2 *= b2;
+    }
+    *tp = t;
+    hyper[5] = (float)(1.0 - p1);
+    hyper[6] = (float)sqrt(1.0 - p2);
+}
+
+struct AdamScalars {
+    float beta1, omb1, beta2, omb2, eps, wd, gs;  // omb = 1 - beta, rounded from double on the host
+    int decoupled;
+};
+
+__device__ static inline void adam_update(float& p, float g, float& m, float& v, const AdamScalars& a, float decay,
+                                          float step, float bc2s) {
+    g *= a.gs;
+    if (a.decoupled)
+        p *= decay;
+    else
+        g = fmaf(a.wd, p, g);
+    m = fmaf(a.beta1, m, a.omb1 * g);
+    v = fmaf(a.beta2, v, a.omb2 * g * g);
+    const float denom = sqrtf(v) / bc2s + a.eps;  // correctly rounded sqrt and divisions (no -ffast-math here)
+    p = fmaf(-step, m / denom, p);
+}
+
+template <typename MT>
+__global__ void __launch_bounds__(kThreads)
+adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+             MT* __restrict__ mirror, long n, AdamScalars a, const float* __restrict__ hyper) {
+    const float lr = hyper[0];
+    const float step = lr / hyper[5];  // lr / (1 - beta1^t)
+    const float bc2s = hyper[6];       // sqrt(1 - beta2^t)
+    const float decay = 1.f - lr * a.wd;
+    const long stride = (long)gridDim.x * kThreads * 4;
+    for (long i = ((long)blockIdx.x * kThreads + threadIdx.x) * 4; i < n; i += stride) {
+        if (i + 4 <= n) {
+            float4 pv = *(float4*)(p + i);
+            const float4 gv = *(const float4*)(g + i);
+            float4 mv = *(float4*)(m + i);
+            float4 vv = *(float4*)(v + i);
+            float* pp = (float*)&pv;
+            const float* gp = (const float*)&gv;
+            float* mp = (float*)&mv;
+            float* vp = (float*)&vv;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) adam_update(pp[e], gp[e], mp[e], vp[e], a, decay, step, bc2s);
+            *(float4*)(p + i) = pv;
+            *(float4*)(m + i) = mv;
+            *(float4*)(v + i) = vv;
+            if (mirror) {
+                if constexpr (sizeof(MT) == 2)
+                    *(uint2*)(mirror + i) = make_uint2(VecIO<bf16_t>::pack2(pp[0], pp[1]), VecIO<bf16_t>::pack2(pp[2], pp[3]));
+                else
+                    *(float4*)(mirror + i) = pv;
+            }
+        } else {
+            for (long j = i; j < n; ++j) {
+                float pj = p[j], mj = m[j], vj = v[j];
+                adam_update(pj, g[j], mj, vj, a, decay, step, bc2s);
+                p[j] = pj, m[j] = mj, v[j] = vj;
+                if (mirror) mirror[j] = from_float<MT>(pj);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------
 // layout / precision plumbing
 // ---------------------------------------------------------------------------------
 template <typename S, typename D>
@@ -2154,6 +2235,43 @@ int vt_sgd_momentum(float* p, const float* g, float* m, void* mirror, int32_t mi
         hipLaunchKernelGGL(sgd_kernel<float>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, p, g, m,
                            (float*)mirror, (long)n, lr, momentum, weight_decay, grad_scale, lr_dev);
     VT_CHECK_LAUNCH("vt_sgd_momentum");
+    return VT_OK;
+}
+
+int vt_adam_tick(float* hyper, double beta1, double beta2, void* stream) {
+    VT_REQUIRE(hyper && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, VT_ERR_INVALID,
+               "vt_adam_tick: bad argument");
+    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper, beta1, beta2);
+    VT_CHECK_LAUNCH("vt_adam_tick");
+    return VT_OK;
+}
+
+int vt_adamw(float* p, const float* g, float* m, float* v, void* mirror, int32_t mirror_dtype, int64_t n,
+             double beta1, double beta2, float eps, float weight_decay, float grad_scale, int32_t decoupled,
+             const float* hyper, void* stream) {
+    VT_REQUIRE(p && g && m && v && hyper && n > 0, VT_ERR_INVALID, "vt_adamw: bad argument");
+    VT_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.f, VT_ERR_INVALID,
+               "vt_adamw: betas in [0, 1), eps >= 0");
+    VT_REQUIRE(vt_aligned16(p) && vt_aligned16(g) && vt_aligned16(m) && vt_aligned16(v), VT_ERR_INVALID,
+               "vt_adamw: p/g/m/v must be 16-byte aligned");
+    const bool bf = mirror && mirror_dtype == VT_BF16;
+    if (mirror && !bf && mirror_dtype != VT_F32) {
+        vt_set_error("vt_adamw: mirror dtype %d", mirror_dtype);
+        return VT_ERR_UNSUPPORTED;
+    }
+    VT_REQUIRE(!mirror || ((uintptr_t)mirror & (bf ? 7 : 15)) == 0, VT_ERR_INVALID,
+               "vt_adamw: the mirror must be aligned to four of its elements");
+    AdamScalars a;
+    a.beta1 = (float)beta1, a.omb1 = (float)(1.0 - beta1), a.beta2 = (float)beta2, a.omb2 = (float)(1.0 - beta2);
+    a.eps = eps, a.wd = weight_decay, a.gs = grad_scale, a.decoupled = decoupled ? 1 : 0;
+    const unsigned blocks = flat_blocks(n, 4);
+    if (bf)
+        hipLaunchKernelGGL(adamw_kernel<bf16_t>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, p, g, m, v,
+                           (bf16_t*)mirror, (long)n, a, hyper);
+    else
+        hipLaunchKernelGGL(adamw_kernel<float>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, p, g, m, v,
+                           (float*)mirror, (long)n, a, hyper);
+    VT_CHECK_LAUNCH("vt_adamw");
     return VT_OK;
 }
 

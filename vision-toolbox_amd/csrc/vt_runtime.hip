@@ -300,6 +300,11 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
         case VT_OP_SGD:  // ptr: p g m mirror lr_dev | i: mirror_dtype | f: n lr momentum wd grad_scale
             return vt_sgd_momentum((float*)P[0], (const float*)P[1], (float*)P[2], P[3], I[0], (int64_t)F[0],
                                    (float)F[1], (float)F[2], (float)F[3], (float)F[4], (const float*)P[4], st);
+        case VT_OP_ADAM_TICK:  // ptr: hyper | f: beta1 beta2
+            return vt_adam_tick((float*)P[0], F[0], F[1], st);
+        case VT_OP_ADAMW:  // ptr: p g m v mirror hyper | i: mirror_dtype decoupled | f: n beta1 beta2 eps wd grad_scale
+            return vt_adamw((float*)P[0], (const float*)P[1], (float*)P[2], (float*)P[3], P[4], I[0], (int64_t)F[0], F[1],
+                            F[2], (float)F[3], (float)F[4], (float)F[5], I[1], (const float*)P[5], st);
         case VT_OP_COPY2D:  // ptr: src dst | i: src_dtype dst_dtype cols accumulate | f: lds ldd rows
             return vt_copy2d(P[0], I[0], (int64_t)F[0], P[1], I[1], (int64_t)F[1], (int64_t)F[2], I[2], I[3], st);
         case VT_OP_NCHW_TO_NHWC:  // ptr: x y [mix] | i: B C H W Cpad dtype

@@ -111,7 +111,9 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_SCALE_RES_FWD,
     OP_SCALE_RES_BWD,
     OP_CHANNEL_SUMS,
-) = range(1, 54)
+    OP_ADAM_TICK,
+    OP_ADAMW,
+) = range(1, 56)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -149,6 +151,8 @@ OP_NAMES = {
     OP_SCALE_RES_BWD: "scale_residual_bwd",
     OP_CHANNEL_SUMS: "channel_sums",
     OP_SGD: "sgd",
+    OP_ADAM_TICK: "adam_tick",
+    OP_ADAMW: "adamw",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -329,6 +333,8 @@ SYMBOLS = {
     "vt_softmax_xent_eval": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vt_mix_nchw_to_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "vt_sgd_momentum": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _f32, _f32, _f32, _f32, _vp, _vp]),
+    "vt_adam_tick": (_i32, [_vp, _f64, _f64, _vp]),
+    "vt_adamw": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _f64, _f64, _f32, _f32, _f32, _i32, _vp, _vp]),
     "vt_copy2d": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i64, _i32, _i32, _vp]),
     "vt_nchw_to_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_nhwc_to_nchw": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

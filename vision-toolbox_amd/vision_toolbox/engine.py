@@ -30,8 +30,8 @@ from . import _native as N
 ALIGN = 256
 
 # base ids (index into the `bases` array handed to vt_run_ops)
-ARENA, PARAMS, GRADS, STATE, MIRROR, INPUT, COUNTERS, LABELS, MOMENTUM, HYPER, ZERO_F, ZERO_B = range(12)
-NUM_BASES = 12
+ARENA, PARAMS, GRADS, STATE, MIRROR, INPUT, COUNTERS, LABELS, MOMENTUM, HYPER, ZERO_F, ZERO_B, MOMENT2 = range(13)
+NUM_BASES = 13
 
 _TORCH_DTYPE = {N.VT_F32: torch.float32, N.VT_BF16: torch.bfloat16}
 _ESIZE = {N.VT_F32: 4, N.VT_BF16: 2}
@@ -110,6 +110,9 @@ class ParamStore:
         self.device = None
         self.pflat = self.sflat = self.nflat = self.mirror = None
         self.pad_multiple = 64  # the flat parameter buffer's length is a multiple of this (sharded exchange: 64 * world)
+        # id(parameter) -> elements its slot must hold at least (zero beyond the parameter's own): a classifier head whose
+        # class count is no multiple of a 16-byte chunk is run as the next wider one over zero rows (trainer.TrainStep)
+        self.reserve: dict[int, int] = {}
         self.index: dict[int, tuple[int, int, int]] = {}  # id(tensor owner) -> (base, elem offset, numel)
         self.params: list[nn.Parameter] = []
         self._ptrs: list[tuple[torch.Tensor, int]] = []
@@ -148,10 +151,11 @@ class ParamStore:
         for p in params:
             if not p.is_floating_point():
                 raise TypeError("non floating point parameter")
-        offs, total = [], 0
+        offs, slots, total = [], [], 0
         for p in params:
             offs.append(total)
-            total += _round_up(p.numel(), 64)
+            slots.append(_round_up(max(p.numel(), self.reserve.get(id(p), 0)), 64))
+            total += slots[-1]
         self.total = total  # elements that belong to parameters (the rest of pflat is padding)
         pflat = torch.zeros(_round_up(max(total, 64), self.pad_multiple), dtype=torch.float32, device=device)
         soffs, stotal = [], 0
@@ -188,7 +192,7 @@ class ParamStore:
                 mod._buffers[name] = view
                 self.index[id(view)] = (COUNTERS, 2 * k, 1)
                 self._ptrs.append((view, view.data_ptr()))
-        self.params, self.offsets = params, offs
+        self.params, self.offsets, self.slots = params, offs, slots
         self.pflat, self.sflat, self.nflat = pflat, sflat, nflat
         self.mirror = torch.zeros(pflat.numel(), dtype=torch.bfloat16, device=device)
         self.device = device
@@ -1597,25 +1601,33 @@ class Builder:
         return y
 
     # -- classifier head + loss (reference classifier.py:58-64, 92) -----------------------
-    def xent(self, logits: TRef, label_smoothing: float, grad_scale: float, mix: bool = False) -> Buf:
+    def xent(self, logits: TRef, label_smoothing: float, grad_scale: float, mix: bool = False,
+             num_classes: Optional[int] = None) -> Buf:
+        """`num_classes` < logits.C: the head was widened to a whole 16-byte chunk over zero rows; the loss reads the
+        first `num_classes` columns and the gradient of the others is zero, so the zero rows stay zero."""
         self.tag += 1
         loss = self.zeroed_f32(64, "loss")
-        Bn, Ncls = logits.B, logits.C
+        Bn, Ncls = logits.B, logits.C if num_classes is None else num_classes
+        assert 0 < Ncls <= logits.C
         g = None
         if self.need_grad:
             gs = self._gs(logits)
             g = self._gref(logits)
             gs.init.append((logits.coff, logits.coff + logits.C))
+            if Ncls < logits.C:
+                assert g.coff == 0 and g.ld == g.C, "a widened head is a dense map of its own"
+                self.emit(N.OP_MEMSET, [g.addr()], [0], [g.M * g.C * g.esize])
         self.emit(N.OP_XENT, [logits.addr(), (LABELS, 0), self.bp(loss), g.addr() if g else None,
                               (HYPER, self.MIX_OFF) if mix else None],
                   [logits.ld, g.ld if g else 0, Bn, Ncls, self.dtype], [label_smoothing, grad_scale])
         return loss
 
-    def xent_eval(self, logits: TRef) -> Buf:
+    def xent_eval(self, logits: TRef, num_classes: Optional[int] = None) -> Buf:
         """validation (classifier.py:97-109): [loss sum without label smoothing, top-1 hits, rows] of the batch, f32[3]."""
         self.tag += 1
         out = self.zeroed_f32(64, "val_sums")
-        self.emit(N.OP_XENT_EVAL, [logits.addr(), (LABELS, 0), self.bp(out)], [logits.ld, logits.B, logits.C, self.dtype])
+        self.emit(N.OP_XENT_EVAL, [logits.addr(), (LABELS, 0), self.bp(out)],
+                  [logits.ld, logits.B, logits.C if num_classes is None else num_classes, self.dtype])
         return out
 
     # -- finish ---------------------------------------------------------------------------

@@ -5,10 +5,12 @@ training_step, :111-169 three-group SGD, configs/base.yaml:16-23 DDP) is here ON
 program per rank:
 
     images -> backbone -> global avg-pool -> linear head -> label-smoothing CE
+              (include_pool=False, ConvNeXt: the backbone's own pooled + normalised (B, C) output -> linear head)
            -> explicit backward into a persistent flat f32 gradient buffer
            -> bucketed gradient all-reduce (RCCL over xGMI); each bucket is issued as soon
               as the backward segment that completes it has been enqueued
-           -> SGD(momentum) over the flat buffers, which also refreshes the bf16 weights
+           -> the optimiser over the flat buffers, which also refreshes the bf16 weights: SGD(momentum), or
+              AdamW / Adam (optimizer=...; the step count lives on the device, see _emit_opt)
 
 The step is one launch list cut into segments at the bucket boundaries; every segment runs
 through the native executor on two streams (main + filter-gradient side stream, left open
@@ -42,6 +44,10 @@ from .program import Program, current_stream_handle
 
 _NORMS = (nn.modules.batchnorm._BatchNorm, nn.modules.instancenorm._InstanceNorm, nn.LayerNorm, nn.GroupNorm)
 GROUP_NORM, GROUP_BIAS, GROUP_OTHER = 0, 1, 2  # flat-buffer order: small, late-produced groups first
+OPTIMIZERS = ("SGD", "AdamW", "Adam")  # classifier.py:46,157-169 takes the name; RMSprop and the timm names are not built
+# HYPER buffer (16 floats): [0..3] learning rate; [4] optimiser step count t (int32 bits), [5] 1 - beta1^t,
+# [6] sqrt(1 - beta2^t), [7] free (vt_adam_tick / vt_adamw); [8..15] MixUp / CutMix block
+HYPER_STEP = 4
 
 
 class _LinearAsConv:
@@ -53,9 +59,10 @@ class _LinearAsConv:
     dilation = (1, 1)
     groups = 1
 
-    def __init__(self, linear: nn.Linear):
+    def __init__(self, linear: nn.Linear, out_channels: Optional[int] = None):
         self.weight, self.bias = linear.weight, linear.bias
-        self.out_channels, self.in_channels = linear.out_features, linear.in_features
+        # (out_channels > out_features: the rows beyond the parameter's own are zeros its slot of the flat store reserves)
+        self.out_channels, self.in_channels = out_channels or linear.out_features, linear.in_features
 
 
 def param_groups(model: nn.Module) -> dict:
@@ -158,8 +165,25 @@ class TrainStep:
         head_bucket_kb: float = 256.0,
         data_parallel: Optional[bool] = None,
         collectives: str = "torch",
+        optimizer: str = "SGD",
+        betas: "tuple[float, float]" = (0.9, 0.999),
+        eps: float = 1e-8,
+        include_pool: bool = True,
     ):
         N.lib()
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer={optimizer!r}: supported are {', '.join(OPTIMIZERS)}")
+        self.optimizer, self._betas, self._eps = optimizer, (float(betas[0]), float(betas[1])), float(eps)
+        self._adam = optimizer != "SGD"
+        self.include_pool = bool(include_pool)
+        if not self.include_pool:
+            from .backbones.convnext import ConvNeXt
+
+            # classifier.py:59-63 with include_pool=False is nn.Sequential(backbone, nn.Linear): right only where
+            # forward() already returns the pooled (B, C) vector; a map-returning family would feed nn.Linear a 4-D map
+            if not isinstance(backbone, ConvNeXt):
+                raise ValueError(f"include_pool=False needs a backbone whose forward returns (B, C) (ConvNeXt); "
+                                 f"{type(backbone).__name__} returns a feature map")
         self.device = torch.device(device if device is not None else "cuda")
         self.plan_only = plan_only  # build launch lists / bucket plan without a GPU (host-logic tests)
         if self.device.type != "cuda" and not plan_only:
@@ -180,7 +204,10 @@ class TrainStep:
         # (measurement only, set through the `exchange_skipped()` context manager, which restores the replicas' state)
         self._skip_exchange = False
         head = nn.Linear(backbone.get_last_out_channels(), num_classes)
-        self.model = nn.Sequential(backbone, nn.AdaptiveAvgPool2d((1, 1)), nn.Flatten(), head)
+        if self.include_pool:
+            self.model = nn.Sequential(backbone, nn.AdaptiveAvgPool2d((1, 1)), nn.Flatten(), head)
+        else:
+            self.model = nn.Sequential(backbone, head)
         self.model.train()
         if freeze_bn:
             # fine-tuning with frozen BatchNorm: every unit normalises with its running statistics (constants
@@ -191,11 +218,28 @@ class TrainStep:
 
         groups = param_groups(self.model)
         self.store = st = E.ParamStore(self.model, order_key=lambda p: groups[id(p)])
+        # the kernels address channels in 16-byte chunks: a class count that is no multiple of one (10 classes) runs as
+        # the next wider head over zero rows, which stay zero -- the loss reads `num_classes` columns and hands the
+        # others a zero gradient, and every optimiser here maps (p, g, state) = 0 to 0
+        self.num_classes = num_classes
+        self._head_rows = E._round_up(num_classes, E._EPC[self.dtype])
+        if self._head_rows != num_classes:
+            st.reserve[id(head.weight)] = self._head_rows * head.in_features
+            st.reserve[id(head.bias)] = self._head_rows
         # gradient exchange: "allreduce" = one f32 all-reduce per bucket, every rank runs the whole optimiser;
         # "sharded" = reduce-scatter -> SGD on the rank's slice of every bucket -> all-gather of the bf16 weights
         if exchange not in ("allreduce", "sharded"):
             raise ValueError(exchange)
         self.exchange = exchange if self.dp else "allreduce"
+        if self.exchange == "sharded":
+            from .backbones.convnext import ConvNeXt
+
+            # the sharded exchange refreshes the bf16 mirror of the slices other ranks own, and f32 only for the head bucket
+            # (BatchNorm parameters, biases); a ConvNeXt's layer scales and depthwise filters are read as f32 masters and
+            # lie in the weight-decay group behind it: they would go stale on every rank but their owner
+            if isinstance(backbone, ConvNeXt):
+                raise NotImplementedError("exchange='sharded' with a ConvNeXt: its layer scales and depthwise filters are read "
+                                          "in f32 outside the head bucket (use exchange='allreduce')")
         # who issues the collectives: "torch" = torch.distributed calls between segments of the launch lists (any
         # backend: gloo in the CPU tests); "rccl" = the library's own RCCL communicator (vt_comm_init), the collectives are
         # OPS of the lists (VT_OP_STAT_SYNC in front of every BatchNorm finalize, FORK + VT_OP_ALLREDUCE on the
@@ -218,7 +262,9 @@ class TrainStep:
             st.ensure(self.device)
             self.gflat = torch.zeros_like(st.pflat)
             self.mflat = torch.zeros_like(st.pflat)
-            # HYPER buffer: [0] learning rate; [8..13] MixUp / CutMix block (mode, lambda, x1, y1, x2, y2)
+            self.vflat = torch.zeros_like(st.pflat) if self._adam else None  # second moment: the Adam family only
+            # HYPER buffer: [0] learning rate; [4..6] optimiser step count and bias corrections (HYPER_STEP);
+            # [8..13] MixUp / CutMix block (mode, lambda, x1, y1, x2, y2)
             self.lr_dev = torch.zeros(16, dtype=torch.float32, device=self.device)
             self.lr_dev[:4] = lr
             self.images = torch.zeros(batch_size, 3, image_size, image_size, device=self.device)
@@ -241,9 +287,10 @@ class TrainStep:
         self.mix = bool(mix)  # MixUp / CutMix applied on device from a per-step parameter block
         x = b.input_images(batch_size, 3, image_size, image_size, mix=self.mix)
         fmap = backbone._vt_emit_maps(b, x)[-1]
-        pooled = b.global_avgpool(fmap, "head.pool")
-        logits = b.conv_unit(pooled, _LinearAsConv(head), None, False, name="head.linear")
-        self._loss_buf = b.xent(logits, label_smoothing, 1.0 / batch_size, mix=self.mix)
+        # (include_pool=False: the last entry IS the backbone's forward output, [B,1,1,C] -- no pooling launch)
+        pooled = b.global_avgpool(fmap, "head.pool") if self.include_pool else fmap
+        logits = b.conv_unit(pooled, _LinearAsConv(head, self._head_rows), None, False, name="head.linear")
+        self._loss_buf = b.xent(logits, label_smoothing, 1.0 / batch_size, mix=self.mix, num_classes=num_classes)
         self._logits = logits
         b.build_backward()
         self.prog = Program(b, [logits], [])
@@ -257,14 +304,14 @@ class TrainStep:
             self.prog.bwd_ops, self.prog.n_bwd = self._with_stat_sync(self.prog.bwd_ops, self.prog.n_bwd, self._bwd_sync)
             self._fwd_sync, self._bwd_sync = [], []
 
-        # ---- optimiser launch list: one SGD launch per weight-decay group ---------------------
+        # ---- optimiser launch list: one launch per weight-decay group -------------------------
         wd_of = {GROUP_OTHER: weight_decay, GROUP_NORM: norm_weight_decay, GROUP_BIAS: bias_weight_decay}
         self.segments = []  # (elem start, elem end, weight decay)
         gids = [groups[id(p)] for p in st.params]
         start = 0
         for i, p in enumerate(st.params):
             if i + 1 == len(st.params) or gids[i + 1] != gids[i]:
-                end = st.offsets[i] + E._round_up(p.numel(), 64)
+                end = st.offsets[i] + st.slots[i]
                 self.segments.append((start, end, wd_of[gids[i]]))
                 start = end
         self._momentum, self._lr0 = momentum, lr
@@ -299,7 +346,7 @@ class TrainStep:
             import bisect
 
             starts = list(st.offsets)
-            ends = [o + E._round_up(p.numel(), 64) for o, p in zip(st.offsets, st.params)]
+            ends = [o + n for o, n in zip(st.offsets, st.slots)]
             for idx in range(self.prog.n_bwd):
                 for off in _grad_write_offsets(self.prog.bwd_ops[idx]):
                     k = bisect.bisect_right(starts, off) - 1
@@ -322,7 +369,7 @@ class TrainStep:
             self.arena.data_ptr(), PARAMS=st.pflat.data_ptr(), GRADS=self.gflat.data_ptr(),
             STATE=st.sflat.data_ptr(), MIRROR=st.mirror.data_ptr(), COUNTERS=st.nflat.data_ptr(),
             INPUT=self.images.data_ptr(), LABELS=self.labels.data_ptr(), MOMENTUM=self.mflat.data_ptr(),
-            HYPER=self.lr_dev.data_ptr())
+            HYPER=self.lr_dev.data_ptr(), **({"MOMENT2": self.vflat.data_ptr()} if self._adam else {}))
         self.use_graphs = use_graphs
         self._master_stale = False
         self.model.register_state_dict_pre_hook(self._refuse_stale_export)
@@ -331,12 +378,25 @@ class TrainStep:
         self.steps_done = 0
 
     def _emit_opt(self, ranges):
-        """optimiser launch list: one SGD launch per (element range, weight-decay segment) overlap"""
+        """optimiser launch list: one launch of the chosen optimiser per (element range, weight-decay segment) overlap.
+
+        Adam family: the list opens with ONE VT_OP_ADAM_TICK, which advances the step count in the HYPER buffer and
+        leaves the two bias corrections beside it; every VT_OP_ADAMW of the step reads them (and the learning rate)
+        from there.  The host passes nothing per step, so an eager run and a replayed hipGraph count alike, and a rank
+        that updates only its shards still sees the step count every other rank sees."""
         ob = E.Builder(self.store, self.dtype, True, True, grad_base=E.GRADS)
+        if self._adam:
+            ob.emit(N.OP_ADAM_TICK, [(E.HYPER, 0)], [], [self._betas[0], self._betas[1]])
         for r0, r1 in ranges:
             for s0, s1, wd in self.segments:
                 lo, hi = max(r0, s0), min(r1, s1)
-                if hi > lo:
+                if hi > lo and self._adam:
+                    ob.emit(N.OP_ADAMW,
+                            [(E.PARAMS, lo * 4), (E.GRADS, lo * 4), (E.MOMENTUM, lo * 4), (E.MOMENT2, lo * 4),
+                             (E.MIRROR, lo * 2) if self.dtype == N.VT_BF16 else None, (E.HYPER, 0)],
+                            [N.VT_BF16, int(self.optimizer == "AdamW")],
+                            [hi - lo, self._betas[0], self._betas[1], self._eps, wd, 1.0 / self.world])
+                elif hi > lo:
                     ob.emit(N.OP_SGD,
                             [(E.PARAMS, lo * 4), (E.GRADS, lo * 4), (E.MOMENTUM, lo * 4),
                              (E.MIRROR, lo * 2) if self.dtype == N.VT_BF16 else None, (E.HYPER, 0)],
@@ -362,6 +422,8 @@ class TrainStep:
         if self.exchange == "sharded":
             self.bucketer.gather(self.store.pflat)
             self.bucketer.gather(self.mflat)
+            if self._adam:
+                self.bucketer.gather(self.vflat)
         self._master_stale = False
 
     def _refuse_stale_export(self, *_):
@@ -508,14 +570,15 @@ class TrainStep:
         @contextlib.contextmanager
         def ctx():
             st = self.store
-            keep = [t.clone() for t in (st.pflat, st.sflat, st.nflat, self.mflat, st.mirror)]
+            state = (st.pflat, st.sflat, st.nflat, self.mflat, st.mirror) + ((self.vflat, self.lr_dev) if self._adam else ())
+            keep = [t.clone() for t in state]
             self._skip_exchange = True
             try:
                 yield self
             finally:
                 self._skip_exchange = False
                 torch.cuda.synchronize(self.device)
-                for dst, src_ in zip((st.pflat, st.sflat, st.nflat, self.mflat, st.mirror), keep):
+                for dst, src_ in zip(state, keep):
                     dst.copy_(src_)
 
         return ctx()
@@ -529,17 +592,28 @@ class TrainStep:
             torch.distributed.broadcast(self.store.sflat, src, group=self.pg)
             torch.distributed.broadcast(self.store.nflat, src, group=self.pg)
             torch.distributed.broadcast(self.mflat, src, group=self.pg)
+            if self._adam:  # second moment and the step count with its bias corrections
+                torch.distributed.broadcast(self.vflat, src, group=self.pg)
+                torch.distributed.broadcast(self.lr_dev[HYPER_STEP:HYPER_STEP + 4], src, group=self.pg)
             if self.dtype == N.VT_BF16:
                 self.store.mirror.copy_(self.store.pflat)
 
     def weights_changed(self) -> None:
-        """call after writing parameters from outside (load_state_dict, manual init)."""
+        """call after writing parameters from outside (load_state_dict, manual init): refreshes the bf16 mirror.
+        Optimiser state (moments, step count) is not reset, as loading weights does not reset it in torch."""
         if self.dtype == N.VT_BF16:
             self.store.mirror.copy_(self.store.pflat)
 
     def set_lr(self, lr: float) -> None:
         self.lr = lr
         self.lr_dev[:4] = lr
+
+    def opt_steps(self) -> int:
+        """optimiser steps taken so far as the DEVICE counts them (Adam family: the int32 in slot HYPER_STEP of the
+        HYPER buffer, advanced by the step's own VT_OP_ADAM_TICK; synchronises).  SGD keeps no device count."""
+        if not self._adam:
+            return self.steps_done
+        return int(self.lr_dev[HYPER_STEP:HYPER_STEP + 1].view(torch.int32).item())
 
     def set_mix(self, mode: str = "none", lam: float = 1.0, box=(0, 0, 0, 0)) -> None:
         """MixUp / CutMix parameters of the NEXT step(s) (TrainStep(mix=True)): mode 'none' | 'mixup' |
@@ -573,7 +647,7 @@ class TrainStep:
             }
 
     def step(self, images: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None) -> None:
-        """fwd + loss + bwd + gradient all-reduce + SGD on the resident (or given) batch."""
+        """fwd + loss + bwd + gradient all-reduce + optimiser on the resident (or given) batch."""
         if self.plan_only:
             raise RuntimeError("plan_only TrainStep cannot execute: there is no CPU path")
         with self._dev_ctx():
@@ -624,9 +698,10 @@ class TrainStep:
             b = E.Builder(self.store, self.dtype, training=False, need_grad=False)
             x = b.input_images(self.B, 3, self.S, self.S)
             fmap = self.model[0]._vt_emit_maps(b, x)[-1]
-            pooled = b.global_avgpool(fmap, "head.pool")
-            logits = b.conv_unit(pooled, _LinearAsConv(self.model[3]), None, False, name="head.linear")
-            sums = b.xent_eval(logits)
+            pooled = b.global_avgpool(fmap, "head.pool") if self.include_pool else fmap
+            # (the head by position from the end: model[3] with the pooling children, model[1] without)
+            logits = b.conv_unit(pooled, _LinearAsConv(self.model[-1], self._head_rows), None, False, name="head.linear")
+            sums = b.xent_eval(logits, num_classes=self.num_classes)
             b.build_backward()
             prog = Program(b, [logits], [])
         finally:
@@ -668,7 +743,7 @@ class TrainStep:
     def eval_logits(self) -> torch.Tensor:
         """logits of the last validate() call"""
         _, arena, _, _, logits = self._eval
-        return E.tref_to_tensor(arena, logits).reshape(self.B, -1)
+        return E.tref_to_tensor(arena, logits).reshape(self.B, -1)[:, :self.num_classes]
 
     def loss(self) -> float:
         """mean loss of the last step (synchronises)."""
@@ -676,4 +751,4 @@ class TrainStep:
         return float(self.arena[off : off + 4].view(torch.float32).item())
 
     def logits(self) -> torch.Tensor:
-        return E.tref_to_tensor(self.arena, self._logits).reshape(self.B, -1)
+        return E.tref_to_tensor(self.arena, self._logits).reshape(self.B, -1)[:, :self.num_classes]
