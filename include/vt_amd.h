@@ -177,6 +177,33 @@ int vt_scale_residual_bwd(const void* dy, int32_t lddy, const void* t, int32_t l
                           int32_t lddt, float* sums, int64_t M, int32_t C, int32_t dtype, void* stream);
 int vt_channel_sums_to_f32(const float* sums, int32_t rows, int32_t C, float* dst0, float* dst1, float* dst2, void* stream);
 
+/* Token mixing (MLP-Mixer: reference backbones/mlp_mixer.py:28,34 -- a Linear over the TOKEN axis) and the patch gather of
+ * the patch embedding (mlp_mixer.py:52,60), vt_token_mix.hip.  Maps are [B][tokens][C] rows with a row stride ld >= C, C a
+ * multiple of 8 (bf16) / 4 (f32); the token counts K and M are arbitrary positive integers.
+ *   vt_token_mix_fwd:    out[b][m][c] = sum_k A[m][k] x[b][k][c] (+ bias[m]) (+ residual[b][m][c], which may alias z);
+ *                        A[m][k] = w[m * ldw + k], or w[k * ldw + m] with `transw` (the data gradient: the same weight,
+ *                        K and M exchanged).  w has the map's dtype (bf16 launches read the bf16 mirror), bias is f32.
+ *                        `z` receives out, `a` (optional) act(z) for activation code 0 / 4 (exact GELU) of the stored z;
+ *                        either may be NULL.  bf16: mfma_f32_16x16x32_bf16 over x tiles read with ds_read_b64_tr_b16, a
+ *                        64-row slice of W resident in LDS (K <= ~1000); f32: exact f32 FMA.
+ *   vt_token_mix_wgrad:  dw[m][k] += sum_{b,c} dz[b][m][c] x[b][k][c] (dense [M][K]), dbias[m] += sum_{b,c} dz[b][m][c]
+ *                        (either may be NULL).  Partial tiles are stored into slabs of `scratch`
+ *                        (vt_token_mix_wgrad_scratch_bytes; a smaller scratch gets fewer, longer splits) and added in split
+ *                        order: no float atomics, bit-identical from run to run.
+ *   vt_patchify_fwd:     out[b][gy][gx][(py p + px) Cin + c] = img[b][gy p + py][gx p + px][c] -- the row order of the
+ *                        channels_last filter image [d_model][p][p][Cin], so the embedding is a Linear over these rows
+ *   vt_patchify_bwd:     the scatter back into the (channel padded) image gradient, pad channels zero (+ residual) */
+int vt_token_mix_fwd(const void* x, int32_t ldx, const void* w, int32_t ldw, int32_t transw, const float* bias,
+                     const void* residual, int32_t ldr, void* z, int32_t ldz, void* a, int32_t lda, int32_t act, int32_t B,
+                     int32_t K, int32_t M, int32_t C, int32_t dtype, void* stream);
+int64_t vt_token_mix_wgrad_scratch_bytes(int32_t B, int32_t K, int32_t M, int32_t C, int32_t dtype);
+int vt_token_mix_wgrad(const void* dz, int32_t lddz, const void* x, int32_t ldx, float* dw, float* dbias, void* scratch,
+                       int64_t scratch_bytes, int32_t B, int32_t K, int32_t M, int32_t C, int32_t dtype, void* stream);
+int vt_patchify_fwd(const void* img, int32_t ldi, void* out, int32_t ldo, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                    int32_t p, int32_t dtype, void* stream);
+int vt_patchify_bwd(const void* dout, int32_t lddo, void* dimg, int32_t ldg, const void* residual, int32_t ldr, int32_t B,
+                    int32_t H, int32_t W, int32_t Cin, int32_t Cpad, int32_t p, int32_t dtype, void* stream);
+
 /* Filter gradient: dw[n][t][c] += sum_pixels dz(pix,n) * x_gathered(pix,t,c),
  * fp32 accumulation straight into the (channels_last) .grad of the weight.
  * `d` is the forward descriptor (ldy = pixel stride of dz).  Replaces the
@@ -607,6 +634,10 @@ enum vt_op_kind {
     VT_OP_CHANNEL_SUMS,      /* vt_channel_sums_to_f32 */
     VT_OP_ADAM_TICK,         /* vt_adam_tick (the optimiser step count, once per step) */
     VT_OP_ADAMW,             /* vt_adamw */
+    VT_OP_TOKEN_MIX,         /* vt_token_mix_fwd (forward and, with transw, the data gradient) */
+    VT_OP_TOKEN_WGRAD,       /* vt_token_mix_wgrad */
+    VT_OP_PATCHIFY_FWD,      /* vt_patchify_fwd */
+    VT_OP_PATCHIFY_BWD,      /* vt_patchify_bwd */
     VT_OP_KIND_END
 };
 

@@ -231,6 +231,16 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
                                          I[3], I[4], st);
         case VT_OP_CHANNEL_SUMS:  // ptr: sums dst0 dst1 dst2 | i: rows C
             return vt_channel_sums_to_f32((const float*)P[0], I[0], I[1], (float*)P[1], (float*)P[2], (float*)P[3], st);
+        case VT_OP_TOKEN_MIX:  // ptr: x w bias residual z a | i: ldx ldw transw ldr ldz lda act B K M C dtype
+            return vt_token_mix_fwd(P[0], I[0], P[1], I[1], I[2], (const float*)P[2], P[3], I[3], P[4], I[4], P[5], I[5], I[6], I[7],
+                                    I[8], I[9], I[10], I[11], st);
+        case VT_OP_TOKEN_WGRAD:  // ptr: dz x dw dbias scratch | i: lddz ldx B K M C dtype | f: scratch bytes
+            return vt_token_mix_wgrad(P[0], I[0], P[1], I[1], (float*)P[2], (float*)P[3], P[4], (int64_t)F[0], I[2], I[3], I[4],
+                                      I[5], I[6], st);
+        case VT_OP_PATCHIFY_FWD:  // ptr: img out | i: ldi ldo B H W Cin p dtype
+            return vt_patchify_fwd(P[0], I[0], P[1], I[1], I[2], I[3], I[4], I[5], I[6], I[7], st);
+        case VT_OP_PATCHIFY_BWD:  // ptr: dout dimg residual | i: lddo ldg ldr B H W Cin Cpad p dtype
+            return vt_patchify_bwd(P[0], I[0], P[1], I[1], P[2], I[2], I[3], I[4], I[5], I[6], I[7], I[8], I[9], st);
         case VT_OP_BN_FIN_APPLY:  // ptr: stats gamma beta rm rv nbt scale shift mean invstd z residual y | i: C ldz ldr ldy relu dtype | f: count eps momentum M
             return vt_bn_finalize_apply((const float*)P[0], I[0], F[0], (const float*)P[1], (const float*)P[2], (float)F[1], (float)F[2],
                                         (float*)P[3], (float*)P[4], (int64_t*)P[5], (float*)P[6], (float*)P[7], (float*)P[8],

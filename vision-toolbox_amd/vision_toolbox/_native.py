@@ -113,7 +113,11 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_CHANNEL_SUMS,
     OP_ADAM_TICK,
     OP_ADAMW,
-) = range(1, 56)
+    OP_TOKEN_MIX,
+    OP_TOKEN_WGRAD,
+    OP_PATCHIFY_FWD,
+    OP_PATCHIFY_BWD,
+) = range(1, 60)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -153,6 +157,10 @@ OP_NAMES = {
     OP_SGD: "sgd",
     OP_ADAM_TICK: "adam_tick",
     OP_ADAMW: "adamw",
+    OP_TOKEN_MIX: "token_mix",
+    OP_TOKEN_WGRAD: "token_wgrad",
+    OP_PATCHIFY_FWD: "patchify_fwd",
+    OP_PATCHIFY_BWD: "patchify_bwd",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -268,6 +276,12 @@ SYMBOLS = {
     "vt_scale_residual_fwd": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _i32, _i64, _i32, _i32, _vp]),
     "vt_scale_residual_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _vp]),
     "vt_channel_sums_to_f32": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "vt_token_mix_fwd": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                _vp]),
+    "vt_token_mix_wgrad_scratch_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "vt_token_mix_wgrad": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vt_patchify_fwd": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vt_patchify_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_bn_act_bwd_fused": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, C.c_int64, _i32, _i32, _i32, _f64, _f64, _i32, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _i32, _vp]),
     "vt_bn_bwd_fused_timeouts": (_i32, [C.POINTER(C.c_uint32)]),

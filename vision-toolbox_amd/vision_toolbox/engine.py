@@ -1564,6 +1564,128 @@ class Builder:
             self.nodes.append(bwd)
         return y
 
+    # -- MLP-Mixer pieces (reference backbones/mlp_mixer.py:28,34,52,60): vt_token_mix.hip ---------------------
+    def patch_embed(self, x: TRef, conv: nn.Conv2d, name: str = "patch_embed") -> TRef:
+        """a p x p stride-p nn.Conv2d over the image as a patch gather (vt_patchify_fwd) and ONE Linear over the
+        Cin * p * p values of a patch: a 16 x 16 patch is 256 taps, which the convolution descriptor (VT_MAX_TAPS, 8-bit
+        tap offsets) does not take.  The gather orders a patch row (py, px, c), the order of the channels_last filter
+        image [d_model][p][p][Cin], so the filter is read as it lies (bf16: in the mirror).  Backward scatters into the
+        image gradient only where the image requires one."""
+        import types
+
+        p = conv.kernel_size[0]
+        if (tuple(conv.kernel_size) != (p, p) or tuple(conv.stride) != (p, p) or tuple(conv.padding) != (0, 0) or
+                tuple(conv.dilation) != (1, 1) or conv.groups != 1):
+            raise NotImplementedError(f"{name}: a patch embedding is a p x p convolution with stride p, no padding, groups = 1")
+        cin, dt = conv.in_channels, self.dtype
+        if getattr(x, "logical_C", x.C) != cin:
+            raise ValueError(f"{name}: conv expects {cin} input channels, got {getattr(x, 'logical_C', x.C)}")
+        if x.H % p or x.W % p:
+            raise ValueError(f"{name}: a {x.H}x{x.W} image is no whole number of {p}x{p} patches")
+        rows = cin * p * p
+        if rows % _EPC[dt]:
+            raise NotImplementedError(f"{name}: {cin} * {p} * {p} = {rows} values per patch must be a multiple of {_EPC[dt]} "
+                                      f"for dtype {dt}")
+        self.tag += 1
+        B, H, W = x.B, x.H, x.W
+        patches = self.act(B, H // p, W // p, rows, name + ".patches", needs_grad=x.needs_grad)
+        self.emit(N.OP_PATCHIFY_FWD, [x.addr(), patches.addr()], [x.ld, patches.ld, B, H, W, cin, p, dt])
+        if self.need_grad and x.needs_grad:
+            tag = self.tag
+
+            def bwd():
+                self.tag = tag
+                dp = self.grad_read(patches)
+                if dp is None:
+                    return
+                gx, res = self.grad_target(x)
+                self.emit(N.OP_PATCHIFY_BWD, [dp.addr(), gx.addr(), res.addr() if res is not None else None],
+                          [dp.ld, gx.ld, res.ld if res is not None else 0, B, H, W, cin, x.C, p, dt])
+                self.grad_written(x)
+
+            self.nodes.append(bwd)
+        lin = types.SimpleNamespace(in_features=rows, out_features=conv.out_channels, weight=conv.weight, bias=conv.bias)
+        return self.linear_unit(patches, lin, 0, name=name)
+
+    def _token_slab(self, nbytes: int) -> Buf:
+        """slab scratch of the token filter gradients: one per size, shared by every layer of that shape (their launches
+        follow each other on one stream)"""
+        slabs = self.__dict__.setdefault("_tok_slabs", {})
+        if nbytes not in slabs:
+            slabs[nbytes] = self.alloc(nbytes, "token_wgrad_slabs")
+        return slabs[nbytes]
+
+    def token_linear(self, x: TRef, linear: nn.Linear, act: int = 0, residual: Optional[TRef] = None,
+                     out: Optional[TRef] = None, name: str = "token_linear") -> TRef:
+        """nn.Linear over the TOKEN axis of a map: y[b, m, c] = sum_k W[m, k] x[b, k, c] + bias[m], tokens k = the H * W
+        pixels of x (vt_token_mix_fwd; the reference transposes the map, applies the Linear and transposes back).  `act`
+        (0, or 4 = exact GELU): the launch writes the pre-activation AND its activation; `residual`: y = residual + ...,
+        in the residual's geometry.  Without a residual y is [B, M, 1, C].  Backward: the stored pre-activation through
+        the activation backward pass, vt_token_mix_wgrad (filter and bias gradient, order-free in every mode) on the
+        filter-gradient stream, and the same forward kernel over W^T for the data gradient, which folds one addend."""
+        K, M, dt = x.H * x.W, linear.out_features, self.dtype
+        if linear.in_features != K:
+            raise ValueError(f"{name}: Linear expects {linear.in_features} tokens, the map has {x.H}x{x.W} = {K}")
+        if getattr(x, "logical_C", x.C) != x.C or x.C % _EPC[dt]:
+            raise NotImplementedError(f"{name}: {x.C} channels must be a multiple of {_EPC[dt]} for dtype {dt}")
+        if act not in (0, 4):
+            raise NotImplementedError(f"{name}: activation code {act} (token mixing implements none and exact GELU)")
+        if act and residual is not None:
+            raise NotImplementedError(f"{name}: an activation and a residual in one launch")
+        self.tag += 1
+        B, Cc = x.B, x.C
+        Hy, Wy = (residual.H, residual.W) if residual is not None else (M, 1)
+        if residual is not None and (residual.B, residual.H * residual.W, residual.C) != (B, M, Cc):
+            raise ValueError(f"{name}: residual geometry does not match the {M}-token output")
+        y = out if out is not None else self.act(B, Hy, Wy, Cc, name + ".y")
+        assert (y.B, y.H * y.W, y.C) == (B, M, Cc), "out geometry mismatch"
+        w, bias = linear.weight, linear.bias
+        # (bf16: from the mirror, like every other GEMM weight -- what the sharded exchange refreshes on every rank)
+        wptr = self.pref(w, mirror=True) if dt == N.VT_BF16 else self.pref(w)
+        track = self.need_grad
+        z = self.act(B, Hy, Wy, Cc, name + ".z") if (act and track) else None
+        if act:
+            self.emit(N.OP_TOKEN_MIX,
+                      [x.addr(), wptr, self.pref(bias) if bias is not None else None, None, z.addr() if z is not None else None,
+                       y.addr()], [x.ld, K, 0, 0, z.ld if z is not None else 0, y.ld, act, B, K, M, Cc, dt])
+        else:
+            self.emit(N.OP_TOKEN_MIX,
+                      [x.addr(), wptr, self.pref(bias) if bias is not None else None,
+                       residual.addr() if residual is not None else None, y.addr(), None],
+                      [x.ld, K, 0, residual.ld if residual is not None else 0, y.ld, 0, 0, B, K, M, Cc, dt])
+        if track:
+            tag = self.tag
+
+            def bwd():
+                self.tag = tag
+                dy = self.grad_read(y)
+                if dy is None:
+                    return
+                if residual is not None:
+                    self.grad_add(residual, dy)
+                dz = dy
+                if act:  # dz = dy * act'(z)
+                    dz = self.act(B, Hy, Wy, Cc, name + ".dz")
+                    self.emit(N.OP_BN_BWD_APPLY, [dy.addr(), z.addr(), None, None, None, dz.addr()],
+                              [dy.ld, z.ld, dz.ld, Cc, act, dt], [dz.M])
+                dw = self.pgrad(w)
+                db = self.pgrad(bias) if bias is not None else None
+                if dw is not None or db is not None:
+                    nbytes = int(N.lib().vt_token_mix_wgrad_scratch_bytes(B, K, M, Cc, dt))
+                    slab = self._token_slab(nbytes)
+                    self.emit(N.OP_FORK)
+                    self.emit(N.OP_TOKEN_WGRAD, [dz.addr(), x.addr(), dw, db, self.bp(slab)], [dz.ld, x.ld, B, K, M, Cc, dt],
+                              [nbytes], side=True)
+                if x.needs_grad:
+                    gx, res = self.grad_target(x)
+                    self.emit(N.OP_TOKEN_MIX,
+                              [dz.addr(), wptr, None, res.addr() if res is not None else None, gx.addr(), None],
+                              [dz.ld, K, 1, res.ld if res is not None else 0, gx.ld, 0, 0, B, M, K, Cc, dt])
+                    self.grad_written(x)
+
+            self.nodes.append(bwd)
+        return y
+
     # -- ESE gate (reference vovnet.py:20-28) ---------------------------------------------
     def ese(self, x: TRef, linear: nn.Conv2d, residual: Optional[TRef] = None,
             out: Optional[TRef] = None, name="ese") -> TRef:

@@ -5,7 +5,7 @@ training_step, :111-169 three-group SGD, configs/base.yaml:16-23 DDP) is here ON
 program per rank:
 
     images -> backbone -> global avg-pool -> linear head -> label-smoothing CE
-              (include_pool=False, ConvNeXt: the backbone's own pooled + normalised (B, C) output -> linear head)
+              (include_pool=False, ConvNeXt / MLPMixer: the backbone's own pooled + normalised (B, C) output -> linear head)
            -> explicit backward into a persistent flat f32 gradient buffer
            -> bucketed gradient all-reduce (RCCL over xGMI); each bucket is issued as soon
               as the backward segment that completes it has been enqueued
@@ -178,11 +178,12 @@ class TrainStep:
         self.include_pool = bool(include_pool)
         if not self.include_pool:
             from .backbones.convnext import ConvNeXt
+            from .backbones.mlp_mixer import MLPMixer
 
             # classifier.py:59-63 with include_pool=False is nn.Sequential(backbone, nn.Linear): right only where
             # forward() already returns the pooled (B, C) vector; a map-returning family would feed nn.Linear a 4-D map
-            if not isinstance(backbone, ConvNeXt):
-                raise ValueError(f"include_pool=False needs a backbone whose forward returns (B, C) (ConvNeXt); "
+            if not isinstance(backbone, (ConvNeXt, MLPMixer)):
+                raise ValueError(f"include_pool=False needs a backbone whose forward returns (B, C) (ConvNeXt, MLPMixer); "
                                  f"{type(backbone).__name__} returns a feature map")
         self.device = torch.device(device if device is not None else "cuda")
         self.plan_only = plan_only  # build launch lists / bucket plan without a GPU (host-logic tests)
