@@ -374,3 +374,43 @@ def test_padded_stem_filter_is_read_from_the_bf16_mirror():
             if (op.kind & 0xFFFF) == N.OP_COPY2D and op.ptr[0].base == E.MIRROR:
                 copies += 1
         assert copies == 1, factory.__name__
+
+
+# ---- the builder's spec types and declared state ---------------------------------------------------------
+def test_conv_spec_groups_resolve_to_parameter_slices():
+    conv = nn.Conv2d(16, 32, 3, groups=2, bias=True)
+    st = E.ParamStore(conv)
+    st.ensure(torch.device("cpu"))
+    spec = E.ConvSpec.from_conv(conv)
+    assert (spec.k, spec.groups, spec.in_channels, spec.out_channels, spec.is_slice) == (3, 2, 16, 32, False)
+    g1 = spec.group(1)
+    n = 16 * 9 * 8  # one group's rows of the [Cout][kh][kw][Cin / G] filter image
+    base, off, _ = st.where(conv.weight)
+    assert st.where(g1.weight) == (base, off + 1 * n, n)
+    bbase, boff, _ = st.where(conv.bias)
+    assert st.where(g1.bias) == (bbase, boff + 16, 16)
+    assert g1.is_slice and (g1.groups, g1.in_channels, g1.out_channels) == (1, 8, 16)
+    assert spec.without_bias().bias is None and spec.without_bias().weight is conv.weight
+
+
+def test_conv_spec_of_a_linear_and_constructor_checks():
+    lin = nn.Linear(32, 10)
+    spec = E.ConvSpec.from_linear(lin, out_channels=16)  # the trainer's head, widened to a whole 16-byte chunk
+    assert (spec.out_channels, spec.in_channels, spec.k, spec.stride, spec.padding) == (16, 32, 1, 1, 0)
+    assert spec.weight is lin.weight and spec.bias is lin.bias and not spec.is_slice
+    assert E.ConvSpec.from_linear(lin).out_channels == 10
+    with pytest.raises(NotImplementedError, match="square convolutions"):
+        E.ConvSpec.from_conv(nn.Conv2d(8, 8, (3, 5)))
+    with pytest.raises(NotImplementedError, match="tap offsets are 8-bit"):
+        E.ConvSpec.from_conv(nn.Conv2d(8, 8, 3, dilation=64))
+    with pytest.raises(NotImplementedError, match="variants other than the default"):
+        E.BNSpec.from_bn(nn.BatchNorm2d(8, affine=False))
+
+
+def test_builder_state_is_declared():
+    b = E.Builder(E.ParamStore(nn.Conv2d(3, 8, 3)), N.VT_BF16, False, False)
+    assert b.input_grad is None
+    x = b.input_images(1, 3, 8, 8)
+    assert (x.C, x.logical_C, x.logical_c) == (8, 3, 3)
+    s = x.sl(0, 8)  # a slice is a tensor of its own: it does not inherit the padding record
+    assert s.logical_C is None and s.logical_c == 8 and not s.stem_out

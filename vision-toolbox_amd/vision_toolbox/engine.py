@@ -17,9 +17,8 @@ torch children (program.py dispatch rule) and never by these launch lists.
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Callable, Optional
 
 import torch
@@ -63,6 +62,12 @@ class TRef:
     coff: int  # channel offset, elements
     dtype: int
     needs_grad: bool = True
+    logical_C: Optional[int] = None  # channels before the padding to a 16-byte chunk (input_images); None: C.  Not inherited by sl()
+    stem_out: bool = False  # written by the stem unit that recomputes z (conv_unit); not inherited by sl() either
+
+    @property
+    def logical_c(self) -> int:
+        return self.C if self.logical_C is None else self.logical_C
 
     @property
     def M(self) -> int:
@@ -208,6 +213,91 @@ class ParamStore:
         return tuple(p._version for p in self.params)
 
 
+# -- what Builder.conv_unit is told about a layer -------------------------------------------
+@dataclass(frozen=True, eq=False)
+class ConvSpec:
+    """A conv-like layer as conv_unit sees it: a square nn.Conv2d, one group of a grouped one, or an nn.Linear as a 1x1
+    convolution over a [B,1,1,C] map (classifier.py:63).  `weight` / `bias` are parameters, or _PSlice views of them
+    (`is_slice`)."""
+
+    k: int
+    stride: int
+    padding: int
+    dilation: int
+    groups: int
+    in_channels: int
+    out_channels: int
+    weight: object
+    bias: object = None
+    is_slice: bool = False
+
+    def __post_init__(self):
+        if self.dilation * (self.k - 1) > 127:
+            raise NotImplementedError(f"dilation {self.dilation}: tap offsets are 8-bit")
+
+    @classmethod
+    def from_conv(cls, conv: nn.Conv2d) -> "ConvSpec":
+        ks, st, dl, pd = conv.kernel_size, conv.stride, conv.dilation, conv.padding
+        if ks[0] != ks[1] or st[0] != st[1] or dl[0] != dl[1] or pd[0] != pd[1]:
+            raise NotImplementedError("hot path covers square convolutions (kernel, stride, dilation, padding)")
+        return cls(ks[0], st[0], pd[0], dl[0], conv.groups, conv.in_channels, conv.out_channels, conv.weight, conv.bias)
+
+    @classmethod
+    def from_linear(cls, linear: nn.Linear, out_channels: Optional[int] = None) -> "ConvSpec":
+        """(out_channels > out_features: the rows beyond the parameter's own are zeros its slot of the flat store reserves)"""
+        return cls(1, 1, 0, 1, 1, linear.in_features, out_channels or linear.out_features, linear.weight, linear.bias)
+
+    def group(self, g: int) -> "ConvSpec":
+        """group g of a grouped convolution: its rows of the [Cout][kh][kw][Cin / G] filter image, its share of the bias"""
+        ci, co = self.in_channels // self.groups, self.out_channels // self.groups
+        wn = co * self.k * self.k * ci
+        return replace(self, groups=1, in_channels=ci, out_channels=co, weight=_PSlice(self.weight, g * wn, wn),
+                       bias=_PSlice(self.bias, g * co, co) if self.bias is not None else None, is_slice=True)
+
+    def without_bias(self) -> "ConvSpec":
+        return replace(self, bias=None)
+
+    def out_size(self, H: int, W: int) -> "tuple[int, int]":
+        reach = 2 * self.padding - self.dilation * (self.k - 1) - 1
+        return (H + reach) // self.stride + 1, (W + reach) // self.stride + 1
+
+
+@dataclass(frozen=True, eq=False)
+class BNSpec:
+    """An nn.BatchNorm2d (default variant: affine, running statistics, a momentum), or one group's slice of it."""
+
+    weight: object
+    bias: object
+    running_mean: object
+    running_var: object
+    num_batches_tracked: object
+    eps: float
+    momentum: float
+    training: bool
+
+    @classmethod
+    def from_bn(cls, bn: nn.BatchNorm2d) -> "BNSpec":
+        if bn.momentum is None or not bn.affine or not bn.track_running_stats:
+            raise NotImplementedError("BatchNorm2d variants other than the default are outside the hot path")
+        return cls(bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps, bn.momentum,
+                   bool(bn.training))
+
+    def group(self, g: int, G: int) -> "BNSpec":
+        co = self.weight.numel() // G
+        sl = lambda t: _PSlice(t, g * co, co)
+        # (the batch counter belongs to the module, not to a group: the first group's finalize advances it)
+        return replace(self, weight=sl(self.weight), bias=sl(self.bias), running_mean=sl(self.running_mean),
+                       running_var=sl(self.running_var), num_batches_tracked=self.num_batches_tracked if g == 0 else None)
+
+
+def _addr(t: "Optional[TRef]"):
+    return t.addr() if t is not None else None
+
+
+def _ld(t: "Optional[TRef]") -> int:
+    return t.ld if t is not None else 0
+
+
 # ---------------------------------------------------------------------------------------
 # gradient bookkeeping (per forward buffer)
 # ---------------------------------------------------------------------------------------
@@ -227,6 +317,89 @@ class _GradState:
 
     def touches(self, c0: int, c1: int) -> bool:
         return any(a < c1 and c0 < b for a, b in self.init)
+
+
+class _BNEmitter:
+    """The BatchNorm of one unit inside a Builder: parameter addresses resolved once, the coefficient buffer
+    (scale | shift | mean | invstd, C floats each) and the launches every BatchNorm unit shares.  `cp`: the four
+    coefficient pointers where the caller owns the buffer (pw_units: one buffer over all groups' channels)."""
+
+    def __init__(self, b: "Builder", spec: BNSpec, C_: int, cp=None):
+        self.b, self.spec, self.C = b, spec, C_
+        if cp is None:
+            coef = b.f32(4 * C_, "bncoef")
+            cp = [b.bp(coef, i * C_ * 4) for i in range(4)]
+        self.cp = cp
+        self.params = [b.pref(spec.weight), b.pref(spec.bias), b.pref(spec.running_mean), b.pref(spec.running_var)]
+        self.nbt = b.pref(spec.num_batches_tracked) if spec.num_batches_tracked is not None else None
+
+    def grads(self):
+        """gradient accumulators of (weight, bias); resolved when a backward op is emitted (they may be allocated then)"""
+        return [self.b.pgrad(self.spec.weight), self.b.pgrad(self.spec.bias)]
+
+    def finalize_operands(self, stats: Buf, M: int):
+        """(pointers, floats) of the finalize step: batch statistics -> coefficients and running statistics"""
+        return ([self.b.bp(stats), *self.params, self.nbt, *self.cp],
+                [M * self.b.bn_world, self.spec.eps, self.spec.momentum])
+
+    def finalize(self, stats: Buf, M: int):
+        ptrs, flts = self.finalize_operands(stats, M)
+        self.b.emit(N.OP_BN_FINALIZE, ptrs, [self.C], flts)
+
+    def eval_coeffs(self, scale_shift_only: bool = False):
+        """coefficients from the running statistics"""
+        cp = self.cp[:2] + [None, None] if scale_shift_only else self.cp
+        self.b.emit(N.OP_BN_EVAL_COEFFS, [*self.params, *cp], [self.C], [self.spec.eps])
+
+    def bwd_buffers(self, y: TRef, dz_name: str):
+        """(sums, coefficients, dz) of the unit's backward, in the order every program has allocated them"""
+        b = self.b
+        sums = b.zeroed_f32(N.stat_floats(self.C), "bwdsums")
+        return sums, b.f32(3 * self.C, "bwdcoef"), b.act(y.B, y.H, y.W, self.C, dz_name)
+
+    def bwd_reduce(self, g: TRef, z: TRef, act: int, sums: Buf, M: int, taps=None):
+        self.b.emit(N.OP_BN_BWD_REDUCE, [g.addr(), z.addr(), *self.cp, self.b.bp(sums)] + ([taps[0]] if taps else []),
+                    [g.ld, z.ld, self.C, int(act), self.b.dtype] + (taps[1] if taps else []), [M])
+
+    def bwd_finalize(self, sums: Buf, bcoef: Buf, M: int):
+        b, cp = self.b, self.cp
+        b.emit(N.OP_BN_BWD_FINALIZE, [b.bp(sums), cp[0], cp[2], cp[3], *self.grads(), b.bp(bcoef)],
+               [self.C, int(self.spec.training)], [M * b.bn_world, 1.0 / b.bn_world])
+
+    def bwd_three_launches(self, g: TRef, z: TRef, act: int, sums: Buf, bcoef: Buf, dz: TRef, taps=None, reduce: bool = True):
+        """reduce -> finalize -> apply.  `taps` = (arg-max address, [B, Ho, Wo]): g is the gradient of the unit's fused
+        max pool; reduce=False: the sums were formed by the launch that produced g."""
+        if reduce:
+            self.bwd_reduce(g, z, act, sums, dz.M, taps)
+        self.bwd_finalize(sums, bcoef, dz.M)
+        self.b._act_bwd(g, z, self.cp[0], self.cp[1], self.b.bp(bcoef), dz, act, taps)
+
+
+@dataclass(eq=False)
+class _ConvUnit:
+    """What the forward half of Builder.conv_unit decided about one unit; its backward works from this record."""
+
+    conv: ConvSpec
+    relu: int  # activation code
+    x: TRef
+    y: TRef
+    residual: Optional[TRef]
+    name: str
+    tag: int
+    wptr: tuple  # the filter operand ...
+    wpack: Optional[Buf]  # ... which is this zero-padded copy for the stem
+    ldw: int
+    z: Optional[TRef] = None  # stored pre-activation (None: the unit has none, or recomputes it)
+    bn: Optional[_BNEmitter] = None
+    stem_fused: bool = False  # one-pass stem backward (vt_stem_bwd.hip) ...
+    stem_y: bool = False  # ... working from y: z is never stored
+    pool_out: Optional[TRef] = None  # max pool fused into the normalise pass ...
+    pool_am: Optional[Buf] = None  # ... and its arg-max taps
+    wg_key: Optional[tuple] = None  # shape group of held-back filter gradients
+
+    @property
+    def padded(self) -> bool:
+        return self.wpack is not None
 
 
 class Builder:
@@ -338,6 +511,9 @@ class Builder:
         # (ext_grads, filled by build_backward) after the backward list
         self.ext_inputs: list[TRef] = []
         self.ext_grads: list[Optional[TRef]] = []
+        self.input_grad: Optional[Buf] = None  # NCHW f32 gradient of the images (input_images(requires_grad=True))
+        self._deferred_flush: Optional[TRef] = None  # grad_target -> grad_written
+        self._tok_slabs: dict[int, Buf] = {}  # _token_slab
 
     # -- memory -----------------------------------------------------------------
     def alloc(self, nbytes: int, name: str = "") -> Buf:
@@ -385,11 +561,8 @@ class Builder:
         for k in range(N.VT_OP_MAX_PTR):
             op.ptr[k].base = -1
         for k, p in enumerate(ptrs):
-            if p is None:
-                continue
-            base, off = p
-            op.ptr[k].base = base
-            op.ptr[k].offset = off
+            if p is not None:
+                op.ptr[k].base, op.ptr[k].offset = p
         if desc is not None:
             C.memmove(C.addressof(op.i), C.addressof(desc), C.sizeof(desc))
             k0 = C.sizeof(desc) // 4
@@ -409,6 +582,9 @@ class Builder:
 
     # -- parameters ---------------------------------------------------------------
     def pref(self, t, mirror: bool = False):
+        """address of a parameter or buffer of the flat store (None -> None: an operand the layer does not have)"""
+        if t is None:
+            return None
         base, off, n = self.store.where(t)
         if mirror:
             assert base == PARAMS
@@ -417,7 +593,7 @@ class Builder:
 
     def pgrad(self, p: nn.Parameter):
         """address of the f32 gradient accumulator of parameter p (None if it needs none)."""
-        if not p.requires_grad:
+        if p is None or not p.requires_grad:
             return None
         if isinstance(p, _PSlice):
             a = self.pgrad(p.base)
@@ -477,7 +653,7 @@ class Builder:
 
     def grad_add(self, t: TRef, addend: TRef):
         """register an identity contribution d(t) += addend (materialised lazily)."""
-        if not t.needs_grad:
+        if t is None or not t.needs_grad:  # (None: an operand the op does not have, a residual as a rule)
             return
         assert t.same_geom(addend)
         self._gs(t).pending.append((t.coff, t.coff + t.C, addend))
@@ -508,10 +684,33 @@ class Builder:
 
     def grad_written(self, t: TRef):
         """call after emitting the writer returned by grad_target when it had leftovers."""
-        d = getattr(self, "_deferred_flush", None)
+        d = self._deferred_flush
         if d is not None:
             self._deferred_flush = None
             self._flush_pending(d)
+
+    def grad_accum_target(self, t: TRef):
+        """for a kernel that writes d(t) and cannot fold an addend but can ACCUMULATE: returns (destination, acc flag).  A
+        foreign addend is materialised in the destination first."""
+        gx, res = self.grad_target(t)
+        if res is None:
+            return gx, 0
+        if not (res.buf is gx.buf and res.coff == gx.coff):
+            self._add_into(gx, res, False)
+        return gx, 1
+
+    def _node(self, y: TRef, bwd: Callable[[TRef], None]):
+        """register the backward of the op that wrote y: it runs under the op's tag with the complete d(y), and not at all
+        where nothing contributed to d(y)"""
+        tag = self.tag
+
+        def run():
+            self.tag = tag
+            dy = self.grad_read(y)
+            if dy is not None:
+                bwd(dy)
+
+        self.nodes.append(run)
 
     def grad_read(self, t: TRef) -> Optional[TRef]:
         """the complete gradient of t, or None if nothing contributed."""
@@ -536,6 +735,13 @@ class Builder:
         return self._gref(t)
 
     # -- input / output plumbing -------------------------------------------------------
+    def refresh_mirror(self):
+        """module API: the caller may have changed the f32 masters with any optimiser, so the bf16 mirror is refreshed
+        at the head of every forward list"""
+        if self.dtype == N.VT_BF16:
+            n = self.store.pflat.numel()
+            self.emit(N.OP_COPY2D, [(PARAMS, 0), (MIRROR, 0)], [N.VT_F32, N.VT_BF16, n, 0], [n, n, 1])
+
     MIX_OFF = 32  # byte offset of the MixUp / CutMix parameter block inside the HYPER buffer
 
     def input_images(self, B, C_, H, W, requires_grad=False, mix: bool = False) -> TRef:
@@ -562,9 +768,6 @@ class Builder:
         return x
 
     # -- the ConvNormAct unit (reference components.py:13-46) --------------------------
-    def _taps(self, k: int, dil: int = 1):
-        return [(r * dil, t * dil) for r in range(k) for t in range(k)]
-
     def _conv_desc(self, x: TRef, Cout, Ho, Wo, s, pad, k, ldy, ldw, flags, ldr=0, dil=1) -> N.ConvDesc:
         d = N.ConvDesc()
         d.dtype = self.dtype
@@ -574,506 +777,428 @@ class Builder:
         d.oHs = d.oWs = 1
         d.oh0 = d.ow0 = 0
         d.ldw, d.ldr, d.flags = ldw, ldr, flags
-        taps = self._taps(k, dil)
-        d.ntaps = len(taps)
-        for i, (r, t) in enumerate(taps):
-            d.dh[i], d.dw[i] = r, t
+        d.ntaps = k * k
+        for i in range(k * k):
+            d.dh[i], d.dw[i] = (i // k) * dil, (i % k) * dil
         return d
 
-    def conv_unit(self, x: TRef, conv: nn.Conv2d, norm: Optional[nn.Module], relu: bool,
-                  residual: Optional[TRef] = None, out: Optional[TRef] = None, name: str = "",
-                  pool_out: Optional[TRef] = None) -> TRef:
-        """y = [relu]([bn](conv(x))) [+ residual], written to `out` when given.  `pool_out`: MaxPool2d(3, 2, 1) of y goes
-        there as well -- from the unit's own normalise pass where it has one (vt_bn_act_apply_pool), and then the unit's
-        BatchNorm backward reads the pooled gradient through the arg-max taps instead of a materialised d(y)."""
-        self.tag += 1
-        self.n_units += 1
-        dt, epc = self.dtype, _EPC[self.dtype]
-        k, s = conv.kernel_size[0], conv.stride[0]
-        pad = conv.padding[0]
-        dil = conv.dilation[0]
-        if conv.kernel_size[0] != conv.kernel_size[1] or conv.stride[0] != conv.stride[1] or \
-                conv.dilation[0] != conv.dilation[1] or conv.padding[0] != conv.padding[1]:
-            raise NotImplementedError("hot path covers square convolutions (kernel, stride, dilation, padding)")
-        if dil * (k - 1) > 127:
-            raise NotImplementedError(f"dilation {dil}: tap offsets are 8-bit")
+    @staticmethod
+    def _specs(conv, norm) -> "tuple[ConvSpec, Optional[BNSpec]]":
+        """a unit's layers as specs: nn.Conv2d / nn.BatchNorm2d / None / nn.Identity, or specs already"""
+        if not isinstance(conv, ConvSpec):
+            conv = ConvSpec.from_conv(conv)
+        if norm is None or isinstance(norm, (BNSpec, nn.Identity)):
+            return conv, norm if isinstance(norm, BNSpec) else None
+        if not isinstance(norm, nn.BatchNorm2d):
+            raise NotImplementedError(f"norm {type(norm).__name__} is outside the hot path")
+        return conv, BNSpec.from_bn(norm)
+
+    def conv_unit(self, x: TRef, conv, norm, relu, residual: Optional[TRef] = None, out: Optional[TRef] = None,
+                  name: str = "", pool_out: Optional[TRef] = None) -> TRef:
+        """y = [relu]([bn](conv(x))) [+ residual], written to `out` when given.  `conv`: nn.Conv2d or ConvSpec, `norm`:
+        nn.BatchNorm2d, BNSpec, nn.Identity or None.  `pool_out`: MaxPool2d(3, 2, 1) of y goes there as well -- from the
+        unit's own normalise pass where it has one (vt_bn_act_apply_pool), and then the unit's BatchNorm backward reads the
+        pooled gradient through the arg-max taps instead of a materialised d(y).
+        Validation and dispatch: grouped -> depthwise -> pointwise -> the general kernels."""
+        conv, bn_spec = self._specs(conv, norm)
+        relu = int(relu)  # activation code: 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 SiLU, 4 GELU (include/vt_amd.h)
         if conv.groups != 1:
-            self.tag -= 1
-            self.n_units -= 1
-            return self._grouped_unit(x, conv, norm, relu, residual, out, name, pool_out)
+            return self._grouped_unit(x, conv, bn_spec, relu, residual, out, name, pool_out)
+        dt, epc = self.dtype, _EPC[self.dtype]
+        k, Cout = conv.k, conv.out_channels
         if k * k > N.VT_MAX_TAPS:
             raise NotImplementedError(f"kernel {k}x{k} exceeds {N.VT_MAX_TAPS} taps")
-        Cout, Cin_w = conv.out_channels, conv.in_channels
-        logical_cin = getattr(x, "logical_C", x.C)
-        if logical_cin != Cin_w:
-            raise ValueError(f"conv expects {Cin_w} input channels, got {logical_cin}")
+        if x.logical_c != conv.in_channels:
+            raise ValueError(f"conv expects {conv.in_channels} input channels, got {x.logical_c}")
         if Cout % epc:
             raise NotImplementedError(f"out_channels={Cout} must be a multiple of {epc} for dtype {dt}")
-        has_bn = isinstance(norm, nn.BatchNorm2d) or getattr(norm, "_vt_bn", False)
-        if norm is not None and not has_bn and not isinstance(norm, nn.Identity):
-            raise NotImplementedError(f"norm {type(norm).__name__} is outside the hot path")
-        if has_bn and (norm.momentum is None or not norm.affine or not norm.track_running_stats):
-            raise NotImplementedError("BatchNorm2d variants other than the default are outside the hot path")
-        relu = int(relu)  # activation code: 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 SiLU, 4 GELU (include/vt_amd.h)
-        generic_act = relu >= 2  # only the unfused BatchNorm passes implement these (off the Darknet / VoVNet path)
-        Ho = (x.H + 2 * pad - dil * (k - 1) - 1) // s + 1
-        Wo = (x.W + 2 * pad - dil * (k - 1) - 1) // s + 1
+        Ho, Wo = conv.out_size(x.H, x.W)
         if Ho <= 0 or Wo <= 0:
             raise ValueError(f"{name}: a {x.H}x{x.W} map is smaller than the dilated {k}x{k} kernel")
-        ntaps = k * k
-        B = x.B
-        M = B * Ho * Wo
-
-        if has_bn:
-            spec = (conv, norm, relu, residual, out, name)
+        if bn_spec is not None:
+            spec = (conv, bn_spec, relu, residual, out, name)
             if self._pw_ok(x, [spec]):
-                self.tag -= 1  # (pw_units takes its own tag)
-                self.n_units -= 1
                 y_pw = self.pw_units(x, [spec])[0]
                 if pool_out is not None:
                     self.maxpool3x3s2(y_pw, out=pool_out, name=name + ".max_pool")
                 return y_pw
+        assert out is None or (out.B, out.H, out.W, out.C) == (x.B, Ho, Wo, Cout), "out geometry mismatch"
+        assert residual is None or (residual.B, residual.H, residual.W, residual.C) == (x.B, Ho, Wo, Cout)
 
-        # ---- filter operand ---------------------------------------------------------
-        w = conv.weight
-        padded = x.C != Cin_w  # stem: 3 channels padded to one 16-byte chunk
-        if padded:
-            wpack = self.alloc(Cout * ntaps * x.C * _ESIZE[dt], "wpad")
-            self.emit(N.OP_MEMSET, [self.bp(wpack)], [0], [wpack.nbytes])
-            # (bf16: from the mirror every other filter is read from -- the same rounding of the same master value, and
-            #  under the sharded gradient exchange the mirror is what the all-gather refreshes on every rank, whereas the
-            #  f32 master of a slice another rank owns goes stale)
-            wsrc, wsrc_dt = (self.pref(w, mirror=True), dt) if dt == N.VT_BF16 else (self.pref(w), N.VT_F32)
-            self.emit(N.OP_COPY2D, [wsrc, self.bp(wpack)], [wsrc_dt, dt, Cin_w, 0],
-                      [Cin_w, x.C, Cout * ntaps])
-            wptr = self.bp(wpack)
-        elif dt == N.VT_F32:
-            wptr = self.pref(w)
-        else:
-            wptr = self.pref(w, mirror=True)
-        ldw = ntaps * x.C
-
-        if out is not None:
-            assert (out.B, out.H, out.W, out.C) == (B, Ho, Wo, Cout), "out geometry mismatch"
-        if residual is not None:
-            assert (residual.B, residual.H, residual.W, residual.C) == (B, Ho, Wo, Cout)
-
-        track = self.need_grad
+        self.tag += 1
+        self.n_units += 1
+        wptr, wpack, ldw = self._filter_operand(conv, x)
+        has_bn, generic_act = bn_spec is not None, relu >= 2  # (generic: only the unfused BatchNorm passes implement these)
+        track, w, s, pad = self.need_grad, conv.weight, conv.stride, conv.padding
         # the unit follows ITS BatchNorm's flag (a frozen bn.eval() inside a training model uses the
         # running statistics and leaves them untouched, like nn.BatchNorm2d)
-        unit_training = bool(norm.training) if has_bn else self.training
+        unit_training = bn_spec.training if has_bn else self.training
         fused = has_bn and not unit_training and not track and not generic_act
-        y = out if out is not None else self.act(B, Ho, Wo, Cout, name + ".y")
-        z = None
-        coef = None
-        stem_fused = (track and padded and has_bn and not fused and residual is None and not generic_act and
-                      not x.needs_grad and w.requires_grad and dt == N.VT_BF16 and Cout == 32 and k == 3 and s == 1 and
-                      dil == 1 and pad == 1 and x.C == 8 and x.ld == 8 and x.W <= 888 and B * (x.H + 1) * (x.W + 1) < 0x7fff0000)  # (ring in LDS: halo <= 896 rows)
-        stem_y = stem_fused and unit_training and x.W <= 824  # (one more step of halo)
+        y = out if out is not None else self.act(x.B, Ho, Wo, Cout, name + ".y")
+        u = _ConvUnit(conv, relu, x, y, residual, name, self.tag, wptr, wpack, ldw)
+        u.stem_fused = stem_fused = (
+            track and u.padded and has_bn and not fused and residual is None and not generic_act and
+            not x.needs_grad and w.requires_grad and dt == N.VT_BF16 and Cout == 32 and k == 3 and s == 1 and
+            conv.dilation == 1 and pad == 1 and x.C == 8 and x.ld == 8 and x.W <= 888 and
+            x.B * (x.H + 1) * (x.W + 1) < 0x7fff0000)  # (ring in LDS: halo <= 896 rows)
+        u.stem_y = stem_y = stem_fused and unit_training and x.W <= 824  # (one more step of halo)
         if has_bn:
-            coef = self.f32(4 * Cout, "bncoef")  # scale, shift, mean, invstd
-            cp = [self.bp(coef, i * Cout * 4) for i in range(4)]
-            g, b_, rm, rv = (self.pref(norm.weight), self.pref(norm.bias), self.pref(norm.running_mean),
-                             self.pref(norm.running_var))
-            nbt = self.pref(norm.num_batches_tracked) if norm.num_batches_tracked is not None else None
-        if fused:
-            self.emit(N.OP_BN_EVAL_COEFFS, [g, b_, rm, rv, cp[0], cp[1], None, None], [Cout], [norm.eps])
-            flags = N.VT_CONV_AFFINE | (N.VT_CONV_RELU if relu else 0) | (N.VT_CONV_RESIDUAL if residual else 0)
-            d = self._conv_desc(x, Cout, Ho, Wo, s, pad, k, y.ld, ldw, flags, residual.ld if residual else 0, dil=dil)
-            self.emit(N.OP_CONV_IGEMM, [x.addr(), wptr, y.addr(), cp[0], cp[1],
-                                        residual.addr() if residual else None, None], desc=d)
-        elif stem_y:
-            y.stem_out = True  # (the unit that reads it releases its filter gradient late: wgrad_late_stem)
-            stats = self.zeroed_f32(N.stat_floats(Cout), "stats")
-            d = self._conv_desc(x, Cout, Ho, Wo, s, pad, k, y.ld, ldw, N.VT_CONV_STATS | N.VT_CONV_NOSTORE, dil=dil)
-            self.emit(N.OP_CONV_IGEMM, [x.addr(), wptr, None, None, None, None, self.bp(stats)], desc=d)
-            self.emit(N.OP_BN_FINALIZE,
-                      [self.bp(stats), g, b_, rm, rv, nbt, *cp],
-                      [Cout], [M * self.bn_world, norm.eps, norm.momentum])
-            d = self._conv_desc(x, Cout, Ho, Wo, s, pad, k, y.ld, ldw, N.VT_CONV_AFFINE | (N.VT_CONV_RELU if relu else 0), dil=dil)
-            self.emit(N.OP_CONV_IGEMM, [x.addr(), wptr, y.addr(), cp[0], cp[1], None, None], desc=d)
-        elif has_bn:
-            z = self.act(B, Ho, Wo, Cout, name + ".z")
-            if unit_training:
-                stats = self.zeroed_f32(N.stat_floats(Cout), "stats")
-                d = self._conv_desc(x, Cout, Ho, Wo, s, pad, k, z.ld, ldw, N.VT_CONV_STATS, dil=dil)
-                fin_fwd = (self.bn_fin_apply and not self.bn_sync and not generic_act and
-                           not (pool_out is not None and not generic_act))
-                self.emit(N.OP_CONV_IGEMM, [x.addr(), wptr, z.addr(), None, None, None, self.bp(stats)], desc=d)
-                if not fin_fwd:
-                    self.emit(N.OP_BN_FINALIZE,
-                              [self.bp(stats), g, b_, rm, rv, nbt, *cp],
-                              [Cout], [M * self.bn_world, norm.eps, norm.momentum])
-            else:
-                fin_fwd = False
-                d = self._conv_desc(x, Cout, Ho, Wo, s, pad, k, z.ld, ldw, 0, dil=dil)
-                self.emit(N.OP_CONV_IGEMM, [x.addr(), wptr, z.addr(), None, None, None, None], desc=d)
-                self.emit(N.OP_BN_EVAL_COEFFS, [g, b_, rm, rv, *cp], [Cout], [norm.eps])
-            pool_am = None
-            if pool_out is not None and not generic_act:
-                assert (pool_out.B, pool_out.H, pool_out.W, pool_out.C) == (B, (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1, Cout)
-                pool_am = self.alloc(B * pool_out.H * pool_out.W * Cout, "argmax")
-                self.emit(N.OP_BN_ACT_APPLY,
-                          [z.addr(), cp[0], cp[1], residual.addr() if residual else None, y.addr(), pool_out.addr(),
-                           self.bp(pool_am)],
-                          [z.ld, residual.ld if residual else 0, y.ld, Cout, int(relu), dt, pool_out.ld, B, Ho, Wo], [M])
-            elif fin_fwd:
-                self.emit(N.OP_BN_FIN_APPLY,
-                          [self.bp(stats), g, b_, rm, rv, nbt, *cp, z.addr(),
-                           residual.addr() if residual else None, y.addr()],
-                          [Cout, z.ld, residual.ld if residual else 0, y.ld, int(relu), dt],
-                          [M * self.bn_world, norm.eps, norm.momentum, M])
-            else:
-                self.emit(N.OP_BN_ACT_APPLY,
-                          [z.addr(), cp[0], cp[1], residual.addr() if residual else None, y.addr()],
-                          [z.ld, residual.ld if residual else 0, y.ld, Cout, int(relu), dt], [M])
-        elif relu:
-            # conv (+bias) -> activation, no BatchNorm: ConvNormAct(norm="none") (components.py:33-36).  The
-            # pre-activation is kept (backward needs act'(z)); the activation is the unit-scale form of the normalise pass.
-            z = self.act(B, Ho, Wo, Cout, name + ".z")
-            d = self._conv_desc(x, Cout, Ho, Wo, s, pad, k, z.ld, ldw, N.VT_CONV_AFFINE if conv.bias is not None else 0,
-                                dil=dil)
-            self.emit(N.OP_CONV_IGEMM,
-                      [x.addr(), wptr, z.addr(), None, self.pref(conv.bias) if conv.bias is not None else None,
-                       None, None], desc=d)
-            self.emit(N.OP_BN_ACT_APPLY,
-                      [z.addr(), None, None, residual.addr() if residual else None, y.addr()],
-                      [z.ld, residual.ld if residual else 0, y.ld, Cout, int(relu), dt], [M])
-        else:
-            # plain conv (+bias): ESE gate conv (vovnet.py:24), classifier head (classifier.py:63)
-            flags = (N.VT_CONV_AFFINE if conv.bias is not None else 0) | (N.VT_CONV_RESIDUAL if residual else 0)
-            d = self._conv_desc(x, Cout, Ho, Wo, s, pad, k, y.ld, ldw, flags, residual.ld if residual else 0, dil=dil)
-            self.emit(N.OP_CONV_IGEMM,
-                      [x.addr(), wptr, y.addr(), None, self.pref(conv.bias) if conv.bias is not None else None,
-                       residual.addr() if residual else None, None], desc=d)
-
+            u.bn = _BNEmitter(self, bn_spec, Cout)
         pool_fused = pool_out is not None and has_bn and not fused and not stem_y and not generic_act
+        if fused:
+            self._fwd_inference_fused(u)
+        elif stem_y:
+            self._fwd_stem(u)
+        elif has_bn:
+            self._fwd_bn(u, pool_out if pool_fused else None)
+        elif relu:
+            self._fwd_act(u)
+        else:
+            self._fwd_plain(u)
         if pool_out is not None and not pool_fused:
             self.maxpool3x3s2(y, out=pool_out, name=name + ".max_pool")  # (no normalise pass to fuse it into)
 
-        wg_key = None
         # (round 5: the 1x1 stride-1 units of a stage too -- DarknetBlock.conv1, darknet.py:23 -- through the general
         #  kernel's grouped launch: a launch of one such layer is mostly its atomic flush and its ramp)
-        grp3 = k == 3 and s == 1 and dil == 1 and pad == 1 and x.C > 32 and Cout > 32
+        grp3 = k == 3 and s == 1 and conv.dilation == 1 and pad == 1 and x.C > 32 and Cout > 32
         grp1 = k == 1 and s == 1 and pad == 0 and self.wgrad_group_1x1
-        if (track and has_bn and not fused and not stem_fused and not padded and w.requires_grad and dt == N.VT_BF16 and
+        if (track and has_bn and not fused and not stem_fused and not u.padded and w.requires_grad and dt == N.VT_BF16 and
                 (grp3 or grp1) and self.wgrad_group > 1 and not self.deterministic):
-            wg_key = (k, B, x.H, x.W, x.C, x.ld, Cout, ldw)
-            self._wg_expect[wg_key] = self._wg_expect.get(wg_key, 0) + 1
-
+            u.wg_key = (k, x.B, x.H, x.W, x.C, x.ld, Cout, ldw)
+            self._wg_expect[u.wg_key] = self._wg_expect.get(u.wg_key, 0) + 1
         if track:
-            tag = self.tag
-            training = unit_training
-
-            def bwd():
-                self.tag = tag
-                pool_grad = None  # (fused pool: the gradient of the pooled map, read through the arg-max taps)
-                if pool_fused:
-                    dp = self.grad_read(pool_out)
-                    if dp is not None:
-                        if residual is None and not stem_fused and self.grad_read(y) is None:
-                            pool_grad = dp  # the pool is y's only consumer: d(y) is never formed
-                        else:  # y feeds something else too (a returned feature map, a shortcut): form d(y) as the pool's backward would
-                            gy, res_ = self.grad_target(y)
-                            acc = 0
-                            if res_ is not None:
-                                if res_ is gy or (res_.buf is gy.buf and res_.coff == gy.coff):
-                                    acc = 1
-                                else:
-                                    self._add_into(gy, res_, False)
-                                    acc = 1
-                            self.emit(N.OP_MAXPOOL_BWD, [dp.addr(), self.bp(pool_am), gy.addr()],
-                                      [dp.ld, gy.ld, B, Ho, Wo, Cout, acc, dt])
-                            self.grad_written(y)
-                dy = self.grad_read(y) if pool_grad is None else None
-                if dy is None and pool_grad is None:
-                    return
-                if residual is not None:
-                    self.grad_add(residual, dy)
-                if stem_fused:
-                    # dz = a*g - b*z + d feeds nothing but the filter gradient (the unit's input is the image): the
-                    # pass that reduces (sum g, sum g*xhat) also correlates g, z and 1 with the tap-shifted x, and a
-                    # small kernel finishes dW = a*G - b*Z + d*X once (a, b, d) exist (vt_stem_bwd.hip)
-                    sums = self.zeroed_f32(N.stat_floats(Cout), "bwdsums")
-                    gzx = self.zeroed_f32(N.lib().vt_stem_bn_bwd_scratch_bytes(Cout) // 4, "stem_gzx")
-                    zy = y if stem_y else z
-                    self.emit(N.OP_STEM_BWD_REDUCE,
-                              [x.addr(), dy.addr(), zy.addr(), cp[0], cp[1], cp[2], cp[3], self.bp(sums), self.bp(gzx)],
-                              [dt, B, x.H, x.W, Cout, dy.ld, zy.ld, int(relu), int(self.deterministic) | (2 if stem_y else 0)])
-                    if stem_y:  # sum g * xhat from the correlations (z is linear in the patch): nothing recovered from y
-                        self.emit(N.OP_STEM_BWD_S2, [self.bp(gzx), wptr, cp[2], cp[3], self.bp(sums)],
-                                  [Cout, int(self.deterministic)])
-                    bcoef = self.f32(3 * Cout, "bwdcoef")
-                    self.emit(N.OP_BN_BWD_FINALIZE,
-                              [self.bp(sums), cp[0], cp[2], cp[3], self.pgrad(norm.weight), self.pgrad(norm.bias),
-                               self.bp(bcoef)], [Cout, int(training)], [M * self.bn_world, 1.0 / self.bn_world])
-                    self.emit(N.OP_STEM_BWD_COMBINE, [self.bp(gzx), self.bp(bcoef), self.pgrad(w), wptr if stem_y else None],
-                              [Cout, Cin_w, int(self.deterministic)])
-                    return
-                if has_bn:
-                    sums = self.zeroed_f32(N.stat_floats(Cout), "bwdsums")
-                    g_ = pool_grad if pool_grad is not None else dy
-                    am_ = [self.bp(pool_am)] if pool_grad is not None else []
-                    geo = [B, Ho, Wo] if pool_grad is not None else []
-                    rec = self._last_dgrad.get(id(dy.buf)) if (self.fuse_bnred and pool_grad is None and dt == N.VT_BF16 and
-                                                                not generic_act and self._cur is self.bwd) else None
-                    fused_red = rec is not None and rec[1] == dy.coff and rec[2] == dy.coff + dy.C and any(o is rec[0] for o in self.bwd)
-                    one_launch = (self.bn_bwd_fused and not fused_red and pool_grad is None and dt == N.VT_BF16 and
-                                  not generic_act and not self.bn_sync)
-                    bcoef = self.f32(3 * Cout, "bwdcoef")
-                    dz = self.act(B, Ho, Wo, Cout, name + ".dz")
-                    if one_launch:
-                        sync = self.zeroed_f32(4, "bwdsync")
-                        self.emit(N.OP_BN_BWD_FUSED,
-                                  [dy.addr(), z.addr(), cp[0], cp[1], cp[2], cp[3], self.bp(sums), self.bp(sync),
-                                   self.pgrad(norm.weight), self.pgrad(norm.bias), self.bp(bcoef), dz.addr()],
-                                  [dy.ld, z.ld, dz.ld, Cout, int(relu), dt, int(training)], [M, M * self.bn_world, 1.0 / self.bn_world])
-                    else:
-                        if fused_red:
-                            # d(y) came out of ONE data-gradient launch and nothing was added to it since: that launch also forms
-                            # this unit's backward sums (the op is patched in place: ptr dz w dy | z scale shift mean invstd sums)
-                            fop = rec[0]
-                            fop.kind = N.OP_CONV_DGRAD_BNRED | (fop.kind & N.OP_SIDE_STREAM)
-                            for k_, pa in ((3, z.addr()), (4, cp[0]), (5, cp[1]), (6, cp[2]), (7, cp[3]), (8, self.bp(sums))):
-                                fop.ptr[k_].base, fop.ptr[k_].offset = pa
-                            k0 = C.sizeof(N.ConvDesc) // 4
-                            fop.i[k0], fop.i[k0 + 1] = z.ld, int(relu)
-                            self._last_dgrad.pop(id(dy.buf), None)
-                        else:
-                            self.emit(N.OP_BN_BWD_REDUCE,
-                                      [g_.addr(), z.addr(), cp[0], cp[1], cp[2], cp[3], self.bp(sums)] + am_,
-                                      [g_.ld, z.ld, Cout, int(relu), dt] + geo, [M])
-                        if self.bn_fin_apply and not self.bn_sync and pool_grad is None and not generic_act:
-                            self.emit(N.OP_BN_BWD_FIN_APPLY,
-                                      [self.bp(sums), cp[0], cp[1], cp[2], cp[3], self.pgrad(norm.weight), self.pgrad(norm.bias),
-                                       self.bp(bcoef), g_.addr(), z.addr(), dz.addr()],
-                                      [Cout, int(training), g_.ld, z.ld, dz.ld, int(relu), dt],
-                                      [M * self.bn_world, 1.0 / self.bn_world, M])
-                        else:
-                            self.emit(N.OP_BN_BWD_FINALIZE,
-                                      [self.bp(sums), cp[0], cp[2], cp[3], self.pgrad(norm.weight), self.pgrad(norm.bias),
-                                       self.bp(bcoef)], [Cout, int(training)], [M * self.bn_world, 1.0 / self.bn_world])
-                            self.emit(N.OP_BN_BWD_APPLY,
-                                      [g_.addr(), z.addr(), cp[0], cp[1], self.bp(bcoef), dz.addr()] + am_,
-                                      [g_.ld, z.ld, dz.ld, Cout, int(relu), dt] + geo, [M])
-                else:
-                    dz = dy
-                    if relu:  # dz = dy * act'(z)
-                        dz = self.act(B, Ho, Wo, Cout, name + ".dz")
-                        self.emit(N.OP_BN_BWD_APPLY, [dy.addr(), z.addr(), None, None, None, dz.addr()],
-                                  [dy.ld, z.ld, dz.ld, Cout, int(relu), dt], [M])
-                    if conv.bias is not None and conv.bias.requires_grad:
-                        if self.deterministic:
-                            qb = self.zeroed_f32(4 * Cout, "dbq", bwd=True)
-                            self.emit(N.OP_COLSUM, [dz.addr(), self.bp(qb)], [dz.ld, Cout, dt, 1], [M])
-                            self.emit(N.OP_FIXED_TO_F32, [self.bp(qb), self.pgrad(conv.bias)], [1], [Cout])
-                        else:
-                            self.emit(N.OP_COLSUM, [dz.addr(), self.pgrad(conv.bias)], [dz.ld, Cout, dt], [M])
-                # filter gradient: needs only x and dz and nothing in backward waits for it, so it goes to the
-                # side stream, beside the HBM-bound BatchNorm passes of the units that follow in backward order
-                def emit_wgrad():
-                    if not w.requires_grad:
-                        return
-                    dfwd = self._conv_desc(x, Cout, Ho, Wo, s, pad, k, dz.ld, ldw, 0, dil=dil)
-                    if wg_key is not None:
-                        self._wgrad_hold(wg_key, x.addr(), dz.addr(), self.pgrad(w), dfwd, ldw)
-                        return
-                    self.emit(N.OP_FORK)
-                    slab, slab_mb = None, 0
-                    if self.wgrad_slab_mb > 0:  # two-stage (stored slabs + ordered reducer) instead of f32 atomics
-                        if self._wgrad_slab is None:
-                            self._wgrad_slab = self.alloc(self.wgrad_slab_mb << 20, "wgrad_slabs")
-                        slab, slab_mb = self.bp(self._wgrad_slab), self.wgrad_slab_mb
-                    if padded:
-                        ws = self.zeroed_f32(Cout * ntaps * x.C, "dwpad", bwd=True)
-                        self.emit(N.OP_CONV_WGRAD, [x.addr(), dz.addr(), self.bp(ws), slab], desc=dfwd,
-                                  extra_ints=[ldw, slab_mb], side=True)
-                        self.emit(N.OP_COPY2D, [self.bp(ws), self.pgrad(w)], [N.VT_F32, N.VT_F32, Cin_w, 1],
-                                  [x.C, Cin_w, Cout * ntaps], side=True)
-                    else:
-                        self.emit(N.OP_CONV_WGRAD, [x.addr(), dz.addr(), self.pgrad(w), slab], desc=dfwd,
-                                  extra_ints=[ldw, slab_mb], side=True)
-
-                # Released BEFORE the unit's data gradient, except behind the stem (see __init__): there the data gradient
-                # runs first and the filter gradient beside the stem's one-pass backward.
-                late = x.needs_grad and getattr(x, "stem_out", False)
-                if not late:
-                    emit_wgrad()
-                # data gradient
-                if x.needs_grad:
-                    self._dgrad(x, dz, wptr if not padded else self.bp(wpack), dt if (padded or dt != N.VT_F32) else N.VT_F32,
-                                ldw, Cout, k, s, pad, Ho, Wo, dil)
-                if late:
-                    emit_wgrad()
-
-            self.nodes.append(bwd)
+            self.nodes.append(lambda: self._conv_unit_bwd(u))
         return y
 
-    def _grouped_unit(self, x: TRef, conv, norm, relu, residual, out, name, pool_out) -> TRef:
+    def _filter_operand(self, conv: ConvSpec, x: TRef):
+        """(address, padded copy or None, row length) of the filter image the unit's launches read: the f32 master, its bf16
+        mirror, or -- the stem, whose 3 input channels are padded to one 16-byte chunk -- a zero-padded copy in the arena"""
+        dt, w, Cin_w, rows = self.dtype, conv.weight, conv.in_channels, conv.out_channels * conv.k ** 2
+        if x.C == Cin_w:
+            return self.pref(w, mirror=dt != N.VT_F32), None, conv.k ** 2 * x.C
+        wpack = self.alloc(rows * x.C * _ESIZE[dt], "wpad")
+        self.emit(N.OP_MEMSET, [self.bp(wpack)], [0], [wpack.nbytes])
+        # (bf16: from the mirror every other filter is read from -- the same rounding of the same master value, and
+        #  under the sharded gradient exchange the mirror is what the all-gather refreshes on every rank, whereas the
+        #  f32 master of a slice another rank owns goes stale)
+        wsrc, wsrc_dt = (self.pref(w, mirror=True), dt) if dt == N.VT_BF16 else (self.pref(w), N.VT_F32)
+        self.emit(N.OP_COPY2D, [wsrc, self.bp(wpack)], [wsrc_dt, dt, Cin_w, 0], [Cin_w, x.C, rows])
+        return self.bp(wpack), wpack, conv.k ** 2 * x.C
+
+    def _unit_desc(self, u: "_ConvUnit", ldy: int, flags: int, ldr: int = 0) -> N.ConvDesc:
+        c = u.conv
+        return self._conv_desc(u.x, c.out_channels, u.y.H, u.y.W, c.stride, c.padding, c.k, ldy, u.ldw, flags, ldr, dil=c.dilation)
+
+    def _conv(self, u: "_ConvUnit", dst: Optional[TRef], flags: int = 0, scale=None, shift=None, res: Optional[TRef] = None,
+              stats: Optional[Buf] = None):
+        """the unit's convolution into dst (None: nothing is stored), with the epilogue its operands ask for"""
+        flags |= (N.VT_CONV_AFFINE if shift is not None else 0) | (N.VT_CONV_RESIDUAL if res is not None else 0) | \
+            (N.VT_CONV_STATS if stats is not None else 0)
+        self.emit(N.OP_CONV_IGEMM, [u.x.addr(), u.wptr, _addr(dst), scale, shift, _addr(res), self.bp(stats) if stats else None],
+                  desc=self._unit_desc(u, (dst or u.y).ld, flags, _ld(res)))
+
+    def _fwd_inference_fused(self, u: "_ConvUnit") -> None:
+        """eval-mode BatchNorm without gradients: ONE conv launch with the affine (+ ReLU, + residual) epilogue"""
+        u.bn.eval_coeffs(scale_shift_only=True)
+        self._conv(u, u.y, N.VT_CONV_RELU if u.relu else 0, u.bn.cp[0], u.bn.cp[1], u.residual)
+
+    def _fwd_stem(self, u: "_ConvUnit") -> None:
+        """the stem with recomputed z: the conv runs twice (statistics only, then with the normalise + ReLU epilogue)"""
+        u.y.stem_out = True  # (the unit that reads it releases its filter gradient late: wgrad_late_stem)
+        stats = self.zeroed_f32(N.stat_floats(u.y.C), "stats")
+        self._conv(u, None, N.VT_CONV_NOSTORE, stats=stats)
+        u.bn.finalize(stats, u.y.M)
+        self._conv(u, u.y, N.VT_CONV_RELU if u.relu else 0, u.bn.cp[0], u.bn.cp[1])
+
+    def _fwd_bn(self, u: "_ConvUnit", pool_out: Optional[TRef]) -> None:
+        """BatchNorm with stored z: conv (+ batch statistics) -> coefficients -> the normalise pass, which may also
+        finalize the statistics for itself (vt_bn_finalize_apply) or write the 3x3 stride-2 max pool of y"""
+        y, bn, res, relu = u.y, u.bn, u.residual, u.relu
+        u.z = z = self.act(y.B, y.H, y.W, y.C, u.name + ".z")
+        fin_fwd = False
+        if bn.spec.training:
+            stats = self.zeroed_f32(N.stat_floats(y.C), "stats")
+            fin_fwd = self.bn_fin_apply and not self.bn_sync and relu < 2 and pool_out is None
+            self._conv(u, z, stats=stats)
+            if not fin_fwd:
+                bn.finalize(stats, y.M)
+        else:
+            self._conv(u, z)
+            bn.eval_coeffs()
+        if pool_out is not None:
+            assert (pool_out.B, pool_out.H, pool_out.W, pool_out.C) == (y.B, (y.H - 1) // 2 + 1, (y.W - 1) // 2 + 1, y.C)
+            u.pool_out, u.pool_am = pool_out, self.alloc(y.B * pool_out.H * pool_out.W * y.C, "argmax")
+            self._act_apply(z, bn.cp[0], bn.cp[1], res, y, relu, [pool_out.addr(), self.bp(u.pool_am)],
+                            [pool_out.ld, y.B, y.H, y.W])
+        elif fin_fwd:
+            ptrs, flts = bn.finalize_operands(stats, y.M)
+            self.emit(N.OP_BN_FIN_APPLY, ptrs + [z.addr(), _addr(res), y.addr()],
+                      [y.C, z.ld, _ld(res), y.ld, relu, self.dtype], flts + [y.M])
+        else:
+            self._act_apply(z, bn.cp[0], bn.cp[1], res, y, relu)
+
+    def _fwd_act(self, u: "_ConvUnit") -> None:
+        """conv (+bias) -> activation, no BatchNorm: ConvNormAct(norm="none") (components.py:33-36).  The
+        pre-activation is kept (backward needs act'(z)); the activation is the unit-scale form of the normalise pass."""
+        u.z = self.act(u.y.B, u.y.H, u.y.W, u.y.C, u.name + ".z")
+        self._conv(u, u.z, shift=self.pref(u.conv.bias))
+        self._act_apply(u.z, None, None, u.residual, u.y, u.relu)
+
+    def _fwd_plain(self, u: "_ConvUnit") -> None:
+        """plain conv (+bias): ESE gate conv (vovnet.py:24), classifier head (classifier.py:63)"""
+        self._conv(u, u.y, shift=self.pref(u.conv.bias), res=u.residual)
+
+    def _act_apply(self, z: TRef, scale, shift, residual: Optional[TRef], y: TRef, act: int, pool_ptrs=(), pool_ints=()):
+        """y = act(z * scale + shift) [+ residual] (vt_bn_act_apply; scale / shift None: unit scale, no shift)"""
+        self.emit(N.OP_BN_ACT_APPLY, [z.addr(), scale, shift, _addr(residual), y.addr(), *pool_ptrs],
+                  [z.ld, _ld(residual), y.ld, y.C, int(act), self.dtype, *pool_ints], [y.M])
+
+    def _act_bwd(self, g: TRef, z: TRef, scale, shift, bcoef, dz: TRef, act: int, taps=None):
+        """dz = act'(.) * g [- the BatchNorm backward terms of `bcoef`] (vt_bn_act_bwd_apply; no coefficients: the
+        activation's backward alone, at the pre-activation z).  `taps` = (arg-max address, [B, Ho, Wo]): g is the gradient
+        of the fused max pool."""
+        self.emit(N.OP_BN_BWD_APPLY, [g.addr(), z.addr(), scale, shift, bcoef, dz.addr()] + ([taps[0]] if taps else []),
+                  [g.ld, z.ld, dz.ld, dz.C, int(act), self.dtype] + (taps[1] if taps else []), [dz.M])
+
+    # .. backward of the unit, from the record its forward left ..........................................................
+    def _conv_unit_bwd(self, u: "_ConvUnit") -> None:
+        self.tag = u.tag
+        x, y, c = u.x, u.y, u.conv
+        pool_grad = None  # (fused pool: the gradient of the pooled map, read through the arg-max taps)
+        if u.pool_out is not None:
+            dp = self.grad_read(u.pool_out)
+            if dp is not None:
+                if u.residual is None and not u.stem_fused and self.grad_read(y) is None:
+                    pool_grad = dp  # the pool is y's only consumer: d(y) is never formed
+                else:  # y feeds something else too (a returned feature map, a shortcut): form d(y) as the pool's backward would
+                    gy, acc = self.grad_accum_target(y)
+                    self.emit(N.OP_MAXPOOL_BWD, [dp.addr(), self.bp(u.pool_am), gy.addr()],
+                              [dp.ld, gy.ld, x.B, u.y.H, u.y.W, y.C, acc, self.dtype])
+                    self.grad_written(y)
+        dy = self.grad_read(y) if pool_grad is None else None
+        if dy is None and pool_grad is None:
+            return
+        self.grad_add(u.residual, dy)
+        if u.stem_fused:
+            return self._stem_bwd(u, dy)
+        dz = self._bn_bwd(u, dy, pool_grad) if u.bn is not None else self._act_bias_bwd(u, dy)
+        # Released BEFORE the unit's data gradient, except behind the stem (see __init__): there the data gradient
+        # runs first and the filter gradient beside the stem's one-pass backward.
+        late = x.needs_grad and x.stem_out
+        if not late:
+            self._release_wgrad(u, dz)
+        if x.needs_grad:
+            self._dgrad(x, dz, u.wptr, u.ldw, c)
+        if late:
+            self._release_wgrad(u, dz)
+
+    def _stem_bwd(self, u: "_ConvUnit", dy: TRef) -> None:
+        # dz = a*g - b*z + d feeds nothing but the filter gradient (the unit's input is the image): the
+        # pass that reduces (sum g, sum g*xhat) also correlates g, z and 1 with the tap-shifted x, and a
+        # small kernel finishes dW = a*G - b*Z + d*X once (a, b, d) exist (vt_stem_bwd.hip)
+        x, cp, Cout, det = u.x, u.bn.cp, u.y.C, int(self.deterministic)
+        sums = self.zeroed_f32(N.stat_floats(Cout), "bwdsums")
+        gzx = self.zeroed_f32(N.lib().vt_stem_bn_bwd_scratch_bytes(Cout) // 4, "stem_gzx")
+        zy = u.y if u.stem_y else u.z
+        self.emit(N.OP_STEM_BWD_REDUCE, [x.addr(), dy.addr(), zy.addr(), *cp, self.bp(sums), self.bp(gzx)],
+                  [self.dtype, x.B, x.H, x.W, Cout, dy.ld, zy.ld, u.relu, det | (2 if u.stem_y else 0)])
+        if u.stem_y:  # sum g * xhat from the correlations (z is linear in the patch): nothing recovered from y
+            self.emit(N.OP_STEM_BWD_S2, [self.bp(gzx), u.wptr, cp[2], cp[3], self.bp(sums)], [Cout, det])
+        bcoef = self.f32(3 * Cout, "bwdcoef")
+        u.bn.bwd_finalize(sums, bcoef, u.y.M)
+        self.emit(N.OP_STEM_BWD_COMBINE, [self.bp(gzx), self.bp(bcoef), self.pgrad(u.conv.weight), u.wptr if u.stem_y else None],
+                  [Cout, u.conv.in_channels, det])
+
+    def _bn_bwd(self, u: "_ConvUnit", dy: Optional[TRef], pool_grad: Optional[TRef]) -> TRef:
+        """dz of a BatchNorm unit from d(y) (or from the gradient of its fused max pool): reduce -> finalize -> apply, the
+        last two in one launch by default, or one of the two off-by-default fused forms (see __init__)"""
+        bn, z, relu, M, dt = u.bn, u.z, u.relu, u.y.M, self.dtype
+        plain = pool_grad is None and dt == N.VT_BF16 and relu < 2
+        rec = self._last_dgrad.get(id(dy.buf)) if (self.fuse_bnred and plain and self._cur is self.bwd) else None
+        fused_red = rec is not None and rec[1] == dy.coff and rec[2] == dy.coff + dy.C and any(o is rec[0] for o in self.bwd)
+        one_launch = self.bn_bwd_fused and not fused_red and plain and not self.bn_sync
+        sums, bcoef, dz = bn.bwd_buffers(u.y, u.name + ".dz")
+        if one_launch:
+            sync = self.zeroed_f32(4, "bwdsync")
+            self.emit(N.OP_BN_BWD_FUSED,
+                      [dy.addr(), z.addr(), *bn.cp, self.bp(sums), self.bp(sync), *bn.grads(), self.bp(bcoef), dz.addr()],
+                      [dy.ld, z.ld, dz.ld, dz.C, relu, dt, int(bn.spec.training)], [M, M * self.bn_world, 1.0 / self.bn_world])
+            return dz
+        if fused_red:
+            # d(y) came out of ONE data-gradient launch and nothing was added to it since: that launch also forms
+            # this unit's backward sums (the op is patched in place: ptr dz w dy | z scale shift mean invstd sums)
+            fop = rec[0]
+            fop.kind = N.OP_CONV_DGRAD_BNRED | (fop.kind & N.OP_SIDE_STREAM)
+            for k_, pa in enumerate((z.addr(), *bn.cp, self.bp(sums)), start=3):
+                fop.ptr[k_].base, fop.ptr[k_].offset = pa
+            k0 = C.sizeof(N.ConvDesc) // 4
+            fop.i[k0], fop.i[k0 + 1] = z.ld, relu
+            self._last_dgrad.pop(id(dy.buf), None)
+        g = dy if pool_grad is None else pool_grad
+        taps = None if pool_grad is None else (self.bp(u.pool_am), [u.x.B, u.y.H, u.y.W])
+        if self.bn_fin_apply and not self.bn_sync and pool_grad is None and relu < 2:
+            if not fused_red:
+                bn.bwd_reduce(g, z, relu, sums, M)
+            self.emit(N.OP_BN_BWD_FIN_APPLY,
+                      [self.bp(sums), *bn.cp, *bn.grads(), self.bp(bcoef), g.addr(), z.addr(), dz.addr()],
+                      [dz.C, int(bn.spec.training), g.ld, z.ld, dz.ld, relu, dt], [M * self.bn_world, 1.0 / self.bn_world, M])
+        else:
+            bn.bwd_three_launches(g, z, relu, sums, bcoef, dz, taps, reduce=not fused_red)
+        return dz
+
+    def _act_bias_bwd(self, u: "_ConvUnit", dy: TRef) -> TRef:
+        """dz of a unit without BatchNorm (dz = dy * act'(z)), and the bias gradient"""
+        dz, bias = dy, u.conv.bias
+        if u.relu:
+            dz = self.act(dy.B, u.y.H, u.y.W, dy.C, u.name + ".dz")
+            self._act_bwd(dy, u.z, None, None, None, dz, u.relu)
+        if bias is not None and bias.requires_grad:
+            if self.deterministic:
+                qb = self.zeroed_f32(4 * dz.C, "dbq", bwd=True)
+                self.emit(N.OP_COLSUM, [dz.addr(), self.bp(qb)], [dz.ld, dz.C, self.dtype, 1], [u.y.M])
+                self.emit(N.OP_FIXED_TO_F32, [self.bp(qb), self.pgrad(bias)], [1], [dz.C])
+            else:
+                self.emit(N.OP_COLSUM, [dz.addr(), self.pgrad(bias)], [dz.ld, dz.C, self.dtype], [u.y.M])
+        return dz
+
+    def _release_wgrad(self, u: "_ConvUnit", dz: TRef) -> None:
+        # filter gradient: needs only x and dz and nothing in backward waits for it, so it goes to the
+        # side stream, beside the HBM-bound BatchNorm passes of the units that follow in backward order
+        x, w = u.x, u.conv.weight
+        if not w.requires_grad:
+            return
+        dfwd = self._unit_desc(u, dz.ld, 0)
+        if u.wg_key is not None:
+            self._wgrad_hold(u.wg_key, x.addr(), dz.addr(), self.pgrad(w), dfwd, u.ldw)
+            return
+        self.emit(N.OP_FORK)
+        slab, slab_mb = None, 0
+        if self.wgrad_slab_mb > 0:  # two-stage (stored slabs + ordered reducer) instead of f32 atomics
+            if self._wgrad_slab is None:
+                self._wgrad_slab = self.alloc(self.wgrad_slab_mb << 20, "wgrad_slabs")
+            slab, slab_mb = self.bp(self._wgrad_slab), self.wgrad_slab_mb
+        ws = None
+        if u.padded:  # the gradient of the padded filter image, then its first in_channels columns into the parameter's
+            rows = u.conv.out_channels * u.conv.k ** 2
+            ws = self.bp(self.zeroed_f32(rows * x.C, "dwpad", bwd=True))
+        self.emit(N.OP_CONV_WGRAD, [x.addr(), dz.addr(), ws or self.pgrad(w), slab], desc=dfwd,
+                  extra_ints=[u.ldw, slab_mb], side=True)
+        if u.padded:
+            self.emit(N.OP_COPY2D, [ws, self.pgrad(w)], [N.VT_F32, N.VT_F32, u.conv.in_channels, 1],
+                      [x.C, u.conv.in_channels, rows], side=True)
+
+    def _grouped_unit(self, x: TRef, conv: "ConvSpec", bn: "Optional[BNSpec]", relu, residual, out, name, pool_out) -> TRef:
         """nn.Conv2d(groups=G) inside a ConvNormAct (reference components.py:32): G independent units over channel slices
         of x and y -- the kernels take a pixel stride and a channel offset, the filter rows of a group are contiguous in
         the [Cout][kh][kw][Cin / G] image, and BatchNorm is per channel, so a group's statistics, coefficients and
         parameter gradients are slices too.  Slices are addressed in 16-byte chunks: Cin / G and Cout / G must be
         multiples of 8 (bf16) / 4 (f32); depthwise convolutions are outside the Darknet / VoVNet path."""
-        import types
-
         G = conv.groups
         Cin, Cout = conv.in_channels, conv.out_channels
         ci, co = Cin // G, Cout // G
         epc = _EPC[self.dtype]
-        if getattr(x, "logical_C", x.C) != Cin or x.C != Cin:
-            raise ValueError(f"conv expects {Cin} (unpadded) input channels, got {getattr(x, 'logical_C', x.C)}")
+        if x.logical_c != Cin or x.C != Cin:
+            raise ValueError(f"conv expects {Cin} (unpadded) input channels, got {x.logical_c}")
         if ci == 1 and co == 1 and Cin % epc == 0:
-            return self._depthwise_unit(x, conv, norm, relu, residual, out, name, pool_out)
+            return self._depthwise_unit(x, conv, bn, relu, residual, out, name, pool_out)
         if ci % epc or co % epc:
             raise NotImplementedError(
                 f"groups={G} with {ci} -> {co} channels per group: channel slices are addressed in 16-byte chunks "
                 f"({epc} elements); narrow groups other than depthwise (groups = in_channels = out_channels) are outside the "
                 "hot path")
-        k, s, pad, dil = conv.kernel_size[0], conv.stride[0], conv.padding[0], conv.dilation[0]
-        Ho = (x.H + 2 * pad - dil * (k - 1) - 1) // s + 1
-        Wo = (x.W + 2 * pad - dil * (k - 1) - 1) // s + 1
+        Ho, Wo = conv.out_size(x.H, x.W)
         y = out if out is not None else self.act(x.B, Ho, Wo, Cout, name + ".y")
         assert (y.B, y.H, y.W, y.C) == (x.B, Ho, Wo, Cout), "out geometry mismatch"
-        has_bn = isinstance(norm, nn.BatchNorm2d)
-        wn = co * k * k * ci
         for g in range(G):
-            cg = types.SimpleNamespace(
-                kernel_size=conv.kernel_size, stride=conv.stride, padding=conv.padding, dilation=conv.dilation, groups=1,
-                in_channels=ci, out_channels=co, weight=_PSlice(conv.weight, g * wn, wn),
-                bias=_PSlice(conv.bias, g * co, co) if conv.bias is not None else None, _vt_slice=True)
-            ng = norm
-            if has_bn:
-                ng = types.SimpleNamespace(
-                    weight=_PSlice(norm.weight, g * co, co), bias=_PSlice(norm.bias, g * co, co),
-                    running_mean=_PSlice(norm.running_mean, g * co, co), running_var=_PSlice(norm.running_var, g * co, co),
-                    # (the batch counter belongs to the module, not to a group: the first group's finalize advances it)
-                    num_batches_tracked=norm.num_batches_tracked if g == 0 else None,
-                    eps=norm.eps, momentum=norm.momentum, affine=norm.affine, track_running_stats=norm.track_running_stats,
-                    training=norm.training, _vt_bn=True)
-            self.conv_unit(x.sl(g * ci, ci), cg, ng, relu,
+            self.conv_unit(x.sl(g * ci, ci), conv.group(g), bn.group(g, G) if bn is not None else None, relu,
                            residual=residual.sl(g * co, co) if residual is not None else None,
                            out=y.sl(g * co, co), name=f"{name}.g{g}")
         if pool_out is not None:
             self.maxpool3x3s2(y, out=pool_out, name=name + ".max_pool")
         return y
 
-    def _depthwise_unit(self, x: TRef, conv, norm, relu, residual, out, name, pool_out) -> TRef:
+    def _depthwise_unit(self, x: TRef, conv: "ConvSpec", bn_spec: "Optional[BNSpec]", relu, residual, out, name,
+                        pool_out) -> TRef:
         """nn.Conv2d(C, C, k, groups=C) inside a ConvNormAct (reference components.py:26-44 with `groups = in_channels`):
         vt_dwconv_fwd (+ batch statistics) -> the ordinary BatchNorm finalize / normalise passes; backward: the ordinary
         BatchNorm backward -> vt_dwconv_wgrad (side stream) and vt_dwconv_dgrad.  Streaming kernels (round 6): off the
         Darknet / VoVNet path, present so that every `groups` the constructor accepts runs on the GPU."""
-        Cc = conv.in_channels
-        k, s, pad, dil = conv.kernel_size[0], conv.stride[0], conv.padding[0], conv.dilation[0]
-        B = x.B
-        Ho = (x.H + 2 * pad - dil * (k - 1) - 1) // s + 1
-        Wo = (x.W + 2 * pad - dil * (k - 1) - 1) // s + 1
+        Cc, B = conv.in_channels, x.B
+        Ho, Wo = conv.out_size(x.H, x.W)
         M, dt = B * Ho * Wo, self.dtype
         if self.deterministic:
             raise NotImplementedError("depthwise filter gradients use f32 atomics: not available in deterministic mode")
         y = out if out is not None else self.act(B, Ho, Wo, Cc, name + ".y")
         assert (y.B, y.H, y.W, y.C) == (B, Ho, Wo, Cc), "out geometry mismatch"
-        has_bn = isinstance(norm, nn.BatchNorm2d)
-        # (the unit follows ITS BatchNorm's flag, as conv_unit does)
-        training = bool(norm.training) if has_bn else self.training
-        track = self.need_grad
         self.tag += 1
         self.n_units += 1
-        w = conv.weight
+        w, bias = conv.weight, conv.bias
         wptr = self.pref(w)  # the f32 master [C][k*k] (the kernels round it for bf16 launches)
-        geo = [B, x.H, x.W, Cc, k, s, pad, dil, dt]
-        z = self.act(B, Ho, Wo, Cc, name + ".z") if (has_bn or relu) else y
-        cp = None
-        if has_bn:
-            coef = self.f32(4 * Cc, "bncoef")
-            cp = [self.bp(coef, i * Cc * 4) for i in range(4)]
-            g, b_, rm, rv = (self.pref(norm.weight), self.pref(norm.bias), self.pref(norm.running_mean),
-                             self.pref(norm.running_var))
-            nbt = self.pref(norm.num_batches_tracked) if norm.num_batches_tracked is not None else None
-            if training:
-                stats = self.zeroed_f32(N.stat_floats(Cc), "stats")
-                self.emit(N.OP_DWCONV_FWD, [x.addr(), wptr, z.addr(), self.bp(stats)], [x.ld, z.ld, 0] + geo)
-                self.emit(N.OP_BN_FINALIZE, [self.bp(stats), g, b_, rm, rv, nbt, *cp], [Cc],
-                          [M * self.bn_world, norm.eps, norm.momentum])
+        geo = [B, x.H, x.W, Cc, conv.k, conv.stride, conv.padding, conv.dilation, dt]
+        z = self.act(B, Ho, Wo, Cc, name + ".z") if (bn_spec is not None or relu) else y
+        # (the unit follows ITS BatchNorm's flag, as conv_unit does)
+        bn = _BNEmitter(self, bn_spec, Cc) if bn_spec is not None else None
+        stats = self.zeroed_f32(N.stat_floats(Cc), "stats") if (bn is not None and bn_spec.training) else None
+        self.emit(N.OP_DWCONV_FWD, [x.addr(), wptr, z.addr(), self.bp(stats) if stats is not None else None],
+                  [x.ld, z.ld, 0] + geo)
+        if bn is not None:
+            if stats is not None:
+                bn.finalize(stats, M)
             else:
-                self.emit(N.OP_DWCONV_FWD, [x.addr(), wptr, z.addr(), None], [x.ld, z.ld, 0] + geo)
-                self.emit(N.OP_BN_EVAL_COEFFS, [g, b_, rm, rv, *cp], [Cc], [norm.eps])
-            self.emit(N.OP_BN_ACT_APPLY, [z.addr(), cp[0], cp[1], residual.addr() if residual else None, y.addr()],
-                      [z.ld, residual.ld if residual else 0, y.ld, Cc, int(relu), dt], [M])
-        else:
-            self.emit(N.OP_DWCONV_FWD, [x.addr(), wptr, z.addr(), None], [x.ld, z.ld, 0] + geo)
-            bias = self.pref(conv.bias) if conv.bias is not None else None
-            if z is not y or bias is not None or residual is not None:
-                # (biased conv -> activation: the unit-scale form of the normalise pass, shift = the bias)
-                self.emit(N.OP_BN_ACT_APPLY, [z.addr(), None, bias, residual.addr() if residual else None, y.addr()],
-                          [z.ld, residual.ld if residual else 0, y.ld, Cc, int(relu), dt], [M])
+                bn.eval_coeffs()
+            self._act_apply(z, bn.cp[0], bn.cp[1], residual, y, relu)
+        elif z is not y or bias is not None or residual is not None:
+            # (biased conv -> activation: the unit-scale form of the normalise pass, shift = the bias)
+            self._act_apply(z, None, self.pref(bias), residual, y, relu)
         if pool_out is not None:
             self.maxpool3x3s2(y, out=pool_out, name=name + ".max_pool")
-        if track:
-            tag = self.tag
+        if self.need_grad:
 
-            def bwd():
-                self.tag = tag
-                dy = self.grad_read(y)
-                if dy is None:
-                    return
-                if residual is not None:
-                    self.grad_add(residual, dy)
-                if has_bn:
-                    sums = self.zeroed_f32(N.stat_floats(Cc), "bwdsums")
-                    self.emit(N.OP_BN_BWD_REDUCE, [dy.addr(), z.addr(), cp[0], cp[1], cp[2], cp[3], self.bp(sums)],
-                              [dy.ld, z.ld, Cc, int(relu), dt], [M])
-                    bcoef = self.f32(3 * Cc, "bwdcoef")
-                    self.emit(N.OP_BN_BWD_FINALIZE,
-                              [self.bp(sums), cp[0], cp[2], cp[3], self.pgrad(norm.weight), self.pgrad(norm.bias), self.bp(bcoef)],
-                              [Cc, int(training)], [M * self.bn_world, 1.0 / self.bn_world])
-                    dz = self.act(B, Ho, Wo, Cc, name + ".dz")
-                    self.emit(N.OP_BN_BWD_APPLY, [dy.addr(), z.addr(), cp[0], cp[1], self.bp(bcoef), dz.addr()],
-                              [dy.ld, z.ld, dz.ld, Cc, int(relu), dt], [M])
+            def bwd(dy):
+                self.grad_add(residual, dy)
+                if bn is not None:
+                    sums, bcoef, dz = bn.bwd_buffers(y, name + ".dz")
+                    bn.bwd_three_launches(dy, z, relu, sums, bcoef, dz)
                 else:
                     dz = dy
                     if relu:  # dz = dy * act'(z + bias): the coefficient-free form reads the pre-activation it is given
                         zb = z
-                        if conv.bias is not None:  # act' is taken at z + bias: form it once
+                        if bias is not None:  # act' is taken at z + bias: form it once
                             zb = self.act(B, Ho, Wo, Cc, name + ".zb")
-                            self.emit(N.OP_BN_ACT_APPLY, [z.addr(), None, self.pref(conv.bias), None, zb.addr()],
-                                      [z.ld, 0, zb.ld, Cc, 0, dt], [M])
+                            self._act_apply(z, None, self.pref(bias), None, zb, 0)
                         dz = self.act(B, Ho, Wo, Cc, name + ".dz")
-                        self.emit(N.OP_BN_BWD_APPLY, [dy.addr(), zb.addr(), None, None, None, dz.addr()],
-                                  [dy.ld, zb.ld, dz.ld, Cc, int(relu), dt], [M])
-                    if conv.bias is not None and conv.bias.requires_grad:
-                        self.emit(N.OP_COLSUM, [dz.addr(), self.pgrad(conv.bias)], [dz.ld, Cc, dt], [M])
+                        self._act_bwd(dy, zb, None, None, None, dz, relu)
+                    if bias is not None and bias.requires_grad:
+                        self.emit(N.OP_COLSUM, [dz.addr(), self.pgrad(bias)], [dz.ld, Cc, dt], [M])
                 if w.requires_grad:
                     self.emit(N.OP_FORK)
                     self.emit(N.OP_DWCONV_WGRAD, [x.addr(), dz.addr(), self.pgrad(w)], [x.ld, dz.ld, 0] + geo, side=True)
                 if x.needs_grad:
                     gx, res = self.grad_target(x)
-                    self.emit(N.OP_DWCONV_DGRAD, [dz.addr(), wptr, gx.addr(), res.addr() if res is not None else None],
-                              [dz.ld, gx.ld, res.ld if res is not None else 0] + geo)
+                    self.emit(N.OP_DWCONV_DGRAD, [dz.addr(), wptr, gx.addr(), _addr(res)], [dz.ld, gx.ld, _ld(res)] + geo)
                     self.grad_written(x)
 
-            self.nodes.append(bwd)
+            self._node(y, bwd)
         return y
 
     # -- pointwise (1x1) units without stored pre-activations (vt_pointwise.hip) ------------------------------------
+    def _unit_specs(self, specs) -> list:
+        """(conv, norm, relu, residual, out, name) per unit, conv and norm as specs"""
+        return [(*self._specs(sp[0], sp[1]), *sp[2:]) for sp in specs]
+
     def _pw_ok(self, x: TRef, specs) -> int:
         """0: the pointwise kernels do not apply to these units (reading the same x); 2: they do, filter gradient
         included; 1: they do, with dz handed to the filter-gradient kernel (vt_pw_supported)."""
         if not self.pointwise or self.dtype != N.VT_BF16 or not (1 <= len(specs) <= 2):
             return 0
+        specs = self._unit_specs(specs)
         flags = set()
-        for conv, norm, relu, residual, out, _ in specs:
-            if getattr(conv, "_vt_slice", False):  # (one group of a grouped convolution: parameter slices)
+        for conv, bn, relu, residual, out, _ in specs:
+            # (a slice: one group of a grouped convolution; LeakyReLU / SiLU / GELU: the unfused BatchNorm passes only)
+            if (conv.is_slice or (conv.k, conv.stride, conv.padding, conv.dilation, conv.groups) != (1, 1, 0, 1, 1) or
+                    conv.bias is not None or bn is None or conv.in_channels != x.C or x.logical_c != x.C or int(relu) >= 2):
                 return 0
-            if (conv.kernel_size != (1, 1) or conv.stride != (1, 1) or conv.padding != (0, 0) or conv.dilation != (1, 1)
-                    or conv.groups != 1 or conv.bias is not None or not isinstance(norm, nn.BatchNorm2d)
-                    or norm.momentum is None or not norm.affine or not norm.track_running_stats):
-                return 0
-            if conv.in_channels != x.C or getattr(x, "logical_C", x.C) != x.C:
-                return 0
-            if int(relu) >= 2:
-                return 0  # (LeakyReLU / SiLU / GELU: the unfused BatchNorm passes only)
-            flags.add((bool(norm.training), bool(relu)))
+            flags.add((bn.training, bool(relu)))
         if len(flags) != 1 or len({sp[3] is None for sp in specs}) != 1:  # (a residual for every group or for none)
             return 0
         unit_training, _ = next(iter(flags))
@@ -1095,27 +1220,25 @@ class Builder:
         """one or two 1x1 ConvNormAct units reading the same tensor x (components.py:26-44; two: CSPDarknetStage's
         conv1 | conv2, darknet.py:46-47,53) as ONE launch per pass: statistics, normalise, backward reduction, backward
         apply with the data gradient and (small shapes) the filter gradient.  z and dz are never stored."""
+        specs = self._unit_specs(specs)
         mode = self._pw_ok(x, specs)
         assert mode in (1, 2)
         self.tag += 1
         self.n_units += len(specs)
-        dt = self.dtype
-        G = len(specs)
-        Cs = [sp[0].out_channels for sp in specs]
+        G, Cs = len(specs), [sp[0].out_channels for sp in specs]
         Ntot, K, M = sum(Cs), x.C, x.M
         offs = [0, Cs[0]][:G]
         relu = bool(specs[0][2])
-        unit_training = bool(specs[0][1].training)
-        convs, norms = [sp[0] for sp in specs], [sp[1] for sp in specs]
+        unit_training = specs[0][1].training
+        convs = [sp[0] for sp in specs]
         ys = []
-        for (conv, norm, _, residual, out, name), c in zip(specs, Cs):
-            if out is not None:
-                assert (out.B, out.H, out.W, out.C) == (x.B, x.H, x.W, c), "out geometry mismatch"
-            if residual is not None:
-                assert (residual.B, residual.H, residual.W, residual.C) == (x.B, x.H, x.W, c)
+        for (conv, _, _, residual, out, name), c in zip(specs, Cs):
+            assert out is None or (out.B, out.H, out.W, out.C) == (x.B, x.H, x.W, c), "out geometry mismatch"
+            assert residual is None or (residual.B, residual.H, residual.W, residual.C) == (x.B, x.H, x.W, c)
             ys.append(out if out is not None else self.act(x.B, x.H, x.W, c, name + ".y"))
         coef = self.f32(4 * Ntot, "bncoef4")  # scale | shift | mean | invstd over all groups' channels
-        cps = [[self.bp(coef, (i * Ntot + o) * 4) for i in range(4)] for o in offs]
+        bns = [_BNEmitter(self, sp[1], c, cp=[self.bp(coef, (i * Ntot + o) * 4) for i in range(4)])
+               for sp, c, o in zip(specs, Cs, offs)]
         wps = [self.pref(c.weight, mirror=True) for c in convs]
         pad2 = lambda v, fill=None: list(v) + [fill] * (2 - len(v))
         head_i = [K, G, int(relu)] + pad2(Cs, 0) + [x.ld] + pad2([K] * G, 0)
@@ -1125,32 +1248,22 @@ class Builder:
         if unit_training:
             stats = [self.zeroed_f32(N.stat_floats(c), "stats") for c in Cs]
             self.emit(N.OP_PW_STATS, [x.addr(), *pad2(wps), *pad2([self.bp(s_) for s_ in stats])], head_i, [M])
-            for g, norm in enumerate(norms):
+            for bn, st in zip(bns, stats):
                 if pw_fin:
-                    fin_p += [self.bp(stats[g]), self.pref(norm.weight), self.pref(norm.bias), self.pref(norm.running_mean),
-                              self.pref(norm.running_var), self.pref(norm.num_batches_tracked)]
-                    continue
-                self.emit(N.OP_BN_FINALIZE,
-                          [self.bp(stats[g]), self.pref(norm.weight), self.pref(norm.bias), self.pref(norm.running_mean),
-                           self.pref(norm.running_var), self.pref(norm.num_batches_tracked), *cps[g]],
-                          [Cs[g]], [M * self.bn_world, norm.eps, norm.momentum])
+                    fin_p += [self.bp(st), *bn.params, bn.nbt]
+                else:
+                    bn.finalize(st, M)
         else:
-            for g, norm in enumerate(norms):
-                self.emit(N.OP_BN_EVAL_COEFFS, [self.pref(norm.weight), self.pref(norm.bias), self.pref(norm.running_mean),
-                                                self.pref(norm.running_var), *cps[g]], [Cs[g]], [norm.eps])
+            for bn in bns:
+                bn.eval_coeffs()
         ress = [sp[3] for sp in specs]
+        apply_p = [x.addr(), *pad2(wps), self.bp(coef), *pad2([y.addr() for y in ys]), *pad2([_addr(r) for r in ress])]
+        apply_i = head_i + pad2([y.ld for y in ys], 0) + pad2([_ld(r) for r in ress], 0)
         if fin_p:
-            epsmom = [v for norm in norms for v in (norm.eps, norm.momentum)]
-            self.emit(N.OP_PW_APPLY_FIN,
-                      [x.addr(), *pad2(wps), self.bp(coef), *pad2([y.addr() for y in ys]),
-                       *pad2([r.addr() if r is not None else None for r in ress]), *fin_p],
-                      head_i + pad2([y.ld for y in ys], 0) + pad2([r.ld if r is not None else 0 for r in ress], 0),
-                      [M, M * self.bn_world] + epsmom)
+            epsmom = [v for bn in bns for v in (bn.spec.eps, bn.spec.momentum)]
+            self.emit(N.OP_PW_APPLY_FIN, apply_p + fin_p, apply_i, [M, M * self.bn_world] + epsmom)
         else:
-            self.emit(N.OP_PW_APPLY,
-                      [x.addr(), *pad2(wps), self.bp(coef), *pad2([y.addr() for y in ys]),
-                       *pad2([r.addr() if r is not None else None for r in ress])],
-                      head_i + pad2([y.ld for y in ys], 0) + pad2([r.ld if r is not None else 0 for r in ress], 0), [M])
+            self.emit(N.OP_PW_APPLY, apply_p, apply_i, [M])
         if self.need_grad:
             tag = self.tag
 
@@ -1172,13 +1285,11 @@ class Builder:
                           head_i + dy_ld, [M])
                 bcoefs = [self.f32(3 * c, "bwdcoef") for c in Cs]
                 bfin_p = []
-                for g, norm in enumerate(norms):
+                for bn, sm, bc in zip(bns, sums, bcoefs):
                     if pw_fin:
-                        bfin_p += [self.bp(sums[g]), self.pgrad(norm.weight), self.pgrad(norm.bias)]
-                        continue
-                    self.emit(N.OP_BN_BWD_FINALIZE,
-                              [self.bp(sums[g]), cps[g][0], cps[g][2], cps[g][3], self.pgrad(norm.weight), self.pgrad(norm.bias),
-                               self.bp(bcoefs[g])], [Cs[g], int(unit_training)], [M * self.bn_world, 1.0 / self.bn_world])
+                        bfin_p += [self.bp(sm), *bn.grads()]
+                    else:
+                        bn.bwd_finalize(sm, bc, M)
                 gx, res = self.grad_target(x)
                 want_dw = [c.weight.requires_grad for c in convs]
                 dws = [self.pgrad(c.weight) if (mode == 2 and w_) else None for c, w_ in zip(convs, want_dw)]
@@ -1186,10 +1297,9 @@ class Builder:
                        for c, sp, w_ in zip(Cs, specs, want_dw)]
                 self.emit(N.OP_PW_BWD_FIN if bfin_p else N.OP_PW_BWD,
                           [x.addr(), *pad2(wps), self.bp(coef), *dy_p, *pad2([self.bp(b_) for b_ in bcoefs]), gx.addr(),
-                           res.addr() if res is not None else None, *pad2(dws),
-                           *pad2([d.addr() if d is not None else None for d in dzs]), *bfin_p],
-                          head_i + dy_ld + [gx.ld, res.ld if res is not None else 0] + pad2([K] * G, 0) +
-                          pad2([d.ld if d is not None else 0 for d in dzs], 0) + [int(unit_training)],
+                           _addr(res), *pad2(dws), *pad2([_addr(d) for d in dzs]), *bfin_p],
+                          head_i + dy_ld + [gx.ld, _ld(res)] + pad2([K] * G, 0) + pad2([_ld(d) for d in dzs], 0) +
+                          [int(unit_training)],
                           [M, M * self.bn_world, 1.0 / self.bn_world])
                 self.grad_written(x)
                 if mode == 1 and any(d is not None for d in dzs):
@@ -1208,15 +1318,11 @@ class Builder:
     def conv_unit_pair(self, x: TRef, a, b):
         """two ConvNormAct units that read the same tensor (CSPDarknetStage.conv1 / conv2): one pointwise launch per
         pass when the kernels cover the joint shape, else two independent units.  a, b = (ConvNormAct, out, name)."""
-        def spec(t):
-            m, out, name = t
-            norm = m.norm if isinstance(m.norm, nn.BatchNorm2d) else None
-            return (m.conv, norm, m._vt_relu(), None, out, name)
-
-        sa, sb = spec(a), spec(b)
-        if sa[1] is not None and sb[1] is not None and self._pw_ok(x, [sa, sb]):
-            return self.pw_units(x, [sa, sb])
-        return [a[0]._vt_emit(self, x, out=a[1], name=a[2]), b[0]._vt_emit(self, x, out=b[1], name=b[2])]
+        specs = [(m.conv, m.norm if isinstance(m.norm, nn.BatchNorm2d) else None, m._vt_relu(), None, out, name)
+                 for m, out, name in (a, b)]
+        if self._pw_ok(x, specs):  # (0 where either unit has no BatchNorm)
+            return self.pw_units(x, specs)
+        return [m._vt_emit(self, x, out=out, name=name) for m, out, name in (a, b)]
 
     def _wgrad_hold(self, key, xa, dza, dwa, desc, ldw):
         """hold a filter gradient back until its shape group is complete (or wgrad_group of them wait), then release the
@@ -1238,8 +1344,33 @@ class Builder:
             for xa, dza, dwa, desc, ldw in pend:
                 self.emit(N.OP_CONV_WGRAD, [xa, dza, dwa, None], desc=desc, extra_ints=[ldw, 0], side=side)
 
-    def _dgrad(self, x: TRef, dz: TRef, wptr, w_dtype, ldw, Cout, k, s, pad, Ho, Wo, dil=1):
-        dt = self.dtype
+    def _pack_dgrad(self, wptr, dst, ints):
+        """a filter repacked for a data-gradient launch; on the forward list's side stream where the trainer asks for it
+        (hoist_dgrad_packs)"""
+        keep, hoist = self._cur, self.hoist_dgrad_packs
+        self._cur = self._hoisted if hoist else keep
+        self.emit(N.OP_PACK_DGRAD, [wptr, dst], ints, side=hoist)
+        self._cur = keep
+
+    def _dgrad_launch(self, dz: TRef, wd: Buf, gx: TRef, res: Optional[TRef], grid, cols, step, origin, taps, flags=0):
+        """a stride-1 convolution over dz (tap offsets `taps`, `cols` output columns, `grid` output positions) written to the
+        pixels origin + step * position of d(x)"""
+        d = N.ConvDesc()
+        d.dtype = self.dtype
+        d.B, d.Hi, d.Wi, d.Cin, d.ldx = dz.B, dz.H, dz.W, dz.C, dz.ld
+        d.Ho, d.Wo, d.sh, d.sw, d.h0, d.w0 = grid[0], grid[1], 1, 1, 0, 0
+        d.Cout, d.ldy, d.oH, d.oW = cols, gx.ld, gx.H, gx.W
+        d.oHs, d.oWs, d.oh0, d.ow0 = step, step, origin[0], origin[1]
+        d.ldw, d.ldr = len(taps) * dz.C, _ld(res)
+        d.flags = flags | (N.VT_CONV_RESIDUAL if res is not None else 0)
+        d.ntaps = len(taps)
+        for i, (a, b) in enumerate(taps):
+            d.dh[i], d.dw[i] = a, b
+        return self.emit(N.OP_CONV_IGEMM, [dz.addr(), self.bp(wd), gx.addr(), None, None, _addr(res), None], desc=d)
+
+    def _dgrad(self, x: TRef, dz: TRef, wptr, ldw, conv: ConvSpec):
+        dt, Cout = self.dtype, dz.C
+        k, s, pad, dil = conv.k, conv.stride, conv.padding, conv.dilation
         # the s*s parity classes tile d(x) disjointly, so they share one destination and
         # one folded addend: every pixel is produced exactly once
         gx, res = self.grad_target(x)
@@ -1260,27 +1391,9 @@ class Builder:
                     for (a, b) in taps:  # class tap (u, v) sits at offset (eh - u, ew - v)
                         u, v = eh - a, ew - b
                         sel.append(rows[u] * k + cols[v] if 0 <= u < len(rows) and 0 <= v < len(cols) else -1)
-                    ints = [w_dtype, ldw, dt, 4, Cout, k * k, x.C, 0] + sel
-                    dst = self.bp(wd, (2 * ph + pw) * x.C * 4 * Cout * _ESIZE[dt])
-                    if self.hoist_dgrad_packs:
-                        keep, self._cur = self._cur, self._hoisted
-                        self.emit(N.OP_PACK_DGRAD, [wptr, dst], ints, side=True)
-                        self._cur = keep
-                    else:
-                        self.emit(N.OP_PACK_DGRAD, [wptr, dst], ints)
-            d = N.ConvDesc()
-            d.dtype = dt
-            d.B, d.Hi, d.Wi, d.Cin, d.ldx = dz.B, Ho, Wo, Cout, dz.ld
-            d.Ho, d.Wo, d.sh, d.sw, d.h0, d.w0 = x.H // 2, x.W // 2, 1, 1, 0, 0
-            d.Cout, d.ldy, d.oH, d.oW = 4 * x.C, gx.ld, x.H, x.W
-            d.oHs, d.oWs, d.oh0, d.ow0 = 2, 2, 0, 0
-            d.ldw, d.ldr = 4 * Cout, (res.ld if res is not None else 0)
-            d.flags = N.VT_CONV_D2S | (N.VT_CONV_RESIDUAL if res is not None else 0)
-            d.ntaps = 4
-            for i, (a, b) in enumerate(taps):
-                d.dh[i], d.dw[i] = a, b
-            self.emit(N.OP_CONV_IGEMM, [dz.addr(), self.bp(wd), gx.addr(), None, None,
-                                        res.addr() if res is not None else None, None], desc=d)
+                    self._pack_dgrad(wptr, self.bp(wd, (2 * ph + pw) * x.C * 4 * Cout * _ESIZE[dt]),
+                                     [dt, ldw, dt, 4, Cout, k * k, x.C, 0] + sel)
+            self._dgrad_launch(dz, wd, gx, res, (x.H // 2, x.W // 2), 4 * x.C, 2, (0, 0), taps, N.VT_CONV_D2S)
             self.grad_written(x)
             return
         # A dilated strided convolution may never read some parity classes of its input (s = 2, dilation 2: the rows
@@ -1302,34 +1415,13 @@ class Builder:
                 cols = [t for t in range(k) if (pw + pad - t * dil) % s == 0]
                 Hc = (x.H - ph + s - 1) // s
                 Wc = (x.W - pw + s - 1) // s
-                if Hc <= 0 or Wc <= 0:
+                if Hc <= 0 or Wc <= 0 or not rows or not cols:  # (no rows / columns: initialised above)
                     continue
-                if not rows or not cols:
-                    continue  # (initialised above)
                 sel = [r * k + t for r in rows for t in cols]
                 offs = [((ph + pad - r * dil) // s, (pw + pad - t * dil) // s) for r in rows for t in cols]
-                nsel = len(sel)
-                wd = self.alloc(x.C * nsel * Cout * _ESIZE[dt], "wd")
-                ints = [w_dtype, ldw, dt, nsel, Cout, k * k, x.C, 0] + sel
-                if self.hoist_dgrad_packs:
-                    keep, self._cur = self._cur, self._hoisted
-                    self.emit(N.OP_PACK_DGRAD, [wptr, self.bp(wd)], ints, side=True)
-                    self._cur = keep
-                else:
-                    self.emit(N.OP_PACK_DGRAD, [wptr, self.bp(wd)], ints)
-                d = N.ConvDesc()
-                d.dtype = dt
-                d.B, d.Hi, d.Wi, d.Cin, d.ldx = dz.B, Ho, Wo, Cout, dz.ld
-                d.Ho, d.Wo, d.sh, d.sw, d.h0, d.w0 = Hc, Wc, 1, 1, 0, 0
-                d.Cout, d.ldy, d.oH, d.oW = x.C, gx.ld, x.H, x.W
-                d.oHs, d.oWs, d.oh0, d.ow0 = s, s, ph, pw
-                d.ldw, d.ldr = nsel * Cout, (res.ld if res is not None else 0)
-                d.flags = N.VT_CONV_RESIDUAL if res is not None else 0
-                d.ntaps = nsel
-                for i, (a, b) in enumerate(offs):
-                    d.dh[i], d.dw[i] = a, b
-                op = self.emit(N.OP_CONV_IGEMM, [dz.addr(), self.bp(wd), gx.addr(), None, None,
-                                                 res.addr() if res is not None else None, None], desc=d)
+                wd = self.alloc(x.C * len(sel) * Cout * _ESIZE[dt], "wd")
+                self._pack_dgrad(wptr, self.bp(wd), [dt, ldw, dt, len(sel), Cout, k * k, x.C, 0] + sel)
+                op = self._dgrad_launch(dz, wd, gx, res, (Hc, Wc), x.C, s, (ph, pw), offs)
                 if s == 1 and res is None and Hc == x.H and Wc == x.W and self._cur is self.bwd:
                     self._last_dgrad[id(gx.buf)] = (op, gx.coff, gx.coff + gx.C)  # this launch alone forms d(x)
         self.grad_written(x)
@@ -1379,33 +1471,19 @@ class Builder:
             assert (other.B, other.H, other.W, other.C) == (src.B, Hd, Wd, src.C), "fuse operands differ in shape"
         y = out if out is not None else self.act(src.B, Hd, Wd, src.C, name)
         assert (y.B, y.H, y.W, y.C) == (src.B, Hd, Wd, src.C)
-        self.emit(N.OP_RESAMPLE_FWD, [src.addr(), other.addr() if other is not None else None, y.addr()],
-                  [src.ld, other.ld if other is not None else 0, y.ld, src.B, Hd, Wd, src.C, mode, self.dtype])
+        self.emit(N.OP_RESAMPLE_FWD, [src.addr(), _addr(other), y.addr()],
+                  [src.ld, _ld(other), y.ld, src.B, Hd, Wd, src.C, mode, self.dtype])
         if self.need_grad and (src.needs_grad or (other is not None and other.needs_grad)):
-            tag = self.tag
 
-            def bwd():
-                self.tag = tag
-                dy = self.grad_read(y)
-                if dy is None:
-                    return
-                if other is not None:
-                    self.grad_add(other, dy)
+            def bwd(dy):
+                self.grad_add(other, dy)
                 if not src.needs_grad:
                     return
-                gx, res = self.grad_target(src)
-                acc = 0
-                if res is not None:
-                    if res is gx or (res.buf is gx.buf and res.coff == gx.coff):
-                        acc = 1
-                    else:  # a foreign addend: materialise it first, then accumulate
-                        self._add_into(gx, res, False)
-                        acc = 1
-                self.emit(N.OP_RESAMPLE_BWD, [dy.addr(), gx.addr()],
-                          [dy.ld, gx.ld, src.B, Hd, Wd, src.C, mode, acc, self.dtype])
+                gx, acc = self.grad_accum_target(src)
+                self.emit(N.OP_RESAMPLE_BWD, [dy.addr(), gx.addr()], [dy.ld, gx.ld, src.B, Hd, Wd, src.C, mode, acc, self.dtype])
                 self.grad_written(src)
 
-            self.nodes.append(bwd)
+            self._node(y, bwd)
         return y
 
     def maxpool3x3s2(self, x: TRef, out: Optional[TRef] = None, name="maxpool") -> TRef:
@@ -1414,29 +1492,16 @@ class Builder:
         y = out if out is not None else self.act(x.B, Ho, Wo, x.C, name)
         assert (y.B, y.H, y.W, y.C) == (x.B, Ho, Wo, x.C)
         am = self.alloc(x.B * Ho * Wo * x.C, "argmax")
-        self.emit(N.OP_MAXPOOL_FWD, [x.addr(), y.addr(), self.bp(am)],
-                  [x.ld, y.ld, x.B, x.H, x.W, x.C, self.dtype])
+        self.emit(N.OP_MAXPOOL_FWD, [x.addr(), y.addr(), self.bp(am)], [x.ld, y.ld, x.B, x.H, x.W, x.C, self.dtype])
         if self.need_grad and x.needs_grad:
-            tag = self.tag
 
-            def bwd():
-                self.tag = tag
-                dy = self.grad_read(y)
-                if dy is None:
-                    return
-                gx, res = self.grad_target(x)
-                acc = 0
-                if res is not None:
-                    if res is gx or (res.buf is gx.buf and res.coff == gx.coff):
-                        acc = 1
-                    else:  # a foreign addend: materialise it first, then accumulate
-                        self._add_into(gx, res, False)
-                        acc = 1
+            def bwd(dy):
+                gx, acc = self.grad_accum_target(x)
                 self.emit(N.OP_MAXPOOL_BWD, [dy.addr(), self.bp(am), gx.addr()],
                           [dy.ld, gx.ld, x.B, x.H, x.W, x.C, acc, self.dtype])
                 self.grad_written(x)
 
-            self.nodes.append(bwd)
+            self._node(y, bwd)
         return y
 
     def global_avgpool(self, x: TRef, name="avgpool") -> TRef:
@@ -1445,47 +1510,26 @@ class Builder:
         y = self.act(x.B, 1, 1, x.C, name)
         self.emit(N.OP_AVGPOOL_FWD, [x.addr(), y.addr()], [x.ld, y.ld, x.B, x.H * x.W, x.C, self.dtype])
         if self.need_grad and x.needs_grad:
-            tag = self.tag
 
-            def bwd():
-                self.tag = tag
-                dy = self.grad_read(y)
-                if dy is None:
-                    return
-                gx, res = self.grad_target(x)
-                acc = 0
-                if res is not None:
-                    if not (res.buf is gx.buf and res.coff == gx.coff):
-                        self._add_into(gx, res, False)
-                    acc = 1
-                self.emit(N.OP_AVGPOOL_BWD, [dy.addr(), gx.addr()],
-                          [dy.ld, gx.ld, x.B, x.H * x.W, x.C, acc, self.dtype])
+            def bwd(dy):
+                gx, acc = self.grad_accum_target(x)
+                self.emit(N.OP_AVGPOOL_BWD, [dy.addr(), gx.addr()], [dy.ld, gx.ld, x.B, x.H * x.W, x.C, acc, self.dtype])
                 self.grad_written(x)
 
-            self.nodes.append(bwd)
+            self._node(y, bwd)
         return y
 
     # -- ConvNeXt pieces (reference backbones/convnext.py:44-58): vt_layernorm.hip ----------------------
     def linear_unit(self, x: TRef, linear: nn.Linear, act: int = 0, name: str = "linear") -> TRef:
         """nn.Linear over the channel axis of an NHWC map = a biased 1x1 convolution (+ activation code `act`)."""
-        import types
-
-        conv = types.SimpleNamespace(
-            kernel_size=(1, 1), stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1, in_channels=linear.in_features,
-            out_channels=linear.out_features, weight=linear.weight, bias=linear.bias)
-        return self.conv_unit(x, conv, None, act, name=name)
+        return self.conv_unit(x, ConvSpec.from_linear(linear), None, act, name=name)
 
     def depthwise_no_bias(self, x: TRef, conv: nn.Conv2d, name: str = "dwconv") -> TRef:
         """a depthwise nn.Conv2d emitted WITHOUT its bias: the LayerNorm behind it adds the bias while it reads the row
         (layer_norm(pre_bias=conv.bias)) instead of one more read + write pass over the map."""
-        import types
-
         if conv.groups != conv.in_channels or conv.in_channels != conv.out_channels:
             raise NotImplementedError("depthwise_no_bias: groups = in_channels = out_channels")
-        ns = types.SimpleNamespace(
-            kernel_size=conv.kernel_size, stride=conv.stride, padding=conv.padding, dilation=conv.dilation, groups=conv.groups,
-            in_channels=conv.in_channels, out_channels=conv.out_channels, weight=conv.weight, bias=None)
-        return self.conv_unit(x, ns, None, 0, name=name)
+        return self.conv_unit(x, ConvSpec.from_conv(conv).without_bias(), None, 0, name=name)
 
     def layer_norm(self, x: TRef, ln: nn.LayerNorm, pre_bias: Optional[nn.Parameter] = None, out: Optional[TRef] = None,
                    name: str = "ln") -> TRef:
@@ -1494,7 +1538,7 @@ class Builder:
         buffer that vt_channel_sums_to_f32 adds to the gradients)."""
         if tuple(ln.normalized_shape) != (x.C,) or not ln.elementwise_affine or ln.bias is None:
             raise NotImplementedError(f"{name}: LayerNorm({ln.normalized_shape}) over a {x.C}-channel map with weight and bias")
-        if getattr(x, "logical_C", x.C) != x.C:
+        if x.logical_c != x.C:
             raise NotImplementedError(f"{name}: LayerNorm over a channel-padded map")
         if x.C % _EPC[self.dtype]:
             raise NotImplementedError(f"{name}: {x.C} channels must be a multiple of {_EPC[self.dtype]} for dtype {self.dtype}")
@@ -1502,32 +1546,26 @@ class Builder:
         dt = self.dtype
         y = out if out is not None else self.act(x.B, x.H, x.W, x.C, name + ".y")
         assert y.same_geom(x), "out geometry mismatch"
-        pb = self.pref(pre_bias) if pre_bias is not None else None
+        pb = self.pref(pre_bias)
         gm = self.pref(ln.weight)
         self.emit(N.OP_LAYERNORM_FWD, [x.addr(), pb, gm, self.pref(ln.bias), y.addr()], [x.ld, y.ld, x.C, dt], [x.M, ln.eps])
         if self.need_grad:
-            tag = self.tag
 
-            def bwd():
-                self.tag = tag
-                dy = self.grad_read(y)
-                if dy is None:
-                    return
+            def bwd(dy):
                 sums = self.zeroed_f32(N.channel_sums_floats(3, x.C), "lnsums")
                 if x.needs_grad:
                     gx, res = self.grad_target(x)
                 else:
                     gx, res = self.act(x.B, x.H, x.W, x.C, name + ".dx"), None
-                self.emit(N.OP_LAYERNORM_BWD,
-                          [dy.addr(), x.addr(), pb, gm, gx.addr(), res.addr() if res is not None else None, self.bp(sums)],
-                          [dy.ld, x.ld, gx.ld, res.ld if res is not None else 0, x.C, dt], [x.M, ln.eps])
+                self.emit(N.OP_LAYERNORM_BWD, [dy.addr(), x.addr(), pb, gm, gx.addr(), _addr(res), self.bp(sums)],
+                          [dy.ld, x.ld, gx.ld, _ld(res), x.C, dt], [x.M, ln.eps])
                 if x.needs_grad:
                     self.grad_written(x)
-                dsts = [self.pgrad(ln.weight), self.pgrad(ln.bias), self.pgrad(pre_bias) if pre_bias is not None else None]
+                dsts = [self.pgrad(ln.weight), self.pgrad(ln.bias), self.pgrad(pre_bias)]
                 if any(d is not None for d in dsts):
                     self.emit(N.OP_CHANNEL_SUMS, [self.bp(sums)] + dsts, [3, x.C])
 
-            self.nodes.append(bwd)
+            self._node(y, bwd)
         return y
 
     def scale_residual(self, t: TRef, gamma: Optional[nn.Parameter], residual: TRef, out: Optional[TRef] = None,
@@ -1538,16 +1576,11 @@ class Builder:
         self.tag += 1
         dt = self.dtype
         y = out if out is not None else self.act(t.B, t.H, t.W, t.C, name + ".y")
-        gm = self.pref(gamma) if gamma is not None else None
+        gm = self.pref(gamma)
         self.emit(N.OP_SCALE_RES_FWD, [t.addr(), gm, residual.addr(), y.addr()], [t.ld, residual.ld, y.ld, t.C, dt], [t.M])
         if self.need_grad:
-            tag = self.tag
 
-            def bwd():
-                self.tag = tag
-                dy = self.grad_read(y)
-                if dy is None:
-                    return
+            def bwd(dy):
                 self.grad_add(residual, dy)
                 if gamma is None:
                     self.grad_add(t, dy)
@@ -1561,7 +1594,7 @@ class Builder:
                 if self.pgrad(gamma) is not None:
                     self.emit(N.OP_CHANNEL_SUMS, [self.bp(sums), self.pgrad(gamma)], [1, t.C])
 
-            self.nodes.append(bwd)
+            self._node(y, bwd)
         return y
 
     # -- MLP-Mixer pieces (reference backbones/mlp_mixer.py:28,34,52,60): vt_token_mix.hip ---------------------
@@ -1571,15 +1604,13 @@ class Builder:
         tap offsets) does not take.  The gather orders a patch row (py, px, c), the order of the channels_last filter
         image [d_model][p][p][Cin], so the filter is read as it lies (bf16: in the mirror).  Backward scatters into the
         image gradient only where the image requires one."""
-        import types
-
         p = conv.kernel_size[0]
         if (tuple(conv.kernel_size) != (p, p) or tuple(conv.stride) != (p, p) or tuple(conv.padding) != (0, 0) or
                 tuple(conv.dilation) != (1, 1) or conv.groups != 1):
             raise NotImplementedError(f"{name}: a patch embedding is a p x p convolution with stride p, no padding, groups = 1")
         cin, dt = conv.in_channels, self.dtype
-        if getattr(x, "logical_C", x.C) != cin:
-            raise ValueError(f"{name}: conv expects {cin} input channels, got {getattr(x, 'logical_C', x.C)}")
+        if x.logical_c != cin:
+            raise ValueError(f"{name}: conv expects {cin} input channels, got {x.logical_c}")
         if x.H % p or x.W % p:
             raise ValueError(f"{name}: a {x.H}x{x.W} image is no whole number of {p}x{p} patches")
         rows = cin * p * p
@@ -1591,29 +1622,21 @@ class Builder:
         patches = self.act(B, H // p, W // p, rows, name + ".patches", needs_grad=x.needs_grad)
         self.emit(N.OP_PATCHIFY_FWD, [x.addr(), patches.addr()], [x.ld, patches.ld, B, H, W, cin, p, dt])
         if self.need_grad and x.needs_grad:
-            tag = self.tag
 
-            def bwd():
-                self.tag = tag
-                dp = self.grad_read(patches)
-                if dp is None:
-                    return
+            def bwd(dp):
                 gx, res = self.grad_target(x)
-                self.emit(N.OP_PATCHIFY_BWD, [dp.addr(), gx.addr(), res.addr() if res is not None else None],
-                          [dp.ld, gx.ld, res.ld if res is not None else 0, B, H, W, cin, x.C, p, dt])
+                self.emit(N.OP_PATCHIFY_BWD, [dp.addr(), gx.addr(), _addr(res)], [dp.ld, gx.ld, _ld(res), B, H, W, cin, x.C, p, dt])
                 self.grad_written(x)
 
-            self.nodes.append(bwd)
-        lin = types.SimpleNamespace(in_features=rows, out_features=conv.out_channels, weight=conv.weight, bias=conv.bias)
-        return self.linear_unit(patches, lin, 0, name=name)
+            self._node(patches, bwd)
+        return self.conv_unit(patches, ConvSpec(1, 1, 0, 1, 1, rows, conv.out_channels, conv.weight, conv.bias), None, 0, name=name)
 
     def _token_slab(self, nbytes: int) -> Buf:
         """slab scratch of the token filter gradients: one per size, shared by every layer of that shape (their launches
         follow each other on one stream)"""
-        slabs = self.__dict__.setdefault("_tok_slabs", {})
-        if nbytes not in slabs:
-            slabs[nbytes] = self.alloc(nbytes, "token_wgrad_slabs")
-        return slabs[nbytes]
+        if nbytes not in self._tok_slabs:
+            self._tok_slabs[nbytes] = self.alloc(nbytes, "token_wgrad_slabs")
+        return self._tok_slabs[nbytes]
 
     def token_linear(self, x: TRef, linear: nn.Linear, act: int = 0, residual: Optional[TRef] = None,
                      out: Optional[TRef] = None, name: str = "token_linear") -> TRef:
@@ -1626,7 +1649,7 @@ class Builder:
         K, M, dt = x.H * x.W, linear.out_features, self.dtype
         if linear.in_features != K:
             raise ValueError(f"{name}: Linear expects {linear.in_features} tokens, the map has {x.H}x{x.W} = {K}")
-        if getattr(x, "logical_C", x.C) != x.C or x.C % _EPC[dt]:
+        if x.logical_c != x.C or x.C % _EPC[dt]:
             raise NotImplementedError(f"{name}: {x.C} channels must be a multiple of {_EPC[dt]} for dtype {dt}")
         if act not in (0, 4):
             raise NotImplementedError(f"{name}: activation code {act} (token mixing implements none and exact GELU)")
@@ -1644,32 +1667,18 @@ class Builder:
         wptr = self.pref(w, mirror=True) if dt == N.VT_BF16 else self.pref(w)
         track = self.need_grad
         z = self.act(B, Hy, Wy, Cc, name + ".z") if (act and track) else None
-        if act:
-            self.emit(N.OP_TOKEN_MIX,
-                      [x.addr(), wptr, self.pref(bias) if bias is not None else None, None, z.addr() if z is not None else None,
-                       y.addr()], [x.ld, K, 0, 0, z.ld if z is not None else 0, y.ld, act, B, K, M, Cc, dt])
-        else:
-            self.emit(N.OP_TOKEN_MIX,
-                      [x.addr(), wptr, self.pref(bias) if bias is not None else None,
-                       residual.addr() if residual is not None else None, y.addr(), None],
-                      [x.ld, K, 0, residual.ld if residual is not None else 0, y.ld, 0, 0, B, K, M, Cc, dt])
+        o1, o2 = (z, y) if act else (y, None)  # (with an activation: the pre-activation, where backward needs it, and y)
+        self.emit(N.OP_TOKEN_MIX, [x.addr(), wptr, self.pref(bias), _addr(residual), _addr(o1), _addr(o2)],
+                  [x.ld, K, 0, _ld(residual), _ld(o1), _ld(o2), act, B, K, M, Cc, dt])
         if track:
-            tag = self.tag
 
-            def bwd():
-                self.tag = tag
-                dy = self.grad_read(y)
-                if dy is None:
-                    return
-                if residual is not None:
-                    self.grad_add(residual, dy)
+            def bwd(dy):
+                self.grad_add(residual, dy)
                 dz = dy
                 if act:  # dz = dy * act'(z)
                     dz = self.act(B, Hy, Wy, Cc, name + ".dz")
-                    self.emit(N.OP_BN_BWD_APPLY, [dy.addr(), z.addr(), None, None, None, dz.addr()],
-                              [dy.ld, z.ld, dz.ld, Cc, act, dt], [dz.M])
-                dw = self.pgrad(w)
-                db = self.pgrad(bias) if bias is not None else None
+                    self._act_bwd(dy, z, None, None, None, dz, act)
+                dw, db = self.pgrad(w), self.pgrad(bias)
                 if dw is not None or db is not None:
                     nbytes = int(N.lib().vt_token_mix_wgrad_scratch_bytes(B, K, M, Cc, dt))
                     slab = self._token_slab(nbytes)
@@ -1678,12 +1687,11 @@ class Builder:
                               [nbytes], side=True)
                 if x.needs_grad:
                     gx, res = self.grad_target(x)
-                    self.emit(N.OP_TOKEN_MIX,
-                              [dz.addr(), wptr, None, res.addr() if res is not None else None, gx.addr(), None],
-                              [dz.ld, K, 1, res.ld if res is not None else 0, gx.ld, 0, 0, B, M, K, Cc, dt])
+                    self.emit(N.OP_TOKEN_MIX, [dz.addr(), wptr, None, _addr(res), gx.addr(), None],
+                              [dz.ld, K, 1, _ld(res), gx.ld, 0, 0, B, M, K, Cc, dt])
                     self.grad_written(x)
 
-            self.nodes.append(bwd)
+            self._node(y, bwd)
         return y
 
     # -- ESE gate (reference vovnet.py:20-28) ---------------------------------------------
@@ -1693,33 +1701,21 @@ class Builder:
         s = self.conv_unit(pooled, linear, None, False, name=name + ".linear")
         self.tag += 1
         y = out if out is not None else self.act(x.B, x.H, x.W, x.C, name + ".y")
-        self.emit(N.OP_ESE_FWD, [x.addr(), s.addr(), residual.addr() if residual else None, y.addr()],
-                  [x.ld, s.ld, residual.ld if residual else 0, y.ld, x.B, x.H * x.W, x.C, self.dtype])
+        self.emit(N.OP_ESE_FWD, [x.addr(), s.addr(), _addr(residual), y.addr()],
+                  [x.ld, s.ld, _ld(residual), y.ld, x.B, x.H * x.W, x.C, self.dtype])
         if self.need_grad:
-            tag = self.tag
 
-            def bwd():
-                self.tag = tag
-                dy = self.grad_read(y)
-                if dy is None:
-                    return
-                if residual is not None:
-                    self.grad_add(residual, dy)
-                gx, res = self.grad_target(x)
-                acc = 0
-                if res is not None:
-                    if not (res.buf is gx.buf and res.coff == gx.coff):
-                        self._add_into(gx, res, False)
-                    acc = 1
+            def bwd(dy):
+                self.grad_add(residual, dy)
+                gx, acc = self.grad_accum_target(x)
                 ds32 = self.f32(x.B * x.C, "ds32")
                 self.emit(N.OP_ESE_BWD, [dy.addr(), x.addr(), s.addr(), gx.addr(), self.bp(ds32)],
                           [dy.ld, x.ld, s.ld, gx.ld, x.B, x.H * x.W, x.C, acc, self.dtype])
                 self.grad_written(x)
                 gs_, _ = self.grad_target(s)
-                self.emit(N.OP_COPY2D, [self.bp(ds32), gs_.addr()], [N.VT_F32, self.dtype, x.C, 0],
-                          [x.C, gs_.ld, x.B])
+                self.emit(N.OP_COPY2D, [self.bp(ds32), gs_.addr()], [N.VT_F32, self.dtype, x.C, 0], [x.C, gs_.ld, x.B])
 
-            self.nodes.append(bwd)
+            self._node(y, bwd)
         return y
 
     # -- classifier head + loss (reference classifier.py:58-64, 92) -----------------------

@@ -56,9 +56,7 @@ class _NeckRunner:
         prog = self.cache.get(key)
         if prog is None:
             b = E.Builder(self.store, dtype, self.module.training, need_grad)
-            if dtype == N.VT_BF16:
-                n = self.store.pflat.numel()
-                b.emit(N.OP_COPY2D, [(E.PARAMS, 0), (E.MIRROR, 0)], [N.VT_F32, N.VT_BF16, n, 0], [n, n, 1])
+            b.refresh_mirror()
             refs = [b.input_map(x.shape[0], x.shape[1], x.shape[2], x.shape[3], f"in{i}",
                                 requires_grad=bool(x.requires_grad) and need_grad) for i, x in enumerate(xs)]
             outs = self.module._vt_emit_list(b, refs)

@@ -102,7 +102,7 @@ class Program:
         self.fwd_ops = E.ops_array(fwd)
         self.bwd_ops = E.ops_array(bwd)
         self.param_grad_off = dict(b.param_grad_off)
-        self.input_grad = getattr(b, "input_grad", None)
+        self.input_grad = b.input_grad
         self.n_units = b.n_units
         self.builder = b  # kept for tools/debug_*.py (name -> activation / gradient buffers)
         self.kind_histogram = {}
@@ -226,11 +226,7 @@ class BackboneRunner:
         if prog is None:
             B, C_, H, W = x.shape
             b = E.Builder(self.store, dtype, self.module.training, need_grad)
-            if dtype == N.VT_BF16:
-                # module API: the caller may have changed the f32 masters with any optimiser,
-                # so the bf16 mirror is refreshed at the head of every forward
-                n = self.store.pflat.numel()
-                b.emit(N.OP_COPY2D, [(E.PARAMS, 0), (E.MIRROR, 0)], [N.VT_F32, N.VT_BF16, n, 0], [n, n, 1])
+            b.refresh_mirror()
             xr = b.input_images(B, C_, H, W, requires_grad=x.requires_grad and need_grad)
             maps = self.module._vt_emit_maps(b, xr)
             outs = maps if all_maps else maps[-1:]

@@ -50,21 +50,6 @@ OPTIMIZERS = ("SGD", "AdamW", "Adam")  # classifier.py:46,157-169 takes the name
 HYPER_STEP = 4
 
 
-class _LinearAsConv:
-    """nn.Linear seen as a 1x1 convolution over a [B,1,1,C] map (classifier.py:63)."""
-
-    kernel_size = (1, 1)
-    stride = (1, 1)
-    padding = (0, 0)
-    dilation = (1, 1)
-    groups = 1
-
-    def __init__(self, linear: nn.Linear, out_channels: Optional[int] = None):
-        self.weight, self.bias = linear.weight, linear.bias
-        # (out_channels > out_features: the rows beyond the parameter's own are zeros its slot of the flat store reserves)
-        self.out_channels, self.in_channels = out_channels or linear.out_features, linear.in_features
-
-
 def param_groups(model: nn.Module) -> dict:
     """id(param) -> group, the split of classifier.py:111-155 (norm / bias / everything else)."""
     out = {}
@@ -290,7 +275,7 @@ class TrainStep:
         fmap = backbone._vt_emit_maps(b, x)[-1]
         # (include_pool=False: the last entry IS the backbone's forward output, [B,1,1,C] -- no pooling launch)
         pooled = b.global_avgpool(fmap, "head.pool") if self.include_pool else fmap
-        logits = b.conv_unit(pooled, _LinearAsConv(head, self._head_rows), None, False, name="head.linear")
+        logits = b.conv_unit(pooled, E.ConvSpec.from_linear(head, self._head_rows), None, False, name="head.linear")
         self._loss_buf = b.xent(logits, label_smoothing, 1.0 / batch_size, mix=self.mix, num_classes=num_classes)
         self._logits = logits
         b.build_backward()
@@ -701,7 +686,7 @@ class TrainStep:
             fmap = self.model[0]._vt_emit_maps(b, x)[-1]
             pooled = b.global_avgpool(fmap, "head.pool") if self.include_pool else fmap
             # (the head by position from the end: model[3] with the pooling children, model[1] without)
-            logits = b.conv_unit(pooled, _LinearAsConv(self.model[-1], self._head_rows), None, False, name="head.linear")
+            logits = b.conv_unit(pooled, E.ConvSpec.from_linear(self.model[-1], self._head_rows), None, False, name="head.linear")
             sums = b.xent_eval(logits, num_classes=self.num_classes)
             b.build_backward()
             prog = Program(b, [logits], [])
