@@ -204,6 +204,42 @@ int vt_patchify_fwd(const void* img, int32_t ldi, void* out, int32_t ldo, int32_
 int vt_patchify_bwd(const void* dout, int32_t lddo, void* dimg, int32_t ldg, const void* residual, int32_t ldr, int32_t B,
                     int32_t H, int32_t W, int32_t Cin, int32_t Cpad, int32_t p, int32_t dtype, void* stream);
 
+/* Multi-head self-attention (ViT: reference backbones/vit.py:34-46 -- F.scaled_dot_product_attention over (B, heads, L,
+ * head_dim) views) and a ViT's token bookkeeping (vit.py:145-151), vt_attention.hip.  Q, K, V, O and their gradients are
+ * [B][L][heads * head_dim] token-major rows with a row stride each (a multiple of 8 (bf16) / 4 (f32), like heads * head_dim);
+ * head h is the channel slice [h head_dim, (h + 1) head_dim), so the three operands may be channel slices of one [B][L][3 d]
+ * buffer and nothing is transposed in memory.  head_dim is 32 or 64 (VT_ERR_UNSUPPORTED otherwise), L is arbitrary.
+ *   vt_attn_fwd:   o = softmax(scale q k^T) v per (image, head); lse[B][heads][L] (f32) = log sum_k exp(scale q.k), for the
+ *                  backward.  The L x L scores never reach memory: 64-query tiles against 64-key tiles with the running row
+ *                  maximum subtracted.  bf16: mfma_f32_16x16x32_bf16 for both products, softmax in f32, P rounded to bf16
+ *                  only as the operand of P v, V tiles read with ds_read_b64_tr_b16; f32: exact f32 FMA.
+ *   vt_attn_bwd:   dq, dk, dv (each may be NULL) from q, k, v, o, dout and lse: P is recomputed from the scores and lse,
+ *                  delta = rowsum(dout o) goes through `scratch` (vt_attn_bwd_scratch_bytes).  One kernel owns a key tile
+ *                  and loops over query tiles (dk, dv), one owns a query tile and loops over key tiles (dq): no atomics,
+ *                  bit-identical from run to run.
+ *   vt_vit_tokens_fwd:   out[b][0] = cls (cls not NULL: c0 = 1, else c0 = 0), out[b][c0 + t] = embed[b][t] + pe[t];
+ *                        embed is [B][T][C], out [B][c0 + T][C]; pe [T][C] and cls [C] are f32 masters
+ *   vt_vit_tokens_bwd:   dembed[b][t] = dout[b][has_cls + t], dpe[t] += sum_b dout[b][has_cls + t], dcls += sum_b dout[b][0]
+ *                        (f32, summed over the images in order by the one thread that owns the element; each may be NULL)
+ *   vt_token_select_fwd: out[b] = x[b][t0]: row t0 of every image of [B][T][C] to [B][C]
+ *   vt_token_select_bwd: dx[b][t0] = dout[b], every other row zero; with `accumulate` dx[b][t0] += dout[b] and the other rows
+ *                        stay */
+int vt_attn_fwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv, void* o, int32_t ldo,
+                float* lse, float scale, int32_t B, int32_t heads, int32_t L, int32_t head_dim, int32_t dtype, void* stream);
+int64_t vt_attn_bwd_scratch_bytes(int32_t B, int32_t heads, int32_t L);
+int vt_attn_bwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv, const void* o, int32_t ldo,
+                const void* dout, int32_t lddo, const float* lse, void* dq, int32_t lddq, void* dk, int32_t lddk, void* dv,
+                int32_t lddv, void* scratch, int64_t scratch_bytes, float scale, int32_t B, int32_t heads, int32_t L,
+                int32_t head_dim, int32_t dtype, void* stream);
+int vt_vit_tokens_fwd(const void* embed, int32_t lde, const float* pe, const float* cls, void* out, int32_t ldo, int32_t B,
+                      int32_t T, int32_t C, int32_t dtype, void* stream);
+int vt_vit_tokens_bwd(const void* dout, int32_t lddo, void* dembed, int32_t lde, float* dpe, float* dcls, int32_t has_cls,
+                      int32_t B, int32_t T, int32_t C, int32_t dtype, void* stream);
+int vt_token_select_fwd(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t B, int32_t T, int32_t t0, int32_t C,
+                        int32_t dtype, void* stream);
+int vt_token_select_bwd(const void* dout, int32_t lddo, void* dx, int32_t ldx, int32_t accumulate, int32_t B, int32_t T,
+                        int32_t t0, int32_t C, int32_t dtype, void* stream);
+
 /* Filter gradient: dw[n][t][c] += sum_pixels dz(pix,n) * x_gathered(pix,t,c),
  * fp32 accumulation straight into the (channels_last) .grad of the weight.
  * `d` is the forward descriptor (ldy = pixel stride of dz).  Replaces the
@@ -638,6 +674,12 @@ enum vt_op_kind {
     VT_OP_TOKEN_WGRAD,       /* vt_token_mix_wgrad */
     VT_OP_PATCHIFY_FWD,      /* vt_patchify_fwd */
     VT_OP_PATCHIFY_BWD,      /* vt_patchify_bwd */
+    VT_OP_ATTN_FWD,          /* vt_attn_fwd */
+    VT_OP_ATTN_BWD,          /* vt_attn_bwd */
+    VT_OP_VIT_TOKENS_FWD,    /* vt_vit_tokens_fwd */
+    VT_OP_VIT_TOKENS_BWD,    /* vt_vit_tokens_bwd */
+    VT_OP_TOKEN_SELECT_FWD,  /* vt_token_select_fwd */
+    VT_OP_TOKEN_SELECT_BWD,  /* vt_token_select_bwd */
     VT_OP_KIND_END
 };
 

@@ -117,7 +117,13 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_TOKEN_WGRAD,
     OP_PATCHIFY_FWD,
     OP_PATCHIFY_BWD,
-) = range(1, 60)
+    OP_ATTN_FWD,
+    OP_ATTN_BWD,
+    OP_VIT_TOKENS_FWD,
+    OP_VIT_TOKENS_BWD,
+    OP_TOKEN_SELECT_FWD,
+    OP_TOKEN_SELECT_BWD,
+) = range(1, 66)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -161,6 +167,12 @@ OP_NAMES = {
     OP_TOKEN_WGRAD: "token_wgrad",
     OP_PATCHIFY_FWD: "patchify_fwd",
     OP_PATCHIFY_BWD: "patchify_bwd",
+    OP_ATTN_FWD: "attn_fwd",
+    OP_ATTN_BWD: "attn_bwd",
+    OP_VIT_TOKENS_FWD: "vit_tokens_fwd",
+    OP_VIT_TOKENS_BWD: "vit_tokens_bwd",
+    OP_TOKEN_SELECT_FWD: "token_select_fwd",
+    OP_TOKEN_SELECT_BWD: "token_select_bwd",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -282,6 +294,14 @@ SYMBOLS = {
     "vt_token_mix_wgrad": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_patchify_fwd": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_patchify_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vt_attn_fwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _f32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vt_attn_bwd_scratch_bytes": (_i64, [_i32, _i32, _i32]),
+    "vt_attn_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64,
+                           _f32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vt_vit_tokens_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vt_vit_tokens_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vt_token_select_fwd": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vt_token_select_bwd": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_bn_act_bwd_fused": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, C.c_int64, _i32, _i32, _i32, _f64, _f64, _i32, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _i32, _vp]),
     "vt_bn_bwd_fused_timeouts": (_i32, [C.POINTER(C.c_uint32)]),

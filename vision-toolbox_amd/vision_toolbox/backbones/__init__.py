@@ -1,16 +1,18 @@
-"""Backbones of the MI355X hot path: Darknet / CSPDarknet / DarknetYOLOv5 / VoVNet / ConvNeXt / MLP-Mixer.
+"""Backbones of the MI355X hot path: Darknet / CSPDarknet / DarknetYOLOv5 / VoVNet / ConvNeXt / MLP-Mixer / ViT.
 
 Both surfaces the reference snapshot exposes are exported: the classes with
 `from_config` (reference backbones/__init__.py:3,10, tests/test_backbones.py:25-30) and the
 named factories that classifier.py:58 / README.md:27 / the checkpoint file names use.
 ConvNeXt (V1 on the GPU; V2's GlobalResponseNorm on CPU tensors only) is exported as the class with
 `from_config`, as the reference does (backbones/convnext.py:112), and so is MLPMixer (backbones/mlp_mixer.py:39), the
-first family without convolutions: its token mixing runs on the transposed-GEMM kernels of vt_token_mix.hip.  The
-reference's other backbones (ViT, Swin, torchvision extractors, ...) are outside this build's scope.
+first family without convolutions: its token mixing runs on the transposed-GEMM kernels of vt_token_mix.hip.  ViT
+(backbones/vit.py:111, with its blocks MHA / ViTBlock / MHAPooling) runs on the fused attention kernels of vt_attention.hip;
+the families the reference builds on it (DeiT, CaiT, Swin) and its torchvision extractors are not part of this build yet.
 """
 from .base import BaseBackbone
 from .convnext import ConvNeXt, ConvNeXtBlock, GlobalResponseNorm
 from .mlp_mixer import MLP, MixerBlock, MLPMixer
+from .vit import MHA, MHAPooling, ViT, ViTBlock
 from .darknet import (
     CSPDarknetStage,
     Darknet,

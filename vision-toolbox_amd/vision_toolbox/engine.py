@@ -514,6 +514,7 @@ class Builder:
         self.input_grad: Optional[Buf] = None  # NCHW f32 gradient of the images (input_images(requires_grad=True))
         self._deferred_flush: Optional[TRef] = None  # grad_target -> grad_written
         self._tok_slabs: dict[int, Buf] = {}  # _token_slab
+        self._attn_scratch: dict[int, Buf] = {}  # attention: the backward's delta, per size
 
     # -- memory -----------------------------------------------------------------
     def alloc(self, nbytes: int, name: str = "") -> Buf:
@@ -1690,6 +1691,97 @@ class Builder:
                     self.emit(N.OP_TOKEN_MIX, [dz.addr(), wptr, None, _addr(res), gx.addr(), None],
                               [dz.ld, K, 1, _ld(res), gx.ld, 0, 0, B, M, K, Cc, dt])
                     self.grad_written(x)
+
+            self._node(y, bwd)
+        return y
+
+    # -- ViT pieces (reference backbones/vit.py:34-46, 145-151): vt_attention.hip ---------------------------------
+    def attention(self, q: TRef, k: TRef, v: TRef, n_heads: int, name: str = "attention") -> TRef:
+        """softmax(q k^T / sqrt(head_dim)) v per (image, head) on token maps [B, 1, L, C] (tokens along W), head h = the
+        channel slice [h head_dim, (h + 1) head_dim) -- q, k and v may be channel slices of one buffer, nothing is
+        transposed (vt_attn_fwd; it also writes the row log-sum-exp the backward needs).  Backward: one vt_attn_bwd
+        writes d(q), d(k) and d(v) into the gradient buffers of the three producers; it has no atomics, so it is the
+        same launch under `deterministic`."""
+        dt = self.dtype
+        if not (q.same_geom(k) and q.same_geom(v)) or q.H != 1:
+            raise ValueError(f"{name}: q, k and v are [B, 1, L, C] token maps of one geometry")
+        if n_heads <= 0 or q.C % n_heads:
+            raise ValueError(f"{name}: {q.C} channels do not split into n_heads={n_heads}")
+        D = q.C // n_heads
+        if D not in (32, 64):
+            raise NotImplementedError(f"{name}: head_dim = {q.C} / n_heads={n_heads} = {D}: the attention kernels implement "
+                                      "head_dim 32 and 64")
+        if any(t.logical_c != t.C for t in (q, k, v)) or q.C % _EPC[dt]:
+            raise NotImplementedError(f"{name}: {q.C} channels must be a multiple of {_EPC[dt]} for dtype {dt}")
+        self.tag += 1
+        B, L, scale = q.B, q.W, D ** -0.5
+        o = self.act(B, 1, L, q.C, name + ".o")
+        lse = self.f32(B * n_heads * L, name + ".lse")
+        self.emit(N.OP_ATTN_FWD, [q.addr(), k.addr(), v.addr(), o.addr(), self.bp(lse)],
+                  [q.ld, k.ld, v.ld, o.ld, B, n_heads, L, D, dt], [scale])
+        if self.need_grad and (q.needs_grad or k.needs_grad or v.needs_grad):
+
+            def bwd(do):
+                nbytes = int(N.lib().vt_attn_bwd_scratch_bytes(B, n_heads, L))
+                if nbytes not in self._attn_scratch:  # (delta: one per size, the launches follow each other on one stream)
+                    self._attn_scratch[nbytes] = self.alloc(nbytes, "attn_delta")
+                gs = []
+                for t in (q, k, v):
+                    g = None
+                    if t.needs_grad:
+                        g, res = self.grad_target(t)
+                        assert res is None and self._deferred_flush is None, "q, k and v have one consumer, the attention"
+                    gs.append(g)
+                self.emit(N.OP_ATTN_BWD,
+                          [q.addr(), k.addr(), v.addr(), o.addr(), do.addr(), self.bp(lse), *[_addr(g) for g in gs],
+                           self.bp(self._attn_scratch[nbytes])],
+                          [q.ld, k.ld, v.ld, o.ld, do.ld, *[_ld(g) for g in gs], B, n_heads, L, D, dt], [scale, nbytes])
+
+            self._node(o, bwd)
+        return o
+
+    def vit_tokens(self, embed: TRef, pe: nn.Parameter, cls_token: Optional[nn.Parameter], name: str = "tokens") -> TRef:
+        """the token map of a ViT: [B, gh, gw, C] patch embeddings + pe, behind the class token where there is one ->
+        [B, 1, L, C] (vt_vit_tokens_fwd; the token is broadcast over the batch).  Backward copies the patch rows into
+        d(embed) and sums d(pe) / d(cls_token) over the batch in a fixed order (vt_vit_tokens_bwd)."""
+        T, Cc, dt = embed.H * embed.W, embed.C, self.dtype
+        if embed.logical_c != Cc or pe.numel() != T * Cc:
+            raise ValueError(f"{name}: pe holds {pe.numel()} values, the {embed.H}x{embed.W} map of {Cc} channels {T * Cc}")
+        if cls_token is not None and cls_token.numel() != Cc:
+            raise ValueError(f"{name}: cls_token holds {cls_token.numel()} values for {Cc} channels")
+        self.tag += 1
+        B, c0 = embed.B, int(cls_token is not None)
+        y = self.act(B, 1, T + c0, Cc, name + ".y")
+        self.emit(N.OP_VIT_TOKENS_FWD, [embed.addr(), self.pref(pe), self.pref(cls_token), y.addr()], [embed.ld, y.ld, B, T, Cc, dt])
+        if self.need_grad:
+
+            def bwd(dy):
+                ge = None
+                if embed.needs_grad:
+                    ge, res = self.grad_target(embed)
+                    assert res is None and self._deferred_flush is None, "the patch embedding has one consumer"
+                dpe, dcls = self.pgrad(pe), self.pgrad(cls_token)
+                if ge is None and dpe is None and dcls is None:
+                    return
+                self.emit(N.OP_VIT_TOKENS_BWD, [dy.addr(), _addr(ge), dpe, dcls], [dy.ld, _ld(ge), c0, B, T, Cc, dt])
+
+            self._node(y, bwd)
+        return y
+
+    def token_select(self, x: TRef, t0: int, name: str = "token_select") -> TRef:
+        """token t0 of every image of a [B, 1, L, C] map -> [B, 1, 1, C] (class-token pooling: `out[:, 0]`).  Backward writes
+        the row and zeros elsewhere, or adds the row to a gradient that is already there."""
+        if x.H != 1 or not 0 <= t0 < x.W:
+            raise ValueError(f"{name}: token {t0} of a [B, {x.H}, {x.W}, C] map")
+        self.tag += 1
+        y = self.act(x.B, 1, 1, x.C, name + ".y")
+        self.emit(N.OP_TOKEN_SELECT_FWD, [x.addr(), y.addr()], [x.ld, y.ld, x.B, x.W, t0, x.C, self.dtype])
+        if self.need_grad and x.needs_grad:
+
+            def bwd(dy):
+                gx, acc = self.grad_accum_target(x)
+                self.emit(N.OP_TOKEN_SELECT_BWD, [dy.addr(), gx.addr()], [dy.ld, gx.ld, acc, x.B, x.W, t0, x.C, self.dtype])
+                self.grad_written(x)
 
             self._node(y, bwd)
         return y
