@@ -429,6 +429,19 @@ typedef struct vt_pw_desc {
     int32_t C[2];       /* output channels per group */
     const void* w[2];   /* filters [C[g]][K], row stride ldw[g] */
     int32_t ldw[2];
+    /* Producer fold (NULL / 0: none, the behaviour above).  `x` then holds the stored PRE-activation z0 of the training-mode
+     * BatchNorm unit that produces this unit's input, `pcoef` is float[4][K] = scale | shift | mean | invstd of that
+     * BatchNorm and `pact` its activation code (0 none, 1 ReLU): every pass applies y0 = act(z0*scale + shift), rounded to
+     * bf16, to what it loads -- bit for bit the values vt_bn_act_apply / vt_bn_finalize_apply would have stored, so every
+     * result equals that of the same call on the stored y0, which then need not exist.  Only shapes with
+     * vt_pw_supported() == 2 (anything else: VT_ERR_UNSUPPORTED). */
+    const float* pcoef;
+    int32_t pact;
+    /* vt_pw_bwd_apply[_finalize] with a producer operand and WITHOUT an addend (the call is then the only writer of
+     * dx = d(y0)): also accumulate the producer's backward sums into this zeroed statistics buffer of K channels, as
+     * vt_bn_act_bwd_reduce(dx, z0, pcoef rows, M, K, pact) would from the stored dx -- [0][c] += sum g, [1][c] += sum g*xhat,
+     * g = dx * [y0 > 0] -- so that pass is not needed.  With an addend: VT_ERR_UNSUPPORTED.  NULL: not wanted. */
+    float* psums;
 } vt_pw_desc;
 int vt_pw_supported(int32_t dtype, int32_t K, int32_t C0, int32_t C1);
 /* the apply pass ALONE (inference: folded running statistics), one output group: additionally the 80-channel shapes of
@@ -471,6 +484,12 @@ int vt_pw_bwd_apply_finalize(const vt_pw_desc* d, const float* coef, const void*
                              const vt_bn_fin_bwd* fin, float* const* bcoef, void* dx, int32_t lddx, const void* addend,
                              int32_t ldadd, float* const* dw, const int32_t* lddw, void* const* dz, const int32_t* lddz,
                              void* stream);
+/* vt_pw_fwd_stats of a descriptor with a producer operand, with the PRODUCER's BatchNorm finalize step in its prologue: the
+ * producer's statistics `pfin->stats` (K channels) are complete when this launch starts, so every workgroup computes
+ * scale | shift for itself and workgroup 0 stores the four rows of d->pcoef (which the later passes read) and the running
+ * statistics.  Same values bit for bit as vt_bn_finalize(pfin->stats, K, ...) into the rows of d->pcoef followed by
+ * vt_pw_fwd_stats; those two calls run with the knob VT_BN_FIN_APPLY = 0. */
+int vt_pw_fwd_stats_finalize(const vt_pw_desc* d, const vt_bn_fin_fwd* pfin, float* const* stats, void* stream);
 
 /* ---- pooling ------------------------------------------------------------ */
 /* The normalise pass fused with the MaxPool2d(3, 2, 1) that reads its output (VoVNet: `stage.max_pool` on the previous

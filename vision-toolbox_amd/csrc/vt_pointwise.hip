@@ -41,6 +41,17 @@
 //   * BatchNorm sums: per-lane partials over the wave's pixels, folded across the 16 pixel lanes by shuffles, across
 //     the waves in LDS in a FIXED order, then one fixed-point integer atomic per channel and moment (vt_common.h):
 //     bit-identical from run to run like every other statistic of the library.
+//
+// Producer fold (template flag PROD, vt_pw_desc::pcoef): x is the stored PRE-activation z0 of the BatchNorm unit that
+// produces the unit's input, and every pass applies that unit's normalise step y0 = act(z0 * scale + shift), rounded to
+// bf16, to the 16 bytes a lane has just loaded -- the expression and the rounding of bn_fin_apply_kernel
+// (vt_elementwise.hip), so the operand is bit for bit what the passes read from a stored y0, and neither that tensor nor
+// the pass that writes it exists.  Nothing crosses a workgroup: the producer's statistics are complete when the first
+// pass starts, and that pass (STATS) may finalize them in its prologue, every workgroup for itself, as the apply passes
+// do for the unit's own BatchNorm (vt_bn_fin.h).  PROD == 2 (BWD without an addend): the kernel is the only writer of
+// d(y0) and holds, per pixel, all K channels of z0 (its operand) and of d(y0) (its result, rounded to bf16 as stored) in
+// the same lane layout, so it also forms the PRODUCER's backward sums -- sum g, sum g * xhat with g = d(y0) * [y0 > 0] --
+// with the fold of the REDUCE mode, in the format of vt_bn_act_bwd_reduce: that pass over d(y0) and z0 disappears too.
 #include <stdlib.h>
 #include <string.h>
 
@@ -101,6 +112,14 @@ struct PwArgs {
     int fin;
     VtFinFwd ffin[2];  // APPLY
     VtFinBwd bfin[2];  // BWD
+    // producer fold (PROD instantiations only; appended, so the fields above keep their offsets): the producer's
+    // coefficient rows scale | shift | mean | invstd ([4][K]), its activation code (0 / 1), and -- STATS -- its finalize
+    // step, run in the prologue of every workgroup (workgroup 0 stores the rows and the running statistics)
+    const float* pcoef;
+    int pact;
+    int pfin_on;
+    VtFinFwd pfin;
+    float* psums;  // BWD, PROD == 2: the producer's backward sums buffer
 };
 
 __device__ __forceinline__ uint4 ldg16(const bf16_t* p) { return *(const uint4*)p; }
@@ -130,7 +149,7 @@ struct PwGeom {
 // one workgroup = 4 independent waves; see the header for the lane mapping
 // EX: the optional operand is present (APPLY: a residual for EVERY group; BWD: the addend of dx) -- compile time, so
 // that the loads of a unit are unconditional and the compiler can count them (s_waitcnt vmcnt(N) instead of 0)
-template <int N, int K, int MODE, bool EX>
+template <int N, int K, int MODE, bool EX, int PROD = 0>
 __global__ void __launch_bounds__(256) pw_kernel(const PwArgs a) {
     using G = PwGeom<N, K>;
     constexpr int NT = G::NT, NU = G::NU, KS = G::KS, CT = G::CT, KV = G::KV, PITCH = G::PITCH;
@@ -211,6 +230,33 @@ __global__ void __launch_bounds__(256) pw_kernel(const PwArgs a) {
     if (kDW) {
         for (int i = tid; i < N * K; i += 256) sRed[i] = 0.f;
     }
+    // producer fold: scale | shift (PROD == 2: | mean | invstd) of the producer's K channels, behind everything else in LDS
+    float* sProd = (float*)(smem + G::SMEM);
+    constexpr bool kPRed = PROD == 2;
+    static_assert(!kPRed || (MODE == PW_BWD && !EX && G::kFull && 8 * K <= N * K), "producer sums: BWD without an addend");
+    if constexpr (PROD) {
+        static_assert(K <= 128, "a thread pair per producer channel");
+        bool pfin_done = false;
+        if constexpr (MODE == PW_STATS) {
+            if (a.pfin_on) {
+                pfin_done = true;
+                const int w = tid & 1, c = tid >> 1;
+                const bool on = c < K;
+                const int cc = on ? c : 0;
+                const VtFinFwdPre pre = vt_fin_fwd_pre(a.pfin, cc);
+                const double v = vt_replica_sum<false>(a.pfin.stats, (long)w * K + cc, 2L * K);
+                const double o = __shfl_xor(v, 1, 64);
+                if (on && w == 0) {
+                    float sc, sf;
+                    vt_fin_fwd_channel(a.pfin, c, v, o, pre.g, pre.b, pre.rm, pre.rv, sc, sf, blockIdx.x == 0);
+                    sProd[c] = sc, sProd[K + c] = sf;
+                }
+            }
+        }
+        if (!pfin_done) {
+            for (int i = tid; i < (kPRed ? 4 : 2) * K; i += 256) sProd[i] = a.pcoef[i];
+        }
+    }
     __syncthreads();
 
     // ---- fragment addressing ------------------------------------------------------------------------------------
@@ -270,6 +316,13 @@ __global__ void __launch_bounds__(256) pw_kernel(const PwArgs a) {
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) dwacc[nt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
+    float p1[kPRed ? KV : 1][8], p2[kPRed ? KV : 1][8];  // PROD == 2: the producer's sum g, sum g * (z0 - mean)
+    if constexpr (kPRed) {
+#pragma unroll
+        for (int v = 0; v < KV; ++v)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) p1[v][e] = p2[v][e] = 0.f;
+    }
 
     // ---- per-unit registers: this unit (16 pixels) and the prefetched next one ----------------------------------
     struct Regs {
@@ -316,6 +369,27 @@ __global__ void __launch_bounds__(256) pw_kernel(const PwArgs a) {
         asm volatile("" ::: "memory");
         const long p = (long)unit * 16 + pl;
         const bool ok = p < a.M;
+        // ---- producer fold: the loaded 16 bytes are z0; x = act(z0 * scale + shift) rounded to bf16 ----
+        uint4 xn[PROD ? KS : 1];
+        if constexpr (PROD) {
+#pragma unroll
+            for (int s = 0; s < KS; ++s) {
+                float v[8], psc[8], psf[8];
+                const int ck = 32 * s + 8 * q;
+                *(f32x4*)&psc[0] = *(const f32x4*)(sProd + ck);
+                *(f32x4*)&psc[4] = *(const f32x4*)(sProd + ck + 4);
+                *(f32x4*)&psf[0] = *(const f32x4*)(sProd + K + ck);
+                *(f32x4*)&psf[4] = *(const f32x4*)(sProd + K + ck + 4);
+                VecIO<bf16_t>::unpack(r.x[s], v);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    v[e] = fmaf(v[e], psc[e], psf[e]);
+                    v[e] = a.pact ? fmaxf(v[e], 0.f) : v[e];
+                }
+                xn[s] = VecIO<bf16_t>::pack(v);
+            }
+        }
+        const uint4* xop = PROD ? xn : r.x;  // the operand everywhere x is used below
         // ---- z^T = W x ----
         f32x4 zacc[NT];
 #pragma unroll
@@ -324,7 +398,7 @@ __global__ void __launch_bounds__(256) pw_kernel(const PwArgs a) {
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
                 const bf16x8 A = G::kRegW ? wz[G::kRegW ? nt : 0][G::kRegW ? s : 0] : wz_frag(nt, s);
-                zacc[nt] = mma(A, as_frag(r.x[s]), zacc[nt]);
+                zacc[nt] = mma(A, as_frag(xop[s]), zacc[nt]);
             }
         }
         bf16x8 dzt[(MODE == PW_BWD) ? NU : 1];
@@ -418,7 +492,27 @@ __global__ void __launch_bounds__(256) pw_kernel(const PwArgs a) {
                 if constexpr (EX) VecIO<bf16_t>::unpack(r.ex[v], ad);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) o[e] = xa[e >> 2][e & 3] + ad[e];
-                if (ok) *(uint4*)(a.dx + p * a.lddx + 32 * v + 8 * q) = VecIO<bf16_t>::pack(o);
+                const uint4 dxp = VecIO<bf16_t>::pack(o);
+                if (ok) *(uint4*)(a.dx + p * a.lddx + 32 * v + 8 * q) = dxp;
+                if constexpr (kPRed) {
+                    // the producer's reduction on the value just stored (what the separate pass would read back) and z0
+                    float gq[8], z0[8], psc[8], psf[8], pmu[8];
+                    const int ck = 32 * v + 8 * q;
+                    *(f32x4*)&psc[0] = *(const f32x4*)(sProd + ck);
+                    *(f32x4*)&psc[4] = *(const f32x4*)(sProd + ck + 4);
+                    *(f32x4*)&psf[0] = *(const f32x4*)(sProd + K + ck);
+                    *(f32x4*)&psf[4] = *(const f32x4*)(sProd + K + ck + 4);
+                    *(f32x4*)&pmu[0] = *(const f32x4*)(sProd + 2 * K + ck);
+                    *(f32x4*)&pmu[4] = *(const f32x4*)(sProd + 2 * K + ck + 4);
+                    VecIO<bf16_t>::unpack(dxp, gq);
+                    VecIO<bf16_t>::unpack(r.x[v], z0);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const float gg = (ok && (!a.pact || fmaf(z0[e], psc[e], psf[e]) > 0.f)) ? gq[e] : 0.f;
+                        p1[v][e] += gg;
+                        p2[v][e] = fmaf(gg, z0[e] - pmu[e], p2[v][e]);
+                    }
+                }
             }
         }
         if constexpr (kDW) {
@@ -435,7 +529,7 @@ __global__ void __launch_bounds__(256) pw_kernel(const PwArgs a) {
             }
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
-                const f32x4 t0 = mma(as_frag(r.x[ct >> 1]), sel[ct & 1], z4);
+                const f32x4 t0 = mma(as_frag(xop[ct >> 1]), sel[ct & 1], z4);
                 const uint32_t lo = VecIO<bf16_t>::pack2(t0[0], t0[1]), hi = VecIO<bf16_t>::pack2(t0[2], t0[3]);
                 xT[ct] = __builtin_bit_cast(s16x4, make_uint2(lo, hi));
             }
@@ -528,13 +622,47 @@ __global__ void __launch_bounds__(256) pw_kernel(const PwArgs a) {
             if (dst) atomicAdd(dst + (long)(n - (g ? N0 : 0)) * a.lddw[g] + c, sRed[i]);
         }
     }
+    if constexpr (kPRed) {
+        // the producer's sums: the fold of the REDUCE mode over K channels (the dW image in sRed has been flushed)
+#pragma unroll
+        for (int v = 0; v < KV; ++v)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+#pragma unroll
+                for (int off = 1; off < 16; off <<= 1) {
+                    p1[v][e] += __shfl_xor(p1[v][e], off, 64);
+                    p2[v][e] += __shfl_xor(p2[v][e], off, 64);
+                }
+            }
+        __syncthreads();
+        if (pl == 0) {
+#pragma unroll
+            for (int v = 0; v < KV; ++v)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    sRed[(wave * 2 + 0) * K + 32 * v + 8 * q + e] = p1[v][e];
+                    sRed[(wave * 2 + 1) * K + 32 * v + 8 * q + e] = p2[v][e];
+                }
+        }
+        __syncthreads();
+        const int rep = (int)(blockIdx.x % kStatReplicas);
+        for (int i = tid; i < 2 * K; i += 256) {
+            const int which = i / K, c = i - which * K;
+            float acc = sRed[(0 * 2 + which) * K + c];
+            acc += sRed[(1 * 2 + which) * K + c];
+            acc += sRed[(2 * 2 + which) * K + c];
+            acc += sRed[(3 * 2 + which) * K + c];
+            if (which) acc *= sProd[3 * K + c];  // invstd
+            vt_stat_add(a.psums, ((long)rep * 2 + which) * K + c, acc);
+        }
+    }
 }
 
-template <int N, int K, int MODE, bool EX>
+template <int N, int K, int MODE, bool EX, int PROD = 0>
 int launch_pw(const PwArgs& a, hipStream_t st, const char* who) {
     using G = PwGeom<N, K>;
-    auto kern = pw_kernel<N, K, MODE, EX>;
-    constexpr int smem = G::SMEM;
+    auto kern = pw_kernel<N, K, MODE, EX, PROD>;
+    constexpr int smem = G::SMEM + (PROD ? 4 * K * 4 : 0);
     static_assert(smem <= 160 * 1024, "weights exceed the LDS of a CU");
     if (smem > 64 * 1024) {
         const int rc = vt_raise_dynamic_lds((const void*)kern, smem, who);
@@ -551,7 +679,7 @@ int launch_pw(const PwArgs& a, hipStream_t st, const char* who) {
     long blocks = ((long)a.nunits + 4 * per_wave - 1) / (4 * per_wave);
     if (blocks > target) blocks = target;
     if (blocks < 1) blocks = 1;
-    vt_note_kernel("pw_kernel<%d,%d,%s>", N, K, MODE == PW_STATS ? "stats" : MODE == PW_APPLY ? "apply" : MODE == PW_REDUCE ? "reduce" : "bwd");
+    vt_note_kernel(PROD == 2 ? "pw_kernel<%d,%d,%s,prod+sums>" : PROD ? "pw_kernel<%d,%d,%s,prod>" : "pw_kernel<%d,%d,%s>", N, K, MODE == PW_STATS ? "stats" : MODE == PW_APPLY ? "apply" : MODE == PW_REDUCE ? "reduce" : "bwd");
     VT_LAUNCH_STOP(kern, dim3((unsigned)blocks), dim3(256), smem, st, a);
     VT_CHECK_LAUNCH(who);
     return VT_OK;
@@ -560,6 +688,25 @@ int launch_pw(const PwArgs& a, hipStream_t st, const char* who) {
 template <int MODE>
 int dispatch_pw(int N, int K, const PwArgs& a, hipStream_t st, const char* who) {
     const bool ex = MODE == PW_APPLY ? a.res[0] != nullptr : (MODE == PW_BWD ? a.add != nullptr : false);
+    if (a.pcoef) {
+        // producer fold: the shapes whose filter gradient stays in the kernel (vt_pw_supported() == 2), full width
+#define VT_PW_PROD_CASE(n, k)                                                      \
+    if (N == n && K == k) {                                                        \
+        if constexpr (MODE == PW_APPLY || MODE == PW_BWD) {                        \
+            if (ex) return launch_pw<n, k, MODE, true, 1>(a, st, who);             \
+        }                                                                          \
+        if constexpr (MODE == PW_BWD) {                                            \
+            if (a.psums) return launch_pw<n, k, MODE, false, 2>(a, st, who);       \
+        }                                                                          \
+        return launch_pw<n, k, MODE, false, 1>(a, st, who);                        \
+    }
+        VT_PW_PROD_CASE(32, 32)
+        VT_PW_PROD_CASE(64, 64)
+        VT_PW_PROD_CASE(32, 64)
+#undef VT_PW_PROD_CASE
+        vt_set_error("%s: no pointwise kernel with a producer operand for %d -> %d channels", who, K, N);
+        return VT_ERR_UNSUPPORTED;
+    }
 #define VT_PW_CASE(n, k)                                                           \
     if (N == n && K == k) {                                                        \
         if constexpr (MODE == PW_APPLY || MODE == PW_BWD) {                        \
@@ -617,6 +764,14 @@ int fill_common(PwArgs& a, const vt_pw_desc* d, const char* who, bool apply = fa
         a.w[g] = (const bf16_t*)d->w[g];
         a.ldw[g] = d->ldw[g];
     }
+    if (d->pcoef) {
+        VT_REQUIRE(!ragged && (int64_t)N * d->K <= 4096, VT_ERR_UNSUPPORTED,
+                   "%s: a producer operand needs a shape with vt_pw_supported() == 2 (%d -> %d channels)", who, d->K, N);
+        VT_REQUIRE(d->pact == 0 || d->pact == 1, VT_ERR_UNSUPPORTED, "%s: producer activation code %d (0 / 1 only)", who, d->pact);
+        VT_REQUIRE(vt_aligned16(d->pcoef), VT_ERR_INVALID, "%s: bad producer coefficients", who);
+        a.pcoef = d->pcoef;
+        a.pact = d->pact;
+    }
     return VT_OK;
 }
 
@@ -642,7 +797,7 @@ int vt_pw_apply_supported(int32_t dtype, int32_t K, int32_t C0) {
     return dtype == VT_BF16 && (shape_ok(C0, K) || ragged_apply_ok(C0, K, 1));
 }
 
-int vt_pw_fwd_stats(const vt_pw_desc* d, float* const* stats, void* stream) {
+static int pw_fwd_stats_impl(const vt_pw_desc* d, const vt_bn_fin_fwd* pfin, float* const* stats, void* stream) {
     PwArgs a;
     int rc = fill_common(a, d, "vt_pw_fwd_stats");
     if (rc != VT_OK) return rc;
@@ -650,7 +805,35 @@ int vt_pw_fwd_stats(const vt_pw_desc* d, float* const* stats, void* stream) {
         VT_REQUIRE(stats && stats[g], VT_ERR_INVALID, "vt_pw_fwd_stats: null statistics buffer");
         a.stats[g] = stats[g];
     }
+    if (pfin) {  // (checked by vt_pw_fwd_stats_finalize)
+        float* c = (float*)d->pcoef;
+        const int K = d->K;
+        a.pfin_on = 1;
+        a.pfin = VtFinFwd{pfin->stats, pfin->gamma, pfin->beta, pfin->running_mean, pfin->running_var, pfin->num_batches_tracked,
+                          c, c + K, c + 2 * K, c + 3 * K, 1.0 / pfin->count,
+                          pfin->count > 1.0 ? pfin->count / (pfin->count - 1.0) : 1.0, pfin->eps, pfin->momentum, K};
+    }
     return dispatch_pw<PW_STATS>(a.N0 + (d->ngroups == 2 ? d->C[1] : 0), d->K, a, (hipStream_t)stream, "vt_pw_fwd_stats");
+}
+
+int vt_pw_fwd_stats(const vt_pw_desc* d, float* const* stats, void* stream) { return pw_fwd_stats_impl(d, nullptr, stats, stream); }
+
+int vt_pw_fwd_stats_finalize(const vt_pw_desc* d, const vt_bn_fin_fwd* pfin, float* const* stats, void* stream) {
+    VT_REQUIRE(d && pfin, VT_ERR_INVALID, "vt_pw_fwd_stats_finalize: null argument");
+    VT_REQUIRE(d->pcoef, VT_ERR_INVALID, "vt_pw_fwd_stats_finalize: the descriptor has no producer operand");
+    VT_REQUIRE(pfin->stats && pfin->count > 0, VT_ERR_INVALID, "vt_pw_fwd_stats_finalize: bad statistics of the producer");
+    VT_REQUIRE((pfin->running_mean == nullptr) == (pfin->running_var == nullptr), VT_ERR_INVALID,
+               "vt_pw_fwd_stats_finalize: running_mean/var must both be given or both NULL");
+    if (!VT_KNOB("VT_BN_FIN_APPLY", 1)) {
+        float* c = (float*)d->pcoef;
+        const int K = d->K;
+        const int rc = vt_bn_finalize(pfin->stats, K, pfin->count, pfin->gamma, pfin->beta, pfin->eps, pfin->momentum,
+                                      pfin->running_mean, pfin->running_var, pfin->num_batches_tracked, c, c + K, c + 2 * K,
+                                      c + 3 * K, stream);
+        if (rc != VT_OK) return rc;
+        return pw_fwd_stats_impl(d, nullptr, stats, stream);
+    }
+    return pw_fwd_stats_impl(d, pfin, stats, stream);
 }
 
 static int pw_fwd_apply_impl(const vt_pw_desc* d, const float* coef, void* const* y, const int32_t* ldy, const void* const* res,
@@ -759,6 +942,12 @@ static int pw_bwd_apply_impl(const vt_pw_desc* d, const float* coef, const void*
         VT_REQUIRE(vt_aligned16(addend) && ldadd % 8 == 0 && ldadd >= d->K, VT_ERR_INVALID, "vt_pw_bwd_apply: bad addend");
         a.add = (const bf16_t*)addend;
         a.ldadd = ldadd;
+    }
+    if (d->psums) {
+        VT_REQUIRE(d->pcoef, VT_ERR_INVALID, "vt_pw_bwd_apply: producer sums without a producer operand");
+        VT_REQUIRE(!addend, VT_ERR_UNSUPPORTED,
+                   "vt_pw_bwd_apply: the producer's sums are formed only where the kernel is the sole writer of dx (no addend)");
+        a.psums = d->psums;
     }
     for (int g = 0; g < d->ngroups; ++g) {
         if ((rc = check_rows("vt_pw_bwd_apply", "dy", g, dy[g], lddy[g], d->C[g], false)) != VT_OK) return rc;

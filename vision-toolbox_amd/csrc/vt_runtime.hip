@@ -354,8 +354,17 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
             d.M = (int64_t)F[0];
             d.x = P[0], d.ldx = I[5];
             d.w[0] = P[1], d.w[1] = P[2], d.ldw[0] = I[6], d.ldw[1] = I[7];
+            // producer fold: ptr[20]: the producer's coefficient rows (null: none) | i[20]: its activation code
+            // | ptr[21] (PW_BWD, PW_BWD_FIN): the producer's backward sums
+            d.pcoef = (const float*)P[20], d.pact = I[20];
+            if (op.kind == VT_OP_PW_BWD || op.kind == VT_OP_PW_BWD_FIN) d.psums = (float*)P[21];
             if (op.kind == VT_OP_PW_STATS) {
                 float* st2[2] = {(float*)P[3], (float*)P[4]};
+                if (d.pcoef && P[5]) {  // ... finalized in the prologue: ptr[5..10]: stats gamma beta rm rv nbt | f[1..3]: count eps momentum
+                    const vt_bn_fin_fwd pf{(const float*)P[5], F[1], (const float*)P[6], (const float*)P[7], (float)F[2], (float)F[3],
+                                           (float*)P[8], (float*)P[9], (int64_t*)P[10]};
+                    return vt_pw_fwd_stats_finalize(&d, &pf, st2, st);
+                }
                 return vt_pw_fwd_stats(&d, st2, st);
             }
             if (op.kind == VT_OP_PW_APPLY) {

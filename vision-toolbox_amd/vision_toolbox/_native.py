@@ -222,6 +222,7 @@ class PwDesc(C.Structure):
         ("C", C.c_int32 * 2),
         ("w", C.c_void_p * 2),
         ("ldw", C.c_int32 * 2),
+        ("pcoef", C.c_void_p), ("pact", C.c_int32), ("psums", C.c_void_p),  # producer fold (NULL / 0: none)
     ]  # fmt: skip
 
 
@@ -339,6 +340,7 @@ SYMBOLS = {
     "vt_pw_supported": (_i32, [_i32, _i32, _i32, _i32]),
     "vt_pw_apply_supported": (_i32, [_i32, _i32, _i32]),
     "vt_pw_fwd_stats": (_i32, [C.POINTER(PwDesc), C.POINTER(_vp), _vp]),
+    "vt_pw_fwd_stats_finalize": (_i32, [C.POINTER(PwDesc), C.POINTER(BnFinFwd), C.POINTER(_vp), _vp]),
     "vt_pw_fwd_apply": (_i32, [C.POINTER(PwDesc), _vp, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_vp), C.POINTER(_i32), _vp]),
     "vt_pw_bwd_reduce": (_i32, [C.POINTER(PwDesc), _vp, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_vp), _vp]),
     "vt_pw_bwd_apply": (_i32, [C.POINTER(PwDesc), _vp, C.POINTER(_vp), C.POINTER(_i32), C.POINTER(_vp), _vp, _i32, _vp, _i32,

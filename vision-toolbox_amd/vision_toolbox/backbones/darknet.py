@@ -94,7 +94,8 @@ class CSPDarknetStage(HipModule):
         self.out_conv = ConvNormAct(out_channels, out_channels, 1)
 
     def _vt_emit(self, b, x, out=None, name: str = "csp"):
-        o = self.conv._vt_emit(b, x, name=name + ".conv")
+        # (the pair below is o's only reader: where it is a pointwise launch it normalises o's pre-activation as it loads)
+        o = self.conv._vt_emit(b, x, name=name + ".conv", defer_norm=True)
         width = self.out_conv.conv.in_channels
         half = self.conv1.conv.out_channels
         joined = b.act(o.B, o.H, o.W, width, name + ".cat")  # the tensor torch.cat would have produced

@@ -127,11 +127,13 @@ class ConvNormAct(nn.Sequential, HipModule):
             "leaky_relu(0.2), swish / silu, gelu)"
         )
 
-    def _vt_emit(self, b, x, out=None, residual=None, name: str = "cna", pool_out=None):
+    def _vt_emit(self, b, x, out=None, residual=None, name: str = "cna", pool_out=None, defer_norm: bool = False):
         """`pool_out`: also write MaxPool2d(3, 2, 1) of the unit's output there (VoVNet's `stage.max_pool`, vovnet.py:94):
-        fused into the unit's normalise pass where one exists, else a pool launch"""
+        fused into the unit's normalise pass where one exists, else a pool launch.  `defer_norm`: the output goes to
+        Builder.conv_unit_pair, which may take over the normalise pass (Builder.conv_unit)"""
         norm = self.norm if isinstance(self.norm, nn.BatchNorm2d) else None
-        return b.conv_unit(x, self.conv, norm, self._vt_relu(), residual=residual, out=out, name=name, pool_out=pool_out)
+        return b.conv_unit(x, self.conv, norm, self._vt_relu(), residual=residual, out=out, name=name, pool_out=pool_out,
+                           defer_norm=defer_norm)
 
     def _vt_emit_maps(self, b, x):
         return [self._vt_emit(b, x)]

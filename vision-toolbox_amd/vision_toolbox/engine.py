@@ -47,6 +47,9 @@ class Buf:
     offset: int  # bytes from the base
     nbytes: int
     name: str = ""
+    # the normalise pass that would write this activation has not been emitted (Builder.conv_unit(defer_norm=True)): the
+    # buffer has no place in the arena yet.  TRef.addr() -- the one door every reader goes through -- emits it then.
+    deferred: Optional["_DeferredNorm"] = None
 
 
 @dataclass(eq=False)
@@ -78,6 +81,8 @@ class TRef:
         return _ESIZE[self.dtype]
 
     def addr(self):
+        if self.buf.deferred is not None:
+            self.buf.deferred.materialise()
         return (self.buf.base, self.buf.offset + self.coff * self.esize)
 
     def sl(self, c0: int, c: int) -> "TRef":
@@ -306,6 +311,9 @@ class _GradState:
     gbuf: Optional[Buf] = None
     init: list = field(default_factory=list)  # initialised channel intervals [c0, c1) in buffer coords
     pending: list = field(default_factory=list)  # (c0, c1, TRef addend)
+    # the BatchNorm-backward sums of the unit that produced the forward buffer, formed by the launch that wrote the whole
+    # gradient (pw_units with a producer operand); Builder.grad_dirty forgets them when anything else writes the gradient
+    bn_sums: Optional[Buf] = None
 
     def covered(self, c0: int, c1: int) -> bool:
         pos = c0
@@ -396,10 +404,39 @@ class _ConvUnit:
     pool_out: Optional[TRef] = None  # max pool fused into the normalise pass ...
     pool_am: Optional[Buf] = None  # ... and its arg-max taps
     wg_key: Optional[tuple] = None  # shape group of held-back filter gradients
+    defer: bool = False  # the normalise pass is held back (_DeferredNorm)
 
     @property
     def padded(self) -> bool:
         return self.wpack is not None
+
+
+class _DeferredNorm:
+    """A training-mode BatchNorm unit whose normalise pass y = act(z * scale + shift) was held back: its only reader may be
+    a pointwise launch that applies the pass to z as it loads it (Builder.pw_units, vt_pw_desc::pcoef), and then neither
+    the pass nor y exists.  Any OTHER reader -- a unit, a returned feature map, a shortcut, a filter gradient -- asks for
+    y's address, and that request (TRef.addr) materialises y here: the buffer gets its place in the arena and the ordinary
+    normalise pass is emitted in front of the op being built."""
+
+    def __init__(self, b: "Builder", u: "_ConvUnit", stats: Buf):
+        self.b, self.u, self.stats = b, u, stats
+        self.finalized = False  # a folding pw_stats launch has finalized the statistics (coefficients, running statistics)
+
+    def materialise(self) -> None:
+        b, u = self.b, self.u
+        y, z, buf = u.y, u.z, u.y.buf
+        if b._cur is not b.fwd:
+            raise RuntimeError(f"{u.name}: the deferred output is first read outside the forward list")
+        buf.deferred = None
+        buf.offset = b.arena_top
+        b.arena_top = _round_up(buf.offset + max(buf.nbytes, 1), ALIGN)
+        tag, b.tag = b.tag, u.tag
+        if self.finalized:
+            b._act_apply(z, u.bn.cp[0], u.bn.cp[1], None, y, u.relu)
+        else:
+            ptrs, flts = u.bn.finalize_operands(self.stats, y.M)
+            b.emit(N.OP_BN_FIN_APPLY, ptrs + [z.addr(), None, y.addr()], [y.C, z.ld, 0, y.ld, u.relu, b.dtype], flts + [y.M])
+        b.tag = tag
 
 
 class Builder:
@@ -456,6 +493,15 @@ class Builder:
         # tensors of stage 2 included, 22.11 without; 23.32 with the pointwise path off).  VT_PW_MIN_MB (the tests set 0:
         # their toy tensors would otherwise never reach these kernels)
         self.pointwise_min_mb = float(os.environ.get("VT_PW_MIN_MB", "80"))
+        # A pointwise launch that is the ONLY reader of a BatchNorm unit's output takes over that unit's normalise pass: it
+        # reads the stored pre-activation and applies scale, shift and ReLU as it loads (vt_pw_desc::pcoef), so the pass and
+        # its output tensor disappear (CSPDarknetStage.conv -> conv1 | conv2 of stage 0).  Only where the producer's tensor
+        # has at least this many MB -- below what the memory-side cache holds the saved pass is a cache hit, as above.
+        # VT_PW_FOLD_MIN_MB (tests of the fold set 0); never in deterministic mode (the pointwise path is off there).
+        self.pw_fold_min_mb = float(os.environ.get("VT_PW_FOLD_MIN_MB", "80"))
+        # ... and, where its backward launch is the only writer of the producer's d(y), the producer's BatchNorm-backward
+        # reduction too (vt_pw_desc::psums).  VT_PW_FOLD_BNRED=0: the separate reduction pass.
+        self.pw_fold_bnred = os.environ.get("VT_PW_FOLD_BNRED", "1") != "0"
         self._hoisted: list[N.Op] = []
         # Filter gradients of same-shape stride-1 3x3 layers (the DarknetBlock.conv2 units of a stage, darknet.py:23-24;
         # an OSA chain, vovnet.py:41-44) are HELD BACK in backward and released together, as consecutive ops that the
@@ -625,6 +671,10 @@ class Builder:
                   [src.addr(), None, None, dst.addr() if accumulate else None, dst.addr()],
                   [src.ld, dst.ld, dst.ld, dst.C, 0, self.dtype], [dst.M])
 
+    def grad_dirty(self, t: TRef) -> None:
+        """a writer of d(t) is coming: sums formed from its earlier contents (_GradState.bn_sums) no longer describe it"""
+        self._gs(t).bn_sums = None
+
     def _flush_pending(self, t: TRef):
         gs = self._gs(t)
         c0, c1 = t.coff, t.coff + t.C
@@ -645,6 +695,7 @@ class Builder:
                 acc = gs.covered(a, b)
                 if not acc and gs.touches(a, b):
                     raise NotImplementedError("partially initialised gradient slice")
+                self.grad_dirty(t)
                 self._add_into(g, add, acc)
                 if not acc:
                     gs.init.append((a, b))
@@ -665,6 +716,7 @@ class Builder:
         gs = self._gs(t)
         c0, c1 = t.coff, t.coff + t.C
         g = self._gref(t)
+        self.grad_dirty(t)
         self._last_dgrad.pop(id(g.buf), None)  # (a writer is coming: whatever wrote the buffer last is no longer the only one)
         if gs.covered(c0, c1):
             self._flush_pending(t)
@@ -728,6 +780,7 @@ class Builder:
             # zero-fill the gaps (only dense full-width buffers can be memset)
             if t.ld == t.C and not gs.touches(c0, c1):
                 g = self._gref(t)
+                self.grad_dirty(t)
                 self._last_dgrad.pop(id(g.buf), None)
                 self.emit(N.OP_MEMSET, [g.addr()], [0], [t.M * t.C * t.esize])
                 gs.init.append((c0, c1))
@@ -795,11 +848,13 @@ class Builder:
         return conv, BNSpec.from_bn(norm)
 
     def conv_unit(self, x: TRef, conv, norm, relu, residual: Optional[TRef] = None, out: Optional[TRef] = None,
-                  name: str = "", pool_out: Optional[TRef] = None) -> TRef:
+                  name: str = "", pool_out: Optional[TRef] = None, defer_norm: bool = False) -> TRef:
         """y = [relu]([bn](conv(x))) [+ residual], written to `out` when given.  `conv`: nn.Conv2d or ConvSpec, `norm`:
         nn.BatchNorm2d, BNSpec, nn.Identity or None.  `pool_out`: MaxPool2d(3, 2, 1) of y goes there as well -- from the
         unit's own normalise pass where it has one (vt_bn_act_apply_pool), and then the unit's BatchNorm backward reads the
         pooled gradient through the arg-max taps instead of a materialised d(y).
+        `defer_norm`: the caller hands y to conv_unit_pair, which may take over the normalise pass (_DeferredNorm); where
+        the unit qualifies, the pass is held back until something asks for y's address.
         Validation and dispatch: grouped -> depthwise -> pointwise -> the general kernels."""
         conv, bn_spec = self._specs(conv, norm)
         relu = int(relu)  # activation code: 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 SiLU, 4 GELU (include/vt_amd.h)
@@ -835,8 +890,18 @@ class Builder:
         # running statistics and leaves them untouched, like nn.BatchNorm2d)
         unit_training = bn_spec.training if has_bn else self.training
         fused = has_bn and not unit_training and not track and not generic_act
-        y = out if out is not None else self.act(x.B, Ho, Wo, Cout, name + ".y")
+        # (a training-mode BatchNorm with activation code < 2, no residual, no pool, no SyncBatchNorm, finalize-in-apply on,
+        #  a tensor beyond the memory-side cache; see pw_fold_min_mb)
+        defer = (defer_norm and has_bn and unit_training and not fused and not generic_act and residual is None and
+                 out is None and pool_out is None and wpack is None and not self.bn_sync and self.bn_fin_apply and
+                 self.pointwise and not self.deterministic and dt == N.VT_BF16 and
+                 x.B * Ho * Wo * Cout * _ESIZE[dt] >= self.pw_fold_min_mb * 1e6)
+        if defer:  # y has no place in the arena until something reads it
+            y = TRef(Buf(ARENA, -1, x.B * Ho * Wo * Cout * _ESIZE[dt], name + ".y"), x.B, Ho, Wo, Cout, Cout, 0, dt)
+        else:
+            y = out if out is not None else self.act(x.B, Ho, Wo, Cout, name + ".y")
         u = _ConvUnit(conv, relu, x, y, residual, name, self.tag, wptr, wpack, ldw)
+        u.defer = defer
         u.stem_fused = stem_fused = (
             track and u.padded and has_bn and not fused and residual is None and not generic_act and
             not x.needs_grad and w.requires_grad and dt == N.VT_BF16 and Cout == 32 and k == 3 and s == 1 and
@@ -921,6 +986,9 @@ class Builder:
             stats = self.zeroed_f32(N.stat_floats(y.C), "stats")
             fin_fwd = self.bn_fin_apply and not self.bn_sync and relu < 2 and pool_out is None
             self._conv(u, z, stats=stats)
+            if u.defer:
+                y.buf.deferred = _DeferredNorm(self, u, stats)
+                return
             if not fin_fwd:
                 bn.finalize(stats, y.M)
         else:
@@ -1017,15 +1085,21 @@ class Builder:
         plain = pool_grad is None and dt == N.VT_BF16 and relu < 2
         rec = self._last_dgrad.get(id(dy.buf)) if (self.fuse_bnred and plain and self._cur is self.bwd) else None
         fused_red = rec is not None and rec[1] == dy.coff and rec[2] == dy.coff + dy.C and any(o is rec[0] for o in self.bwd)
+        # (the launch that wrote the whole of d(y) also formed this unit's sums, and nothing has written d(y) since)
+        pre = self._gs(u.y).bn_sums if (plain and dy.buf is self._gs(u.y).gbuf and (dy.coff, dy.C) == (u.y.coff, u.y.C)) else None
+        if pre is not None:
+            fused_red = True
         one_launch = self.bn_bwd_fused and not fused_red and plain and not self.bn_sync
         sums, bcoef, dz = bn.bwd_buffers(u.y, u.name + ".dz")
+        if pre is not None:
+            sums = pre
         if one_launch:
             sync = self.zeroed_f32(4, "bwdsync")
             self.emit(N.OP_BN_BWD_FUSED,
                       [dy.addr(), z.addr(), *bn.cp, self.bp(sums), self.bp(sync), *bn.grads(), self.bp(bcoef), dz.addr()],
                       [dy.ld, z.ld, dz.ld, dz.C, relu, dt, int(bn.spec.training)], [M, M * self.bn_world, 1.0 / self.bn_world])
             return dz
-        if fused_red:
+        if fused_red and pre is None:
             # d(y) came out of ONE data-gradient launch and nothing was added to it since: that launch also forms
             # this unit's backward sums (the op is patched in place: ptr dz w dy | z scale shift mean invstd sums)
             fop = rec[0]
@@ -1242,13 +1316,31 @@ class Builder:
                for sp, c, o in zip(specs, Cs, offs)]
         wps = [self.pref(c.weight, mirror=True) for c in convs]
         pad2 = lambda v, fill=None: list(v) + [fill] * (2 - len(v))
-        head_i = [K, G, int(relu)] + pad2(Cs, 0) + [x.ld] + pad2([K] * G, 0)
+        # the producer fold: x is a deferred output that this launch reads whole and whose filter gradient stays in the
+        # kernel -- the passes read the producer's pre-activation and normalise it as they load (ptr[20]: its coefficient
+        # rows, i[20]: its activation code), and the statistics pass finalizes its BatchNorm (ptr[5..10], f[1..3])
+        prod = x.buf.deferred
+        if prod is not None and not (mode == 2 and unit_training and not self.bn_sync and x.coff == 0 and
+                                     x.ld == x.C == prod.u.y.C and not prod.finalized):
+            prod = None
+        xs = prod.u.z if prod is not None else x  # the tensor the passes read
+        xa = xs.addr()  # (a deferred x that is not folded is materialised here)
+        fold_p = lambda ptrs: ptrs + [None] * (20 - len(ptrs)) + [prod.u.bn.cp[0]] if prod is not None else ptrs
+        fold_i = lambda ints: ints + [0] * (20 - len(ints)) + [prod.u.relu] if prod is not None else ints
+        head_i = [K, G, int(relu)] + pad2(Cs, 0) + [xs.ld] + pad2([K] * G, 0)
         # the finalize step of every group inside the apply passes (vt_pw_fwd_apply_finalize / vt_pw_bwd_apply_finalize)
         pw_fin = self.bn_fin_apply and not self.bn_sync and Ntot <= 128
         fin_p = []
         if unit_training:
             stats = [self.zeroed_f32(N.stat_floats(c), "stats") for c in Cs]
-            self.emit(N.OP_PW_STATS, [x.addr(), *pad2(wps), *pad2([self.bp(s_) for s_ in stats])], head_i, [M])
+            if prod is not None:
+                pbn = prod.u.bn
+                self.emit(N.OP_PW_STATS, fold_p([xa, *pad2(wps), *pad2([self.bp(s_) for s_ in stats]), self.bp(prod.stats),
+                                                 *pbn.params, pbn.nbt]),
+                          fold_i(head_i), [M, M * self.bn_world, pbn.spec.eps, pbn.spec.momentum])
+                prod.finalized = True
+            else:
+                self.emit(N.OP_PW_STATS, [xa, *pad2(wps), *pad2([self.bp(s_) for s_ in stats])], head_i, [M])
             for bn, st in zip(bns, stats):
                 if pw_fin:
                     fin_p += [self.bp(st), *bn.params, bn.nbt]
@@ -1258,13 +1350,13 @@ class Builder:
             for bn in bns:
                 bn.eval_coeffs()
         ress = [sp[3] for sp in specs]
-        apply_p = [x.addr(), *pad2(wps), self.bp(coef), *pad2([y.addr() for y in ys]), *pad2([_addr(r) for r in ress])]
+        apply_p = [xa, *pad2(wps), self.bp(coef), *pad2([y.addr() for y in ys]), *pad2([_addr(r) for r in ress])]
         apply_i = head_i + pad2([y.ld for y in ys], 0) + pad2([_ld(r) for r in ress], 0)
         if fin_p:
             epsmom = [v for bn in bns for v in (bn.spec.eps, bn.spec.momentum)]
-            self.emit(N.OP_PW_APPLY_FIN, apply_p + fin_p, apply_i, [M, M * self.bn_world] + epsmom)
+            self.emit(N.OP_PW_APPLY_FIN, fold_p(apply_p + fin_p), fold_i(apply_i), [M, M * self.bn_world] + epsmom)
         else:
-            self.emit(N.OP_PW_APPLY, apply_p, apply_i, [M])
+            self.emit(N.OP_PW_APPLY, fold_p(apply_p), fold_i(apply_i), [M])
         if self.need_grad:
             tag = self.tag
 
@@ -1282,8 +1374,8 @@ class Builder:
                         self.grad_add(ress[g], dys[g])
                 sums = [self.zeroed_f32(N.stat_floats(c), "bwdsums") for c in Cs]
                 dy_p, dy_ld = pad2([d.addr() for d in dys]), pad2([d.ld for d in dys], 0)
-                self.emit(N.OP_PW_REDUCE, [x.addr(), *pad2(wps), self.bp(coef), *dy_p, *pad2([self.bp(s_) for s_ in sums])],
-                          head_i + dy_ld, [M])
+                self.emit(N.OP_PW_REDUCE, fold_p([xa, *pad2(wps), self.bp(coef), *dy_p, *pad2([self.bp(s_) for s_ in sums])]),
+                          fold_i(head_i + dy_ld), [M])
                 bcoefs = [self.f32(3 * c, "bwdcoef") for c in Cs]
                 bfin_p = []
                 for bn, sm, bc in zip(bns, sums, bcoefs):
@@ -1292,17 +1384,23 @@ class Builder:
                     else:
                         bn.bwd_finalize(sm, bc, M)
                 gx, res = self.grad_target(x)
+                # the only writer of the producer's d(y) (no addend, nothing left to add behind it): its sums too
+                psums = None
+                if prod is not None and self.pw_fold_bnred and res is None and self._deferred_flush is None:
+                    psums = self.zeroed_f32(N.stat_floats(K), "bwdsums")
+                fold_b = lambda ptrs: fold_p(ptrs) + [self.bp(psums)] if psums is not None else fold_p(ptrs)
                 want_dw = [c.weight.requires_grad for c in convs]
                 dws = [self.pgrad(c.weight) if (mode == 2 and w_) else None for c, w_ in zip(convs, want_dw)]
                 dzs = [self.act(x.B, x.H, x.W, c, sp[5] + ".dz") if (mode == 1 and w_) else None
                        for c, sp, w_ in zip(Cs, specs, want_dw)]
                 self.emit(N.OP_PW_BWD_FIN if bfin_p else N.OP_PW_BWD,
-                          [x.addr(), *pad2(wps), self.bp(coef), *dy_p, *pad2([self.bp(b_) for b_ in bcoefs]), gx.addr(),
-                           _addr(res), *pad2(dws), *pad2([_addr(d) for d in dzs]), *bfin_p],
-                          head_i + dy_ld + [gx.ld, _ld(res)] + pad2([K] * G, 0) + pad2([_ld(d) for d in dzs], 0) +
-                          [int(unit_training)],
+                          fold_b([xa, *pad2(wps), self.bp(coef), *dy_p, *pad2([self.bp(b_) for b_ in bcoefs]), gx.addr(),
+                                  _addr(res), *pad2(dws), *pad2([_addr(d) for d in dzs]), *bfin_p]),
+                          fold_i(head_i + dy_ld + [gx.ld, _ld(res)] + pad2([K] * G, 0) + pad2([_ld(d) for d in dzs], 0) +
+                                 [int(unit_training)]),
                           [M, M * self.bn_world, 1.0 / self.bn_world])
                 self.grad_written(x)
+                self._gs(x).bn_sums = psums
                 if mode == 1 and any(d is not None for d in dzs):
                     # the filter gradient does not fit the kernel's accumulators: dz was written, the usual kernel takes it
                     self.emit(N.OP_FORK)

@@ -82,6 +82,8 @@ class Program:
         self.outs = list(outs)
         self.seeds = list(seeds)
         self.dtype = b.dtype
+        for t in self.outs:
+            t.addr()  # (a returned map whose normalise pass was deferred is materialised: engine._DeferredNorm)
         top = E._round_up(b.arena_top, E.ALIGN)
         self.zf_off, self.zf_bytes = top, b.zf_top
         top = E._round_up(top + b.zf_top, E.ALIGN)
