@@ -240,6 +240,36 @@ int vt_token_select_fwd(const void* x, int32_t ldx, void* out, int32_t ldo, int3
 int vt_token_select_bwd(const void* dout, int32_t lddo, void* dx, int32_t ldx, int32_t accumulate, int32_t B, int32_t T,
                         int32_t t0, int32_t C, int32_t dtype, void* stream);
 
+/* Shifted-window attention with a learned relative-position bias (Swin: reference backbones/swin.py:32-86 -- roll, window
+ * partition, MHA with attn_bias = table[index] (+ the -100 region mask), un-partition, roll back), vt_window_attention.hip.
+ * Q, K, V, O and their gradients are [B][H][W][heads * head_dim] pixel-major rows of an NHWC map with a pixel stride each (a
+ * multiple of 8 (bf16) / 4 (f32)); head h is the channel slice [h head_dim, (h + 1) head_dim), so q | k | v may be channel
+ * slices of one [B][H][W][3 C] buffer.  The partition and both rolls are index arithmetic in the loads and stores
+ * (vt_window_index.h): token t = i ws + j of window (wy, wx) is pixel ((wy ws + i + shift) mod H, (wx ws + j + shift) mod W),
+ * and o goes back to that pixel; no map is gathered, rolled or copied.  `table` is the f32 master [heads][(2 ws - 1)^2], read
+ * at (i_q - i_k + ws - 1)(2 ws - 1) + (j_q - j_k + ws - 1); with shift > 0, -100.0 is added where query and key lie in
+ * different regions of the rolled map (3 per axis: [0, n - ws), [n - ws, n - shift), [n - shift, n)).
+ * head_dim is 32, ws^2 <= 64 (a window is one 64-row tile; ws = 14 is VT_ERR_UNSUPPORTED), 0 <= shift < ws, H and W
+ * multiples of ws (VT_ERR_INVALID otherwise).
+ *   vt_win_attn_fwd:  o = softmax(scale q k^T + bias + mask) v per (window, head), one workgroup each;
+ *                     lse[B][heads][H W] (f32, at the pixel) = the log-sum-exp of the row.  bf16: mfma_f32_16x16x32_bf16 for
+ *                     both products, softmax in f32 with the row maximum subtracted after bias and mask; f32: exact f32 FMA.
+ *   vt_win_attn_bwd:  dq, dk, dv, dtable (each may be NULL) in ONE kernel per (window, head): P and dS = P o (dout v^T - delta)
+ *                     are formed once, delta = rowsum(dout o) inside the kernel.  dtable[h][idx] += the sum over images,
+ *                     windows and (q, k) pairs with that index of dS (the gradient of the pre-softmax score, unscaled):
+ *                     every workgroup stores its share into `scratch` (vt_win_attn_bwd_scratch_bytes) and a second kernel
+ *                     adds the shares in a fixed order.  No atomics: bit-identical from run to run.  `scratch` is read and
+ *                     checked only where dtable is given; with dtable NULL it may be NULL. */
+int vt_win_attn_fwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv, void* o, int32_t ldo,
+                    float* lse, const float* table, float scale, int32_t B, int32_t H, int32_t W, int32_t heads, int32_t head_dim,
+                    int32_t ws, int32_t shift, int32_t dtype, void* stream);
+int64_t vt_win_attn_bwd_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t heads, int32_t ws);
+int vt_win_attn_bwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv, const void* o,
+                    int32_t ldo, const void* dout, int32_t lddo, const float* lse, const float* table, void* dq, int32_t lddq,
+                    void* dk, int32_t lddk, void* dv, int32_t lddv, float* dtable, void* scratch, int64_t scratch_bytes,
+                    float scale, int32_t B, int32_t H, int32_t W, int32_t heads, int32_t head_dim, int32_t ws, int32_t shift,
+                    int32_t dtype, void* stream);
+
 /* Filter gradient: dw[n][t][c] += sum_pixels dz(pix,n) * x_gathered(pix,t,c),
  * fp32 accumulation straight into the (channels_last) .grad of the weight.
  * `d` is the forward descriptor (ldy = pixel stride of dz).  Replaces the
@@ -699,6 +729,8 @@ enum vt_op_kind {
     VT_OP_VIT_TOKENS_BWD,    /* vt_vit_tokens_bwd */
     VT_OP_TOKEN_SELECT_FWD,  /* vt_token_select_fwd */
     VT_OP_TOKEN_SELECT_BWD,  /* vt_token_select_bwd */
+    VT_OP_WIN_ATTN_FWD,      /* vt_win_attn_fwd */
+    VT_OP_WIN_ATTN_BWD,      /* vt_win_attn_bwd */
     VT_OP_KIND_END
 };
 

@@ -255,6 +255,13 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
             return vt_token_select_fwd(P[0], I[0], P[1], I[1], I[2], I[3], I[4], I[5], I[6], st);
         case VT_OP_TOKEN_SELECT_BWD:  // ptr: dout dx | i: lddo ldx accumulate B T t0 C dtype
             return vt_token_select_bwd(P[0], I[0], P[1], I[1], I[2], I[3], I[4], I[5], I[6], I[7], st);
+        case VT_OP_WIN_ATTN_FWD:  // ptr: q k v o lse table | i: ldq ldk ldv ldo B H W heads head_dim ws shift dtype | f: scale
+            return vt_win_attn_fwd(P[0], I[0], P[1], I[1], P[2], I[2], P[3], I[3], (float*)P[4], (const float*)P[5], (float)F[0], I[4],
+                                   I[5], I[6], I[7], I[8], I[9], I[10], I[11], st);
+        case VT_OP_WIN_ATTN_BWD:  // ptr: q k v o dout lse table dq dk dv dtable scratch | i: ldq ldk ldv ldo lddo lddq lddk lddv B H W heads head_dim ws shift dtype | f: scale, scratch bytes
+            return vt_win_attn_bwd(P[0], I[0], P[1], I[1], P[2], I[2], P[3], I[3], P[4], I[4], (const float*)P[5], (const float*)P[6],
+                                   P[7], I[5], P[8], I[6], P[9], I[7], (float*)P[10], P[11], (int64_t)F[1], (float)F[0], I[8], I[9],
+                                   I[10], I[11], I[12], I[13], I[14], I[15], st);
         case VT_OP_BN_FIN_APPLY:  // ptr: stats gamma beta rm rv nbt scale shift mean invstd z residual y | i: C ldz ldr ldy relu dtype | f: count eps momentum M
             return vt_bn_finalize_apply((const float*)P[0], I[0], F[0], (const float*)P[1], (const float*)P[2], (float)F[1], (float)F[2],
                                         (float*)P[3], (float*)P[4], (int64_t*)P[5], (float*)P[6], (float*)P[7], (float*)P[8],

@@ -123,7 +123,9 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_VIT_TOKENS_BWD,
     OP_TOKEN_SELECT_FWD,
     OP_TOKEN_SELECT_BWD,
-) = range(1, 66)
+    OP_WIN_ATTN_FWD,
+    OP_WIN_ATTN_BWD,
+) = range(1, 68)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -173,6 +175,8 @@ OP_NAMES = {
     OP_VIT_TOKENS_BWD: "vit_tokens_bwd",
     OP_TOKEN_SELECT_FWD: "token_select_fwd",
     OP_TOKEN_SELECT_BWD: "token_select_bwd",
+    OP_WIN_ATTN_FWD: "win_attn_fwd",
+    OP_WIN_ATTN_BWD: "win_attn_bwd",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -299,6 +303,10 @@ SYMBOLS = {
     "vt_attn_bwd_scratch_bytes": (_i64, [_i32, _i32, _i32]),
     "vt_attn_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64,
                            _f32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vt_win_attn_fwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _f32] + [_i32] * 8 + [_vp]),
+    "vt_win_attn_bwd_scratch_bytes": (_i64, [_i32] * 5),
+    "vt_win_attn_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp,
+                               _vp, _i64, _f32] + [_i32] * 8 + [_vp]),
     "vt_vit_tokens_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_vit_tokens_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_token_select_fwd": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -112,6 +112,10 @@ class ParamStore:
     OIHW shapes are exactly the reference's, base.py:23-25), but their storage becomes
     a slice of one flat tensor; 4-D conv weights are held channels_last, i.e.
     physically [Cout][kh][kw][Cin], which is the filter image the kernels read.
+
+    Non-persistent buffers (register_buffer(..., persistent=False)) of ANY module are left out: they get no slot, are not
+    moved to the device and no launch may read them.  Today those are the index / mask tables of the Swin CPU path, which
+    the window attention kernels recompute.  A launch that needs a buffer's values needs a persistent buffer.
     """
 
     def __init__(self, root: nn.Module, order_key=None):
@@ -139,6 +143,8 @@ class ParamStore:
             for name, b in mod._buffers.items():
                 if b is None or id(b) in seen:
                     continue
+                if name in mod._non_persistent_buffers_set:
+                    continue  # derived index / mask tables of the CPU path (Swin): no launch reads them, they stay as they are
                 seen.add(id(b))
                 (fbufs if b.is_floating_point() else ibufs).append((mod, name, b))
         if self.order_key is not None:
@@ -561,6 +567,7 @@ class Builder:
         self._deferred_flush: Optional[TRef] = None  # grad_target -> grad_written
         self._tok_slabs: dict[int, Buf] = {}  # _token_slab
         self._attn_scratch: dict[int, Buf] = {}  # attention: the backward's delta, per size
+        self._win_scratch: dict[int, Buf] = {}  # window attention: the per-window shares of the table gradient, per size
 
     # -- memory -----------------------------------------------------------------
     def alloc(self, nbytes: int, name: str = "") -> Buf:
@@ -1716,9 +1723,15 @@ class Builder:
         if rows % _EPC[dt]:
             raise NotImplementedError(f"{name}: {cin} * {p} * {p} = {rows} values per patch must be a multiple of {_EPC[dt]} "
                                       f"for dtype {dt}")
+        patches = self._patchify(x, cin, p, name)
+        return self.conv_unit(patches, ConvSpec(1, 1, 0, 1, 1, rows, conv.out_channels, conv.weight, conv.bias), None, 0, name=name)
+
+    def _patchify(self, x: TRef, cin: int, p: int, name: str) -> TRef:
+        """the p x p patches of the first `cin` channels of x as rows in (py, px, c) order: [B, H, W, C] -> [B, H/p, W/p,
+        cin p p] (vt_patchify_fwd); backward scatters them back (vt_patchify_bwd)"""
         self.tag += 1
-        B, H, W = x.B, x.H, x.W
-        patches = self.act(B, H // p, W // p, rows, name + ".patches", needs_grad=x.needs_grad)
+        B, H, W, dt = x.B, x.H, x.W, self.dtype
+        patches = self.act(B, H // p, W // p, cin * p * p, name + ".patches", needs_grad=x.needs_grad)
         self.emit(N.OP_PATCHIFY_FWD, [x.addr(), patches.addr()], [x.ld, patches.ld, B, H, W, cin, p, dt])
         if self.need_grad and x.needs_grad:
 
@@ -1728,7 +1741,7 @@ class Builder:
                 self.grad_written(x)
 
             self._node(patches, bwd)
-        return self.conv_unit(patches, ConvSpec(1, 1, 0, 1, 1, rows, conv.out_channels, conv.weight, conv.bias), None, 0, name=name)
+        return patches
 
     def _token_slab(self, nbytes: int) -> Buf:
         """slab scratch of the token filter gradients: one per size, shared by every layer of that shape (their launches
@@ -1837,6 +1850,75 @@ class Builder:
 
             self._node(o, bwd)
         return o
+
+    # -- Swin pieces (reference backbones/swin.py:32-124): vt_window_attention.hip ---------------------------------
+    def window_attention(self, q: TRef, k: TRef, v: TRef, n_heads: int, table: nn.Parameter, ws: int, shift: int,
+                         name: str = "window_attention") -> TRef:
+        """softmax(q k^T / sqrt(head_dim) + table[relative index] (+ the -100 region mask where shift > 0)) v inside the
+        ws x ws windows of [B, H, W, C] maps, cyclically shifted by `shift` (vt_win_attn_fwd).  The partition and both rolls
+        are index arithmetic of the kernel: q, k, v and o are maps in un-rolled pixel order, head h a channel slice, and q,
+        k, v may be channel slices of one buffer.  `table` is the (1, n_heads, (2 ws - 1)^2) parameter, read as the f32
+        master.  Backward: one vt_win_attn_bwd writes d(q), d(k), d(v) into the gradient buffers of the three producers
+        and adds the table's gradient, summed in a fixed order through a scratch that every layer of the same size shares:
+        no atomics, the same launch under `deterministic`."""
+        dt = self.dtype
+        if not (q.same_geom(k) and q.same_geom(v)):
+            raise ValueError(f"{name}: q, k and v are [B, H, W, C] maps of one geometry")
+        if n_heads <= 0 or q.C % n_heads:
+            raise ValueError(f"{name}: {q.C} channels do not split into n_heads={n_heads}")
+        D = q.C // n_heads
+        if D != 32:
+            raise NotImplementedError(f"{name}: head_dim = {q.C} / n_heads={n_heads} = {D}: the window attention kernels "
+                                      "implement head_dim 32")
+        if ws * ws > 64:
+            raise NotImplementedError(f"{name}: window_size={ws}: a window of {ws * ws} tokens does not fit the kernels' 64-row "
+                                      "tile (window_size <= 8)")
+        if q.H % ws or q.W % ws or not 0 <= shift < ws:
+            raise ValueError(f"{name}: a {q.H}x{q.W} map, window_size={ws}, shift={shift}")
+        if table.numel() != n_heads * (2 * ws - 1) ** 2:
+            raise ValueError(f"{name}: the table holds {table.numel()} values, {n_heads} heads x (2 * {ws} - 1)^2 are expected")
+        if any(t.logical_c != t.C for t in (q, k, v)) or q.C % _EPC[dt]:
+            raise NotImplementedError(f"{name}: {q.C} channels must be a multiple of {_EPC[dt]} for dtype {dt}")
+        self.tag += 1
+        B, H, W, scale = q.B, q.H, q.W, D ** -0.5
+        o = self.act(B, H, W, q.C, name + ".o")
+        lse = self.f32(B * n_heads * H * W, name + ".lse")
+        tb = self.pref(table)
+        geom = [B, H, W, n_heads, D, ws, shift, dt]
+        self.emit(N.OP_WIN_ATTN_FWD, [q.addr(), k.addr(), v.addr(), o.addr(), self.bp(lse), tb], [q.ld, k.ld, v.ld, o.ld, *geom],
+                  [scale])
+        if self.need_grad and (q.needs_grad or k.needs_grad or v.needs_grad or self.pgrad(table) is not None):
+
+            def bwd(do):
+                nbytes = int(N.lib().vt_win_attn_bwd_scratch_bytes(B, H, W, n_heads, ws))
+                if nbytes not in self._win_scratch:  # (one per size: the launches follow each other on one stream)
+                    self._win_scratch[nbytes] = self.alloc(nbytes, "win_attn_dtable_shares")
+                gs = []
+                for t in (q, k, v):
+                    g = None
+                    if t.needs_grad:
+                        g, res = self.grad_target(t)
+                        assert res is None and self._deferred_flush is None, "q, k and v have one consumer, the attention"
+                    gs.append(g)
+                self.emit(N.OP_WIN_ATTN_BWD,
+                          [q.addr(), k.addr(), v.addr(), o.addr(), do.addr(), self.bp(lse), tb, *[_addr(g) for g in gs],
+                           self.pgrad(table), self.bp(self._win_scratch[nbytes])],
+                          [q.ld, k.ld, v.ld, o.ld, do.ld, *[_ld(g) for g in gs], *geom], [scale, nbytes])
+
+            self._node(o, bwd)
+        return o
+
+    def patch_merging(self, x: TRef, norm: nn.LayerNorm, reduction: nn.Linear, name: str = "patch_merging") -> TRef:
+        """Swin's PatchMerging: the 2 x 2 neighbourhoods of [B, H, W, C] as [B, H/2, W/2, 4 C] rows in (dy, dx, c) order (the
+        patch gather with p = 2 -- the order of the reference's view / transpose / flatten), LayerNorm(4 C), then the
+        bias-free Linear(4 C, 2 C) as a 1x1 convolution."""
+        if x.logical_c != x.C or x.H % 2 or x.W % 2:
+            raise ValueError(f"{name}: a {x.H}x{x.W} map of {x.logical_c} channels does not merge 2 x 2")
+        if reduction.bias is not None or reduction.in_features != 4 * x.C:
+            raise NotImplementedError(f"{name}: the reduction is a bias-free Linear({4 * x.C}, .)")
+        g = self._patchify(x, x.C, 2, name)
+        n = self.layer_norm(g, norm, name=name + ".norm")
+        return self.conv_unit(n, ConvSpec.from_linear(reduction), None, 0, name=name + ".reduction")
 
     def vit_tokens(self, embed: TRef, pe: nn.Parameter, cls_token: Optional[nn.Parameter], name: str = "tokens") -> TRef:
         """the token map of a ViT: [B, gh, gw, C] patch embeddings + pe, behind the class token where there is one ->

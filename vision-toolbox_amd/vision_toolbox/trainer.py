@@ -5,7 +5,7 @@ training_step, :111-169 three-group SGD, configs/base.yaml:16-23 DDP) is here ON
 program per rank:
 
     images -> backbone -> global avg-pool -> linear head -> label-smoothing CE
-              (include_pool=False, ConvNeXt / MLPMixer / ViT: the backbone's own pooled + normalised (B, C) output -> linear head)
+              (include_pool=False, ConvNeXt / MLPMixer / ViT / SwinTransformer: the backbone's own pooled + normalised (B, C) output -> linear head)
            -> explicit backward into a persistent flat f32 gradient buffer
            -> bucketed gradient all-reduce (RCCL over xGMI); each bucket is issued as soon
               as the backward segment that completes it has been enqueued
@@ -164,12 +164,14 @@ class TrainStep:
         if not self.include_pool:
             from .backbones.convnext import ConvNeXt
             from .backbones.mlp_mixer import MLPMixer
+            from .backbones.swin import SwinTransformer
             from .backbones.vit import ViT
 
             # classifier.py:59-63 with include_pool=False is nn.Sequential(backbone, nn.Linear): right only where
             # forward() already returns the pooled (B, C) vector; a map-returning family would feed nn.Linear a 4-D map
-            if not isinstance(backbone, (ConvNeXt, MLPMixer, ViT)):
-                raise ValueError(f"include_pool=False needs a backbone whose forward returns (B, C) (ConvNeXt, MLPMixer, ViT); "
+            if not isinstance(backbone, (ConvNeXt, MLPMixer, ViT, SwinTransformer)):
+                raise ValueError(f"include_pool=False needs a backbone whose forward returns (B, C) (ConvNeXt, MLPMixer, ViT, "
+                                 f"SwinTransformer); "
                                  f"{type(backbone).__name__} returns a feature map")
         self.device = torch.device(device if device is not None else "cuda")
         self.plan_only = plan_only  # build launch lists / bucket plan without a GPU (host-logic tests)
@@ -233,6 +235,12 @@ class TrainStep:
             if isinstance(backbone, ViT):
                 raise NotImplementedError("exchange='sharded' with a ViT: its position embedding, class token and layer scales "
                                           "are read in f32 outside the head bucket (use exchange='allreduce')")
+            from .backbones.swin import SwinTransformer
+
+            # (... and for a Swin's relative-position tables and layer scales)
+            if isinstance(backbone, SwinTransformer):
+                raise NotImplementedError("exchange='sharded' with a SwinTransformer: its relative-position tables and layer "
+                                          "scales are read in f32 outside the head bucket (use exchange='allreduce')")
         # who issues the collectives: "torch" = torch.distributed calls between segments of the launch lists (any
         # backend: gloo in the CPU tests); "rccl" = the library's own RCCL communicator (vt_comm_init), the collectives are
         # OPS of the lists (VT_OP_STAT_SYNC in front of every BatchNorm finalize, FORK + VT_OP_ALLREDUCE on the
