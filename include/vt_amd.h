@@ -270,6 +270,53 @@ int vt_win_attn_bwd(const void* q, int32_t ldq, const void* k, int32_t ldk, cons
                     float scale, int32_t B, int32_t H, int32_t W, int32_t heads, int32_t head_dim, int32_t ws, int32_t shift,
                     int32_t dtype, void* stream);
 
+/* The two attention forms of CaiT (reference backbones/cait.py:16-51) and the token bookkeeping of its class-attention
+ * stage, vt_talking_attention.hip.  Layout as vt_attn_*: [B][L][heads * head_dim] token-major rows with a row stride each (a
+ * multiple of 8 (bf16) / 4 (f32)), head h is a channel slice, q | k | v may be slices of one buffer.
+ * Talking heads, per image, s = scale, Wl / Ww the [heads][heads] f32 masters of the two 1x1 mixes, bl / bw their [heads]
+ * biases (may be NULL = 0):
+ *     A_h = s q_h k_h^T    M_g = sum_h Wl[g,h] A_h + bl[g]    P_g = softmax_j M_g    R_g = sum_h Ww[g,h] P_h + bw[g]
+ *     O_g = R_g v_g        lse[B][heads][L] (f32) = logsumexp_j M_g
+ * head_dim is 48 and 1 <= heads <= 16 (VT_ERR_UNSUPPORTED otherwise), L is arbitrary.  The L x L planes never reach memory:
+ * a workgroup owns a 16-row tile of an image and ALL heads, a thread owns one (query, key) pair and mixes the heads in
+ * registers; two passes over the key tiles (lse of M, then the normalised P mixed to R and R v).  f32: exact f32 FMA.  bf16
+ * forward: mfma_f32_16x16x32_bf16 (second k-step zero-padded from 48) for the scores, the mixes on the accumulator tiles, R
+ * rounded to bf16 as the operand of mfma_f32_16x16x16_bf16 for R v.  The backward computes in f32 FMA in both dtypes (bf16
+ * operands are widened when staged: the loads and stores are its only rounding points).
+ *   vt_talk_attn_bwd: dq, dk, dv, dwl, dbl, dww, dbw (each may be NULL; the parameter gradients accumulate with += in f32)
+ *                     from q, k, v, dout, lse and the parameters; P is recomputed from lse.  delta_h = sum_j dP_h P_h (not
+ *                     rowsum(dout o)) takes a pass of its own over the keys.  One kernel owns query tiles (delta, dq and the
+ *                     workgroup's share of the parameter gradients), one owns key tiles (dk, dv); a third adds the shares in
+ *                     a fixed order.  No atomics: bit-identical from run to run.
+ *                     scratch bytes = 4 (B heads L + B ceil(L / 16) (2 heads^2 + 2 heads)): delta, then the shares.
+ * Class attention: plain softmax attention of ONE query row per image.  q, o, dout, dq are [B][heads * head_dim] rows; k, v,
+ * dk, dv are [B][Lk][heads * head_dim]; lse is [B][heads].  head_dim 32, 48 or 64.  One wave per (image, head), vector FMA,
+ * k and v read once; the backward (delta = dout . o) writes every row of dk and dv with plain stores, no scratch, no
+ * atomics; dq, dk, dv may each be NULL, not all.
+ *   vt_token_prepend_fwd: out[b][0] = first[b] ([B][C] activation) or first_param ([C] f32 master, broadcast); exactly one
+ *                         of the two is non-NULL; out[b][1 + t] = x[b][t].  x is [B][T][C], out [B][1 + T][C].
+ *   vt_token_prepend_bwd: dx[b][t] (+)= dout[b][1 + t] (`accumulate`), dfirst[b] = dout[b][0] or dfirst_param += sum_b
+ *                         dout[b][0] in image order; each may be NULL, not all. */
+int vt_talk_attn_fwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv, void* o, int32_t ldo,
+                     float* lse, const float* wl, const float* bl, const float* ww, const float* bw, float scale, int32_t B,
+                     int32_t heads, int32_t L, int32_t head_dim, int32_t dtype, void* stream);
+int64_t vt_talk_attn_bwd_scratch_bytes(int32_t B, int32_t heads, int32_t L);
+int vt_talk_attn_bwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv, const void* dout,
+                     int32_t lddo, const float* lse, const float* wl, const float* bl, const float* ww, const float* bw, void* dq,
+                     int32_t lddq, void* dk, int32_t lddk, void* dv, int32_t lddv, float* dwl, float* dbl, float* dww, float* dbw,
+                     void* scratch, int64_t scratch_bytes, float scale, int32_t B, int32_t heads, int32_t L, int32_t head_dim,
+                     int32_t dtype, void* stream);
+int vt_cls_attn_fwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv, void* o, int32_t ldo,
+                    float* lse, float scale, int32_t B, int32_t heads, int32_t Lk, int32_t head_dim, int32_t dtype, void* stream);
+int vt_cls_attn_bwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv, const void* o, int32_t ldo,
+                    const void* dout, int32_t lddo, const float* lse, void* dq, int32_t lddq, void* dk, int32_t lddk, void* dv,
+                    int32_t lddv, float scale, int32_t B, int32_t heads, int32_t Lk, int32_t head_dim, int32_t dtype,
+                    void* stream);
+int vt_token_prepend_fwd(const void* x, int32_t ldx, const void* first, int32_t ldf, const float* first_param, void* out,
+                         int32_t ldo, int32_t B, int32_t T, int32_t C, int32_t dtype, void* stream);
+int vt_token_prepend_bwd(const void* dout, int32_t lddo, void* dx, int32_t ldx, int32_t accumulate, void* dfirst, int32_t ldf,
+                         float* dfirst_param, int32_t B, int32_t T, int32_t C, int32_t dtype, void* stream);
+
 /* Filter gradient: dw[n][t][c] += sum_pixels dz(pix,n) * x_gathered(pix,t,c),
  * fp32 accumulation straight into the (channels_last) .grad of the weight.
  * `d` is the forward descriptor (ldy = pixel stride of dz).  Replaces the
@@ -731,6 +778,12 @@ enum vt_op_kind {
     VT_OP_TOKEN_SELECT_BWD,  /* vt_token_select_bwd */
     VT_OP_WIN_ATTN_FWD,      /* vt_win_attn_fwd */
     VT_OP_WIN_ATTN_BWD,      /* vt_win_attn_bwd */
+    VT_OP_TALK_ATTN_FWD,     /* vt_talk_attn_fwd */
+    VT_OP_TALK_ATTN_BWD,     /* vt_talk_attn_bwd */
+    VT_OP_CLS_ATTN_FWD,      /* vt_cls_attn_fwd */
+    VT_OP_CLS_ATTN_BWD,      /* vt_cls_attn_bwd */
+    VT_OP_TOKEN_PREPEND_FWD, /* vt_token_prepend_fwd */
+    VT_OP_TOKEN_PREPEND_BWD, /* vt_token_prepend_bwd */
     VT_OP_KIND_END
 };
 

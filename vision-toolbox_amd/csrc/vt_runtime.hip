@@ -262,6 +262,24 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
             return vt_win_attn_bwd(P[0], I[0], P[1], I[1], P[2], I[2], P[3], I[3], P[4], I[4], (const float*)P[5], (const float*)P[6],
                                    P[7], I[5], P[8], I[6], P[9], I[7], (float*)P[10], P[11], (int64_t)F[1], (float)F[0], I[8], I[9],
                                    I[10], I[11], I[12], I[13], I[14], I[15], st);
+        case VT_OP_TALK_ATTN_FWD:  // ptr: q k v o lse wl bl ww bw | i: ldq ldk ldv ldo B heads L head_dim dtype | f: scale
+            return vt_talk_attn_fwd(P[0], I[0], P[1], I[1], P[2], I[2], P[3], I[3], (float*)P[4], (const float*)P[5], (const float*)P[6],
+                                    (const float*)P[7], (const float*)P[8], (float)F[0], I[4], I[5], I[6], I[7], I[8], st);
+        case VT_OP_TALK_ATTN_BWD:  // ptr: q k v dout lse wl bl ww bw dq dk dv dwl dbl dww dbw scratch | i: ldq ldk ldv lddo lddq lddk lddv B heads L head_dim dtype | f: scale, scratch bytes
+            return vt_talk_attn_bwd(P[0], I[0], P[1], I[1], P[2], I[2], P[3], I[3], (const float*)P[4], (const float*)P[5],
+                                    (const float*)P[6], (const float*)P[7], (const float*)P[8], P[9], I[4], P[10], I[5], P[11], I[6],
+                                    (float*)P[12], (float*)P[13], (float*)P[14], (float*)P[15], P[16], (int64_t)F[1], (float)F[0],
+                                    I[7], I[8], I[9], I[10], I[11], st);
+        case VT_OP_CLS_ATTN_FWD:  // ptr: q k v o lse | i: ldq ldk ldv ldo B heads Lk head_dim dtype | f: scale
+            return vt_cls_attn_fwd(P[0], I[0], P[1], I[1], P[2], I[2], P[3], I[3], (float*)P[4], (float)F[0], I[4], I[5], I[6], I[7],
+                                   I[8], st);
+        case VT_OP_CLS_ATTN_BWD:  // ptr: q k v o dout lse dq dk dv | i: ldq ldk ldv ldo lddo lddq lddk lddv B heads Lk head_dim dtype | f: scale
+            return vt_cls_attn_bwd(P[0], I[0], P[1], I[1], P[2], I[2], P[3], I[3], P[4], I[4], (const float*)P[5], P[6], I[5], P[7],
+                                   I[6], P[8], I[7], (float)F[0], I[8], I[9], I[10], I[11], I[12], st);
+        case VT_OP_TOKEN_PREPEND_FWD:  // ptr: x first first_param out | i: ldx ldf ldo B T C dtype
+            return vt_token_prepend_fwd(P[0], I[0], P[1], I[1], (const float*)P[2], P[3], I[2], I[3], I[4], I[5], I[6], st);
+        case VT_OP_TOKEN_PREPEND_BWD:  // ptr: dout dx dfirst dfirst_param | i: lddo ldx accumulate ldf B T C dtype
+            return vt_token_prepend_bwd(P[0], I[0], P[1], I[1], I[2], P[2], I[3], (float*)P[3], I[4], I[5], I[6], I[7], st);
         case VT_OP_BN_FIN_APPLY:  // ptr: stats gamma beta rm rv nbt scale shift mean invstd z residual y | i: C ldz ldr ldy relu dtype | f: count eps momentum M
             return vt_bn_finalize_apply((const float*)P[0], I[0], F[0], (const float*)P[1], (const float*)P[2], (float)F[1], (float)F[2],
                                         (float*)P[3], (float*)P[4], (int64_t*)P[5], (float*)P[6], (float*)P[7], (float*)P[8],

@@ -125,7 +125,13 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_TOKEN_SELECT_BWD,
     OP_WIN_ATTN_FWD,
     OP_WIN_ATTN_BWD,
-) = range(1, 68)
+    OP_TALK_ATTN_FWD,
+    OP_TALK_ATTN_BWD,
+    OP_CLS_ATTN_FWD,
+    OP_CLS_ATTN_BWD,
+    OP_TOKEN_PREPEND_FWD,
+    OP_TOKEN_PREPEND_BWD,
+) = range(1, 74)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -177,6 +183,12 @@ OP_NAMES = {
     OP_TOKEN_SELECT_BWD: "token_select_bwd",
     OP_WIN_ATTN_FWD: "win_attn_fwd",
     OP_WIN_ATTN_BWD: "win_attn_bwd",
+    OP_TALK_ATTN_FWD: "talk_attn_fwd",
+    OP_TALK_ATTN_BWD: "talk_attn_bwd",
+    OP_CLS_ATTN_FWD: "cls_attn_fwd",
+    OP_CLS_ATTN_BWD: "cls_attn_bwd",
+    OP_TOKEN_PREPEND_FWD: "token_prepend_fwd",
+    OP_TOKEN_PREPEND_BWD: "token_prepend_bwd",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -307,6 +319,15 @@ SYMBOLS = {
     "vt_win_attn_bwd_scratch_bytes": (_i64, [_i32] * 5),
     "vt_win_attn_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp,
                                _vp, _i64, _f32] + [_i32] * 8 + [_vp]),
+    "vt_talk_attn_fwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _f32] + [_i32] * 5 + [_vp]),
+    "vt_talk_attn_bwd_scratch_bytes": (_i64, [_i32, _i32, _i32]),
+    "vt_talk_attn_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32,
+                                _vp, _vp, _vp, _vp, _vp, _i64, _f32] + [_i32] * 5 + [_vp]),
+    "vt_cls_attn_fwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _f32] + [_i32] * 5 + [_vp]),
+    "vt_cls_attn_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _f32]
+                        + [_i32] * 5 + [_vp]),
+    "vt_token_prepend_fwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vt_token_prepend_bwd": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "vt_vit_tokens_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_vit_tokens_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_token_select_fwd": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

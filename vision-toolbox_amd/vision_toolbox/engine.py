@@ -568,6 +568,7 @@ class Builder:
         self._tok_slabs: dict[int, Buf] = {}  # _token_slab
         self._attn_scratch: dict[int, Buf] = {}  # attention: the backward's delta, per size
         self._win_scratch: dict[int, Buf] = {}  # window attention: the per-window shares of the table gradient, per size
+        self._talk_scratch: dict[int, Buf] = {}  # talking-heads attention: delta and the parameter-gradient shares, per size
 
     # -- memory -----------------------------------------------------------------
     def alloc(self, nbytes: int, name: str = "") -> Buf:
@@ -1962,6 +1963,138 @@ class Builder:
                 gx, acc = self.grad_accum_target(x)
                 self.emit(N.OP_TOKEN_SELECT_BWD, [dy.addr(), gx.addr()], [dy.ld, gx.ld, acc, x.B, x.W, t0, x.C, self.dtype])
                 self.grad_written(x)
+
+            self._node(y, bwd)
+        return y
+
+    # -- CaiT pieces (reference backbones/cait.py:16-51, 74-77): vt_talking_attention.hip -----------------------------
+    def talking_attention(self, q: TRef, k: TRef, v: TRef, n_heads: int, proj_l: nn.Conv2d, proj_w: nn.Conv2d,
+                          name: str = "talking_attention") -> TRef:
+        """talking-heads attention on token maps [B, 1, L, C]: the scores of all heads are mixed by `proj_l` (a 1x1
+        Conv2d(n_heads, n_heads)) in front of the softmax and by `proj_w` behind it (vt_talk_attn_fwd; it writes the row
+        log-sum-exp of the MIXED scores).  The mixing weights and biases are read as f32 masters in both dtypes and their
+        gradients go to the f32 gradient buffer.  Backward: one vt_talk_attn_bwd writes d(q), d(k), d(v) and adds the four
+        parameter gradients through a scratch that every layer of the same size shares; no atomics, the same launch under
+        `deterministic`."""
+        dt = self.dtype
+        if not (q.same_geom(k) and q.same_geom(v)) or q.H != 1:
+            raise ValueError(f"{name}: q, k and v are [B, 1, L, C] token maps of one geometry")
+        if n_heads <= 0 or q.C % n_heads:
+            raise ValueError(f"{name}: {q.C} channels do not split into n_heads={n_heads}")
+        D = q.C // n_heads
+        if D != 48:
+            raise NotImplementedError(f"{name}: head_dim = {q.C} / n_heads={n_heads} = {D}: the talking-heads kernels "
+                                      "implement head_dim 48")
+        if n_heads > 16:
+            raise NotImplementedError(f"{name}: n_heads={n_heads}: the talking-heads kernels hold at most 16 heads per pair")
+        for conv, what in ((proj_l, "proj_l"), (proj_w, "proj_w")):
+            if tuple(conv.weight.shape) != (n_heads, n_heads, 1, 1) or conv.bias is None:
+                raise ValueError(f"{name}: {what} is a biased 1x1 Conv2d({n_heads}, {n_heads}), its weight is "
+                                 f"{tuple(conv.weight.shape)}")
+        if any(t.logical_c != t.C for t in (q, k, v)) or q.C % _EPC[dt]:
+            raise NotImplementedError(f"{name}: {q.C} channels must be a multiple of {_EPC[dt]} for dtype {dt}")
+        self.tag += 1
+        B, L, scale = q.B, q.W, D ** -0.5
+        o = self.act(B, 1, L, q.C, name + ".o")
+        lse = self.f32(B * n_heads * L, name + ".lse")
+        mix = [proj_l.weight, proj_l.bias, proj_w.weight, proj_w.bias]
+        mp = [self.pref(p) for p in mix]
+        self.emit(N.OP_TALK_ATTN_FWD, [q.addr(), k.addr(), v.addr(), o.addr(), self.bp(lse), *mp],
+                  [q.ld, k.ld, v.ld, o.ld, B, n_heads, L, D, dt], [scale])
+        if self.need_grad and (q.needs_grad or k.needs_grad or v.needs_grad or any(self.pgrad(p) is not None for p in mix)):
+
+            def bwd(do):
+                nbytes = int(N.lib().vt_talk_attn_bwd_scratch_bytes(B, n_heads, L))
+                if nbytes not in self._talk_scratch:  # (one per size: the launches follow each other on one stream)
+                    self._talk_scratch[nbytes] = self.alloc(nbytes, "talk_attn_delta_shares")
+                gs = []
+                for t in (q, k, v):
+                    g = None
+                    if t.needs_grad:
+                        g, res = self.grad_target(t)
+                        assert res is None and self._deferred_flush is None, "q, k and v have one consumer, the attention"
+                    gs.append(g)
+                self.emit(N.OP_TALK_ATTN_BWD,
+                          [q.addr(), k.addr(), v.addr(), do.addr(), self.bp(lse), *mp, *[_addr(g) for g in gs],
+                           *[self.pgrad(p) for p in mix], self.bp(self._talk_scratch[nbytes])],
+                          [q.ld, k.ld, v.ld, do.ld, *[_ld(g) for g in gs], B, n_heads, L, D, dt], [scale, nbytes])
+
+            self._node(o, bwd)
+        return o
+
+    def class_attention(self, q: TRef, k: TRef, v: TRef, n_heads: int, name: str = "class_attention") -> TRef:
+        """softmax(q k^T / sqrt(head_dim)) v with ONE query row per image: q is [B, 1, 1, C], k and v are [B, 1, Lk, C] maps
+        (channel slices of one buffer or not), the result [B, 1, 1, C] (vt_cls_attn_fwd).  Backward: one vt_cls_attn_bwd
+        writes d(q) and every row of d(k), d(v); no scratch, no atomics."""
+        dt = self.dtype
+        if not k.same_geom(v) or k.H != 1 or (q.B, q.H, q.W, q.C) != (k.B, 1, 1, k.C):
+            raise ValueError(f"{name}: q is a [B, 1, 1, C] row per image, k and v are [B, 1, Lk, C] token maps of one geometry")
+        if n_heads <= 0 or q.C % n_heads:
+            raise ValueError(f"{name}: {q.C} channels do not split into n_heads={n_heads}")
+        D = q.C // n_heads
+        if D not in (32, 48, 64):
+            raise NotImplementedError(f"{name}: head_dim = {q.C} / n_heads={n_heads} = {D}: the class-attention kernels "
+                                      "implement head_dim 32, 48 and 64")
+        if any(t.logical_c != t.C for t in (q, k, v)) or q.C % _EPC[dt]:
+            raise NotImplementedError(f"{name}: {q.C} channels must be a multiple of {_EPC[dt]} for dtype {dt}")
+        self.tag += 1
+        B, Lk, scale = k.B, k.W, D ** -0.5
+        o = self.act(B, 1, 1, q.C, name + ".o")
+        lse = self.f32(B * n_heads, name + ".lse")
+        self.emit(N.OP_CLS_ATTN_FWD, [q.addr(), k.addr(), v.addr(), o.addr(), self.bp(lse)],
+                  [q.ld, k.ld, v.ld, o.ld, B, n_heads, Lk, D, dt], [scale])
+        if self.need_grad and (q.needs_grad or k.needs_grad or v.needs_grad):
+
+            def bwd(do):
+                gs = []
+                for t in (q, k, v):
+                    g = None
+                    if t.needs_grad:
+                        g, res = self.grad_target(t)
+                        assert res is None and self._deferred_flush is None, "q, k and v have one consumer, the attention"
+                    gs.append(g)
+                self.emit(N.OP_CLS_ATTN_BWD,
+                          [q.addr(), k.addr(), v.addr(), o.addr(), do.addr(), self.bp(lse), *[_addr(g) for g in gs]],
+                          [q.ld, k.ld, v.ld, o.ld, do.ld, *[_ld(g) for g in gs], B, n_heads, Lk, D, dt], [scale])
+
+            self._node(o, bwd)
+        return o
+
+    def token_prepend(self, x: TRef, first, name: str = "token_prepend") -> TRef:
+        """[first | x]: one row in front of the tokens of a [B, 1, T, C] map -> [B, 1, 1 + T, C] (vt_token_prepend_fwd).
+        `first` is a [B, 1, 1, C] activation or a parameter of C values (read as the f32 master and broadcast over the
+        batch).  Backward copies or accumulates the token rows into d(x) and hands row 0 to d(first), summed over the images
+        in order for a parameter (vt_token_prepend_bwd)."""
+        Cc, dt = x.C, self.dtype
+        is_param = not isinstance(first, TRef)
+        if x.H != 1 or x.logical_c != Cc:
+            raise ValueError(f"{name}: x is a [B, 1, T, C] token map")
+        if is_param and first.numel() != Cc:
+            raise ValueError(f"{name}: the first token holds {first.numel()} values for {Cc} channels")
+        if not is_param and (first.B, first.H, first.W, first.C) != (x.B, 1, 1, Cc):
+            raise ValueError(f"{name}: the first token is a [B, 1, 1, {Cc}] row per image")
+        self.tag += 1
+        B, T = x.B, x.W
+        y = self.act(B, 1, T + 1, Cc, name + ".y")
+        fa, fp = (None, self.pref(first)) if is_param else (first.addr(), None)
+        self.emit(N.OP_TOKEN_PREPEND_FWD, [x.addr(), fa, fp, y.addr()], [x.ld, 0 if is_param else first.ld, y.ld, B, T, Cc, dt])
+        if self.need_grad:
+
+            def bwd(dy):
+                gx, acc = (None, 0)
+                if x.needs_grad:
+                    gx, acc = self.grad_accum_target(x)
+                gf, gp = None, None
+                if is_param:
+                    gp = self.pgrad(first)
+                elif first.needs_grad:
+                    gf, res = self.grad_target(first)
+                    assert res is None and self._deferred_flush is None, "the first token has one consumer"
+                if gx is None and gf is None and gp is None:
+                    return
+                self.emit(N.OP_TOKEN_PREPEND_BWD, [dy.addr(), _addr(gx), _addr(gf), gp], [dy.ld, _ld(gx), acc, _ld(gf), B, T, Cc, dt])
+                if x.needs_grad:
+                    self.grad_written(x)
 
             self._node(y, bwd)
         return y

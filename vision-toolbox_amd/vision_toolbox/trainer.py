@@ -162,6 +162,7 @@ class TrainStep:
         self._adam = optimizer != "SGD"
         self.include_pool = bool(include_pool)
         if not self.include_pool:
+            from .backbones.cait import CaiT
             from .backbones.convnext import ConvNeXt
             from .backbones.mlp_mixer import MLPMixer
             from .backbones.swin import SwinTransformer
@@ -169,9 +170,9 @@ class TrainStep:
 
             # classifier.py:59-63 with include_pool=False is nn.Sequential(backbone, nn.Linear): right only where
             # forward() already returns the pooled (B, C) vector; a map-returning family would feed nn.Linear a 4-D map
-            if not isinstance(backbone, (ConvNeXt, MLPMixer, ViT, SwinTransformer)):
+            if not isinstance(backbone, (ConvNeXt, MLPMixer, ViT, SwinTransformer, CaiT)):
                 raise ValueError(f"include_pool=False needs a backbone whose forward returns (B, C) (ConvNeXt, MLPMixer, ViT, "
-                                 f"SwinTransformer); "
+                                 f"SwinTransformer, CaiT); "
                                  f"{type(backbone).__name__} returns a feature map")
         self.device = torch.device(device if device is not None else "cuda")
         self.plan_only = plan_only  # build launch lists / bucket plan without a GPU (host-logic tests)
@@ -241,6 +242,13 @@ class TrainStep:
             if isinstance(backbone, SwinTransformer):
                 raise NotImplementedError("exchange='sharded' with a SwinTransformer: its relative-position tables and layer "
                                           "scales are read in f32 outside the head bucket (use exchange='allreduce')")
+            from .backbones.cait import CaiT
+
+            # (... and for a CaiT's position embedding, class token, layer scales and head-mixing weights)
+            if isinstance(backbone, CaiT):
+                raise NotImplementedError("exchange='sharded' with a CaiT: its position embedding, class token, layer scales and "
+                                          "talking-heads weights are read in f32 outside the head bucket (use "
+                                          "exchange='allreduce')")
         # who issues the collectives: "torch" = torch.distributed calls between segments of the launch lists (any
         # backend: gloo in the CPU tests); "rccl" = the library's own RCCL communicator (vt_comm_init), the collectives are
         # OPS of the lists (VT_OP_STAT_SYNC in front of every BatchNorm finalize, FORK + VT_OP_ALLREDUCE on the
