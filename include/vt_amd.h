@@ -317,6 +317,50 @@ int vt_token_prepend_fwd(const void* x, int32_t ldx, const void* first, int32_t 
 int vt_token_prepend_bwd(const void* dout, int32_t lddo, void* dx, int32_t ldx, int32_t accumulate, void* dfirst, int32_t ldf,
                          float* dfirst_param, int32_t B, int32_t T, int32_t C, int32_t dtype, void* stream);
 
+/* PatchConvNet (reference backbones/patchconvnet.py:25-103; vt_patchconv.hip).  bf16 and f32, f32 arithmetic from
+ * storage-rounded operands, pixel strides ld >= C, C a multiple of a 16-byte chunk.  No float atomics: a workgroup owns one
+ * image and one slab of channels and walks all its pixels, so every sum has one owner and a fixed order and every result is
+ * bit-identical from run to run.
+ *   vt_dw3_gelu_pool_fwd: a = GELU(dwconv3x3_pad1(u, w) + bias) (exact GELU; stored in the compute dtype) and
+ *                         pooled[b][c] = mean over the pixels of the STORED a, a [B][C] row in the compute dtype (the
+ *                         contract of vt_global_avgpool_fwd).  u, a are [B][H][W][C]; w is the f32 master [C][9] (bf16
+ *                         launches round it as vt_dwconv_fwd does), bias the f32 master [C] or NULL.  The slab's u plane is
+ *                         staged with its halo in LDS.
+ *   vt_dw3_gelu_pool_bwd: the whole backward of that column in one kernel: z is recomputed (never stored),
+ *                         dz = (da + dpooled / HW) * GELU'(z) is formed into an LDS plane, du = conv_transpose(dz, w)
+ *                         (+ residual, which may alias du), and the image's share of dw[c][9] and dbias[c] goes to
+ *                         scratch [B][C][10] f32; a second small kernel adds the shares over the images in image order
+ *                         into the f32 gradients (+=).  da or dpooled may be NULL (zero), du / dw / dbias too (not all).
+ *   Both return VT_ERR_UNSUPPORTED for a map whose planes ((H + 2)(W + 2) cells of one 16-byte chunk, plus 4 bytes per
+ *   element for dz in the backward) exceed the 160 KiB of LDS; vt_dw3_gelu_pool_supported(H, W, dtype) tells (1 / 0).
+ *   vt_se_gate_fwd:       y = a * sigmoid(s[b][c]); a, y are [B][HW][C], s is [B][C] in the compute dtype
+ *   vt_se_gate_bwd:       da (+)= dy * sigmoid(s) (`accumulate`), ds[b][c] = sigmoid'(s) * sum_pixels dy * a, f32 [B][C]
+ *   vt_channel_stats:     per-channel sum and sum of squares of a stored [M][C] map into a statistics buffer: exactly the
+ *                         contract of VT_CONV_STATS (fixed point, VT_STAT_REPLICAS; zeroed by the caller).  For a BatchNorm
+ *                         in front of its convolution, which has no producing conv epilogue.
+ *   vt_pool_attn_fwd/bwd: softmax attention of ONE query row per image with ONE head of width C (any multiple of a 16-byte
+ *                         chunk up to 256 chunks).  q, o, dout, dq are [B][C]; k, v, dk, dv are [B][Lk][C]; lse is [B].  One
+ *                         workgroup per image; the backward (delta = dout . o) writes dq and every row of dk and dv with
+ *                         plain stores; each may be NULL, not all. */
+int vt_dw3_gelu_pool_supported(int32_t H, int32_t W, int32_t dtype);
+int vt_dw3_gelu_pool_fwd(const void* u, int32_t ldu, const float* w, const float* bias, void* a, int32_t lda, void* pooled,
+                         int32_t ldp, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype, void* stream);
+int64_t vt_dw3_gelu_pool_bwd_scratch_bytes(int32_t B, int32_t C);
+int vt_dw3_gelu_pool_bwd(const void* u, int32_t ldu, const void* da, int32_t ldda, const void* dpooled, int32_t lddp,
+                         const float* w, const float* bias, void* du, int32_t lddu, const void* residual, int32_t ldr, float* dw,
+                         float* dbias, void* scratch, int64_t scratch_bytes, int32_t B, int32_t H, int32_t W, int32_t C,
+                         int32_t dtype, void* stream);
+int vt_se_gate_fwd(const void* a, int32_t lda, const void* s, int32_t lds, void* y, int32_t ldy, int32_t B, int32_t HW, int32_t C,
+                   int32_t dtype, void* stream);
+int vt_se_gate_bwd(const void* dy, int32_t lddy, const void* a, int32_t lda, const void* s, int32_t lds, void* da, int32_t ldda,
+                   float* ds, int32_t B, int32_t HW, int32_t C, int32_t accumulate, int32_t dtype, void* stream);
+int vt_channel_stats(const void* x, int32_t ldx, int64_t M, int32_t C, int32_t dtype, float* stats, void* stream);
+int vt_pool_attn_fwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv, void* o, int32_t ldo,
+                     float* lse, float scale, int32_t B, int32_t Lk, int32_t C, int32_t dtype, void* stream);
+int vt_pool_attn_bwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv, const void* o, int32_t ldo,
+                     const void* dout, int32_t lddo, const float* lse, void* dq, int32_t lddq, void* dk, int32_t lddk, void* dv,
+                     int32_t lddv, float scale, int32_t B, int32_t Lk, int32_t C, int32_t dtype, void* stream);
+
 /* Filter gradient: dw[n][t][c] += sum_pixels dz(pix,n) * x_gathered(pix,t,c),
  * fp32 accumulation straight into the (channels_last) .grad of the weight.
  * `d` is the forward descriptor (ldy = pixel stride of dz).  Replaces the
@@ -784,6 +828,13 @@ enum vt_op_kind {
     VT_OP_CLS_ATTN_BWD,      /* vt_cls_attn_bwd */
     VT_OP_TOKEN_PREPEND_FWD, /* vt_token_prepend_fwd */
     VT_OP_TOKEN_PREPEND_BWD, /* vt_token_prepend_bwd */
+    VT_OP_DW3_GELU_POOL_FWD, /* vt_dw3_gelu_pool_fwd */
+    VT_OP_DW3_GELU_POOL_BWD, /* vt_dw3_gelu_pool_bwd */
+    VT_OP_SE_GATE_FWD,       /* vt_se_gate_fwd */
+    VT_OP_SE_GATE_BWD,       /* vt_se_gate_bwd */
+    VT_OP_CHANNEL_STATS,     /* vt_channel_stats */
+    VT_OP_POOL_ATTN_FWD,     /* vt_pool_attn_fwd */
+    VT_OP_POOL_ATTN_BWD,     /* vt_pool_attn_bwd */
     VT_OP_KIND_END
 };
 

@@ -280,6 +280,24 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
             return vt_token_prepend_fwd(P[0], I[0], P[1], I[1], (const float*)P[2], P[3], I[2], I[3], I[4], I[5], I[6], st);
         case VT_OP_TOKEN_PREPEND_BWD:  // ptr: dout dx dfirst dfirst_param | i: lddo ldx accumulate ldf B T C dtype
             return vt_token_prepend_bwd(P[0], I[0], P[1], I[1], I[2], P[2], I[3], (float*)P[3], I[4], I[5], I[6], I[7], st);
+        case VT_OP_DW3_GELU_POOL_FWD:  // ptr: u w bias a pooled | i: ldu lda ldp B H W C dtype
+            return vt_dw3_gelu_pool_fwd(P[0], I[0], (const float*)P[1], (const float*)P[2], P[3], I[1], P[4], I[2], I[3], I[4], I[5],
+                                        I[6], I[7], st);
+        case VT_OP_DW3_GELU_POOL_BWD:  // ptr: u da dpooled w bias du residual dw dbias scratch | i: ldu ldda lddp lddu ldr B H W C dtype | f: scratch bytes
+            return vt_dw3_gelu_pool_bwd(P[0], I[0], P[1], I[1], P[2], I[2], (const float*)P[3], (const float*)P[4], P[5], I[3], P[6],
+                                        I[4], (float*)P[7], (float*)P[8], P[9], (int64_t)F[0], I[5], I[6], I[7], I[8], I[9], st);
+        case VT_OP_SE_GATE_FWD:  // ptr: a s y | i: lda lds ldy B HW C dtype
+            return vt_se_gate_fwd(P[0], I[0], P[1], I[1], P[2], I[2], I[3], I[4], I[5], I[6], st);
+        case VT_OP_SE_GATE_BWD:  // ptr: dy a s da ds | i: lddy lda lds ldda B HW C accumulate dtype
+            return vt_se_gate_bwd(P[0], I[0], P[1], I[1], P[2], I[2], P[3], I[3], (float*)P[4], I[4], I[5], I[6], I[7], I[8], st);
+        case VT_OP_CHANNEL_STATS:  // ptr: x stats | i: ldx C dtype | f: M
+            return vt_channel_stats(P[0], I[0], (int64_t)F[0], I[1], I[2], (float*)P[1], st);
+        case VT_OP_POOL_ATTN_FWD:  // ptr: q k v o lse | i: ldq ldk ldv ldo B Lk C dtype | f: scale
+            return vt_pool_attn_fwd(P[0], I[0], P[1], I[1], P[2], I[2], P[3], I[3], (float*)P[4], (float)F[0], I[4], I[5], I[6], I[7],
+                                    st);
+        case VT_OP_POOL_ATTN_BWD:  // ptr: q k v o dout lse dq dk dv | i: ldq ldk ldv ldo lddo lddq lddk lddv B Lk C dtype | f: scale
+            return vt_pool_attn_bwd(P[0], I[0], P[1], I[1], P[2], I[2], P[3], I[3], P[4], I[4], (const float*)P[5], P[6], I[5], P[7],
+                                    I[6], P[8], I[7], (float)F[0], I[8], I[9], I[10], I[11], st);
         case VT_OP_BN_FIN_APPLY:  // ptr: stats gamma beta rm rv nbt scale shift mean invstd z residual y | i: C ldz ldr ldy relu dtype | f: count eps momentum M
             return vt_bn_finalize_apply((const float*)P[0], I[0], F[0], (const float*)P[1], (const float*)P[2], (float)F[1], (float)F[2],
                                         (float*)P[3], (float*)P[4], (int64_t*)P[5], (float*)P[6], (float*)P[7], (float*)P[8],

@@ -131,7 +131,14 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_CLS_ATTN_BWD,
     OP_TOKEN_PREPEND_FWD,
     OP_TOKEN_PREPEND_BWD,
-) = range(1, 74)
+    OP_DW3_GELU_POOL_FWD,
+    OP_DW3_GELU_POOL_BWD,
+    OP_SE_GATE_FWD,
+    OP_SE_GATE_BWD,
+    OP_CHANNEL_STATS,
+    OP_POOL_ATTN_FWD,
+    OP_POOL_ATTN_BWD,
+) = range(1, 81)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -189,6 +196,13 @@ OP_NAMES = {
     OP_CLS_ATTN_BWD: "cls_attn_bwd",
     OP_TOKEN_PREPEND_FWD: "token_prepend_fwd",
     OP_TOKEN_PREPEND_BWD: "token_prepend_bwd",
+    OP_DW3_GELU_POOL_FWD: "dw3_gelu_pool_fwd",
+    OP_DW3_GELU_POOL_BWD: "dw3_gelu_pool_bwd",
+    OP_SE_GATE_FWD: "se_gate_fwd",
+    OP_SE_GATE_BWD: "se_gate_bwd",
+    OP_CHANNEL_STATS: "channel_stats",
+    OP_POOL_ATTN_FWD: "pool_attn_fwd",
+    OP_POOL_ATTN_BWD: "pool_attn_bwd",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -328,6 +342,17 @@ SYMBOLS = {
                         + [_i32] * 5 + [_vp]),
     "vt_token_prepend_fwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_token_prepend_bwd": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "vt_dw3_gelu_pool_supported": (_i32, [_i32, _i32, _i32]),
+    "vt_dw3_gelu_pool_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32] + [_i32] * 5 + [_vp]),
+    "vt_dw3_gelu_pool_bwd_scratch_bytes": (_i64, [_i32, _i32]),
+    "vt_dw3_gelu_pool_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64]
+                             + [_i32] * 5 + [_vp]),
+    "vt_se_gate_fwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32] + [_i32] * 4 + [_vp]),
+    "vt_se_gate_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp] + [_i32] * 5 + [_vp]),
+    "vt_channel_stats": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp]),
+    "vt_pool_attn_fwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _f32] + [_i32] * 4 + [_vp]),
+    "vt_pool_attn_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _f32]
+                         + [_i32] * 4 + [_vp]),
     "vt_vit_tokens_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_vit_tokens_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_token_select_fwd": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -1,4 +1,5 @@
-"""Backbones of the MI355X hot path: Darknet / CSPDarknet / DarknetYOLOv5 / VoVNet / ConvNeXt / MLP-Mixer / ViT / Swin / CaiT.
+"""Backbones of the MI355X hot path: Darknet / CSPDarknet / DarknetYOLOv5 / VoVNet / ConvNeXt / MLP-Mixer / ViT / Swin / CaiT /
+PatchConvNet.
 
 Both surfaces the reference snapshot exposes are exported: the classes with
 `from_config` (reference backbones/__init__.py:3,10, tests/test_backbones.py:25-30) and the
@@ -9,14 +10,17 @@ first family without convolutions: its token mixing runs on the transposed-GEMM 
 (backbones/vit.py:111, with its blocks MHA / ViTBlock / MHAPooling) runs on the fused attention kernels of vt_attention.hip,
 and SwinTransformer (backbones/swin.py:127, with WindowAttention / SwinBlock / PatchMerging), the hierarchical one, on the
 shifted-window kernels of vt_window_attention.hip.  CaiT (backbones/cait.py:101, with ClassAttention / TalkingHeadAttention /
-CaiTCABlock / CaiTSABlock) runs its talking-heads and class attention on the kernels of vt_talking_attention.hip.  DeiT, the
-other family the reference builds on ViT, and its torchvision extractors are not part of this build yet.
+CaiTCABlock / CaiTSABlock) runs its talking-heads and class attention on the kernels of vt_talking_attention.hip.
+PatchConvNet (backbones/patchconvnet.py:106, with PatchConvBlockLN / PatchConvBlockBN / AttentionPooling and a
+SqueezeExcitation of our own: torchvision is not imported) runs on the plane, gate and pooling kernels of vt_patchconv.hip.
+DeiT, the other family the reference builds on ViT, and its torchvision extractors are not part of this build yet.
 """
 from .base import BaseBackbone
 from .convnext import ConvNeXt, ConvNeXtBlock, GlobalResponseNorm
 from .mlp_mixer import MLP, MixerBlock, MLPMixer
 from .vit import MHA, MHAPooling, ViT, ViTBlock
 from .cait import CaiT, CaiTCABlock, CaiTSABlock, ClassAttention, TalkingHeadAttention
+from .patchconvnet import AttentionPooling, PatchConvBlockBN, PatchConvBlockLN, PatchConvNet, SqueezeExcitation
 from .swin import PatchMerging, SwinBlock, SwinTransformer, WindowAttention, window_partition, window_unpartition
 from .darknet import (
     CSPDarknetStage,

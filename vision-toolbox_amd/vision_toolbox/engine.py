@@ -569,6 +569,7 @@ class Builder:
         self._attn_scratch: dict[int, Buf] = {}  # attention: the backward's delta, per size
         self._win_scratch: dict[int, Buf] = {}  # window attention: the per-window shares of the table gradient, per size
         self._talk_scratch: dict[int, Buf] = {}  # talking-heads attention: delta and the parameter-gradient shares, per size
+        self._dw3_scratch: dict[int, Buf] = {}  # depthwise 3x3 + GELU + pool: the per-image filter-gradient shares, per size
 
     # -- memory -----------------------------------------------------------------
     def alloc(self, nbytes: int, name: str = "") -> Buf:
@@ -2098,6 +2099,151 @@ class Builder:
 
             self._node(y, bwd)
         return y
+
+    # -- PatchConvNet pieces (reference backbones/patchconvnet.py:25-103): vt_patchconv.hip ------------------------------
+    def batch_norm(self, x: TRef, bn: nn.BatchNorm2d, name: str = "bn") -> TRef:
+        """a BatchNorm2d that stands IN FRONT of its convolution: there is no conv epilogue to take the batch statistics
+        from, so vt_channel_stats forms them from the stored map (the contract of VT_CONV_STATS); the rest are the launches of
+        a conv unit with activation code 0 and x as the "pre-activation" -- finalize / normalise (or the two in one), the
+        running-statistics update, SyncBatchNorm's exchange in front of the finalize, and the BatchNorm backward."""
+        spec = bn if isinstance(bn, BNSpec) else BNSpec.from_bn(bn)
+        if x.logical_c != x.C or x.C % _EPC[self.dtype] or spec.weight.numel() != x.C:
+            raise NotImplementedError(f"{name}: BatchNorm2d({spec.weight.numel()}) over a {x.logical_c}-channel map")
+        self.tag += 1
+        em = _BNEmitter(self, spec, x.C)
+        y = self.act(x.B, x.H, x.W, x.C, name + ".y")
+        if spec.training:
+            stats = self.zeroed_f32(N.stat_floats(x.C), "stats")
+            self.emit(N.OP_CHANNEL_STATS, [x.addr(), self.bp(stats)], [x.ld, x.C, self.dtype], [x.M])
+            if self.bn_fin_apply and not self.bn_sync:
+                ptrs, flts = em.finalize_operands(stats, x.M)
+                self.emit(N.OP_BN_FIN_APPLY, ptrs + [x.addr(), None, y.addr()], [x.C, x.ld, 0, y.ld, 0, self.dtype], flts + [x.M])
+            else:
+                em.finalize(stats, x.M)
+                self._act_apply(x, em.cp[0], em.cp[1], None, y, 0)
+        else:
+            em.eval_coeffs()
+            self._act_apply(x, em.cp[0], em.cp[1], None, y, 0)
+        if self.need_grad:
+
+            def bwd(dy):
+                sums, bcoef, dz = em.bwd_buffers(y, name + ".dx")
+                if self.bn_fin_apply and not self.bn_sync:
+                    em.bwd_reduce(dy, x, 0, sums, x.M)
+                    self.emit(N.OP_BN_BWD_FIN_APPLY,
+                              [self.bp(sums), *em.cp, *em.grads(), self.bp(bcoef), dy.addr(), x.addr(), dz.addr()],
+                              [x.C, int(spec.training), dy.ld, x.ld, dz.ld, 0, self.dtype],
+                              [x.M * self.bn_world, 1.0 / self.bn_world, x.M])
+                else:
+                    em.bwd_three_launches(dy, x, 0, sums, bcoef, dz)
+                self.grad_add(x, dz)
+
+            self._node(y, bwd)
+        return y
+
+    def dw3_gelu_pool(self, u: TRef, conv: nn.Conv2d, name: str = "dw") -> "tuple[TRef, TRef]":
+        """(a, pooled): a = GELU(depthwise 3x3, padding 1, of u + bias) and pooled = mean over the pixels of a, [B, 1, 1, C],
+        in ONE launch that owns (image, channel slab) and walks all its pixels (vt_dw3_gelu_pool_fwd).  Backward: one
+        launch recomputes z, forms dz from d(a) and d(pooled), writes d(u) and each image's share of the filter / bias
+        gradient, which a small second kernel adds in image order (vt_dw3_gelu_pool_bwd): no atomics, the same launch under
+        `deterministic`.  The filter and bias are read as f32 masters."""
+        dt, Cc = self.dtype, u.C
+        if (tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding), tuple(conv.dilation)) != ((3, 3), (1, 1), (1, 1), (1, 1)) \
+                or conv.groups != Cc or conv.in_channels != Cc or conv.out_channels != Cc:
+            raise NotImplementedError(f"{name}: a depthwise 3x3 convolution with stride 1 and padding 1 over {Cc} channels")
+        if u.logical_c != Cc or Cc % _EPC[dt]:
+            raise NotImplementedError(f"{name}: {Cc} channels must be a multiple of {_EPC[dt]} for dtype {dt}")
+        if not N.lib().vt_dw3_gelu_pool_supported(u.H, u.W, dt):
+            raise NotImplementedError(f"{name}: a {u.H}x{u.W} token map is too large for the plane kernels: the planes of one "
+                                      "16-byte channel slab with their halo must fit 160 KiB of LDS")
+        self.tag += 1
+        tag = self.tag
+        B, H, W = u.B, u.H, u.W
+        a = self.act(B, H, W, Cc, name + ".a")
+        pooled = self.act(B, 1, 1, Cc, name + ".pooled")
+        wp, bp_ = self.pref(conv.weight), self.pref(conv.bias)
+        self.emit(N.OP_DW3_GELU_POOL_FWD, [u.addr(), wp, bp_, a.addr(), pooled.addr()], [u.ld, a.ld, pooled.ld, B, H, W, Cc, dt])
+        if self.need_grad:
+
+            def bwd():
+                self.tag = tag
+                da, dp = self.grad_read(a), self.grad_read(pooled)
+                if da is None and dp is None:
+                    return
+                gu = res = None
+                if u.needs_grad:
+                    gu, res = self.grad_target(u)
+                dw, db = self.pgrad(conv.weight), self.pgrad(conv.bias)
+                if gu is None and dw is None and db is None:
+                    return
+                nbytes = int(N.lib().vt_dw3_gelu_pool_bwd_scratch_bytes(B, Cc))
+                if nbytes not in self._dw3_scratch:  # (one per size: the launches follow each other on one stream)
+                    self._dw3_scratch[nbytes] = self.alloc(nbytes, "dw3_shares")
+                self.emit(N.OP_DW3_GELU_POOL_BWD,
+                          [u.addr(), _addr(da), _addr(dp), wp, bp_, _addr(gu), _addr(res), dw, db, self.bp(self._dw3_scratch[nbytes])],
+                          [u.ld, _ld(da), _ld(dp), _ld(gu), _ld(res), B, H, W, Cc, dt], [nbytes])
+                if gu is not None:
+                    self.grad_written(u)
+
+            self.nodes.append(bwd)
+        return a, pooled
+
+    def se_gate(self, a: TRef, s: TRef, out: Optional[TRef] = None, name: str = "se") -> TRef:
+        """y = a * sigmoid(s): the Squeeze-Excitation scale, s a [B, 1, 1, C] row per image (vt_se_gate_fwd).  Backward: d(a)
+        and the f32 d(s), summed over the pixels by the (image, slab) owner (vt_se_gate_bwd)."""
+        if (s.B, s.H, s.W, s.C) != (a.B, 1, 1, a.C):
+            raise ValueError(f"{name}: s is a [B, 1, 1, {a.C}] row per image")
+        self.tag += 1
+        dt = self.dtype
+        y = out if out is not None else self.act(a.B, a.H, a.W, a.C, name + ".y")
+        assert y.same_geom(a), "out geometry mismatch"
+        self.emit(N.OP_SE_GATE_FWD, [a.addr(), s.addr(), y.addr()], [a.ld, s.ld, y.ld, a.B, a.H * a.W, a.C, dt])
+        if self.need_grad:
+
+            def bwd(dy):
+                ga, acc = self.grad_accum_target(a)
+                ds32 = self.f32(a.B * a.C, "ds32")
+                self.emit(N.OP_SE_GATE_BWD, [dy.addr(), a.addr(), s.addr(), ga.addr(), self.bp(ds32)],
+                          [dy.ld, a.ld, s.ld, ga.ld, a.B, a.H * a.W, a.C, acc, dt])
+                self.grad_written(a)
+                gs_, _ = self.grad_target(s)
+                self.emit(N.OP_COPY2D, [self.bp(ds32), gs_.addr()], [N.VT_F32, dt, a.C, 0], [a.C, gs_.ld, a.B])
+
+            self._node(y, bwd)
+        return y
+
+    def pool_attention(self, q: TRef, k: TRef, v: TRef, name: str = "pool_attention") -> TRef:
+        """softmax(q k^T / sqrt(C)) v with ONE query row per image and ONE head as wide as the embedding: q is [B, 1, 1, C],
+        k and v are [B, 1, Lk, C] maps (channel slices of one buffer or not), the result [B, 1, 1, C] (vt_pool_attn_fwd).
+        Backward: one vt_pool_attn_bwd writes d(q) and every row of d(k), d(v); no scratch, no atomics."""
+        dt = self.dtype
+        if not k.same_geom(v) or k.H != 1 or (q.B, q.H, q.W, q.C) != (k.B, 1, 1, k.C):
+            raise ValueError(f"{name}: q is a [B, 1, 1, C] row per image, k and v are [B, 1, Lk, C] token maps of one geometry")
+        if any(t.logical_c != t.C for t in (q, k, v)) or q.C % _EPC[dt] or q.C // _EPC[dt] > 256:
+            raise NotImplementedError(f"{name}: {q.C} channels must be a multiple of {_EPC[dt]} and at most {256 * _EPC[dt]} "
+                                      f"for dtype {dt}")
+        self.tag += 1
+        B, Lk, Cc, scale = k.B, k.W, q.C, q.C ** -0.5
+        o = self.act(B, 1, 1, Cc, name + ".o")
+        lse = self.f32(B, name + ".lse")
+        self.emit(N.OP_POOL_ATTN_FWD, [q.addr(), k.addr(), v.addr(), o.addr(), self.bp(lse)],
+                  [q.ld, k.ld, v.ld, o.ld, B, Lk, Cc, dt], [scale])
+        if self.need_grad and (q.needs_grad or k.needs_grad or v.needs_grad):
+
+            def bwd(do):
+                gs = []
+                for t in (q, k, v):
+                    g = None
+                    if t.needs_grad:
+                        g, res = self.grad_target(t)
+                        assert res is None and self._deferred_flush is None, "q, k and v have one consumer, the attention"
+                    gs.append(g)
+                self.emit(N.OP_POOL_ATTN_BWD,
+                          [q.addr(), k.addr(), v.addr(), o.addr(), do.addr(), self.bp(lse), *[_addr(g) for g in gs]],
+                          [q.ld, k.ld, v.ld, o.ld, do.ld, *[_ld(g) for g in gs], B, Lk, Cc, dt], [scale])
+
+            self._node(o, bwd)
+        return o
 
     # -- ESE gate (reference vovnet.py:20-28) ---------------------------------------------
     def ese(self, x: TRef, linear: nn.Conv2d, residual: Optional[TRef] = None,

@@ -165,14 +165,15 @@ class TrainStep:
             from .backbones.cait import CaiT
             from .backbones.convnext import ConvNeXt
             from .backbones.mlp_mixer import MLPMixer
+            from .backbones.patchconvnet import PatchConvNet
             from .backbones.swin import SwinTransformer
             from .backbones.vit import ViT
 
             # classifier.py:59-63 with include_pool=False is nn.Sequential(backbone, nn.Linear): right only where
             # forward() already returns the pooled (B, C) vector; a map-returning family would feed nn.Linear a 4-D map
-            if not isinstance(backbone, (ConvNeXt, MLPMixer, ViT, SwinTransformer, CaiT)):
+            if not isinstance(backbone, (ConvNeXt, MLPMixer, ViT, SwinTransformer, CaiT, PatchConvNet)):
                 raise ValueError(f"include_pool=False needs a backbone whose forward returns (B, C) (ConvNeXt, MLPMixer, ViT, "
-                                 f"SwinTransformer, CaiT); "
+                                 f"SwinTransformer, CaiT, PatchConvNet); "
                                  f"{type(backbone).__name__} returns a feature map")
         self.device = torch.device(device if device is not None else "cuda")
         self.plan_only = plan_only  # build launch lists / bucket plan without a GPU (host-logic tests)
@@ -249,6 +250,12 @@ class TrainStep:
                 raise NotImplementedError("exchange='sharded' with a CaiT: its position embedding, class token, layer scales and "
                                           "talking-heads weights are read in f32 outside the head bucket (use "
                                           "exchange='allreduce')")
+            from .backbones.patchconvnet import PatchConvNet
+
+            # (... and for a PatchConvNet's depthwise filters, class token and layer scales)
+            if isinstance(backbone, PatchConvNet):
+                raise NotImplementedError("exchange='sharded' with a PatchConvNet: its depthwise filters, class token and layer "
+                                          "scales are read in f32 outside the head bucket (use exchange='allreduce')")
         # who issues the collectives: "torch" = torch.distributed calls between segments of the launch lists (any
         # backend: gloo in the CPU tests); "rccl" = the library's own RCCL communicator (vt_comm_init), the collectives are
         # OPS of the lists (VT_OP_STAT_SYNC in front of every BatchNorm finalize, FORK + VT_OP_ALLREDUCE on the
