@@ -361,6 +361,35 @@ int vt_pool_attn_bwd(const void* q, int32_t ldq, const void* k, int32_t ldk, con
                      const void* dout, int32_t lddo, const float* lse, void* dq, int32_t lddq, void* dk, int32_t lddk, void* dv,
                      int32_t lddv, float scale, int32_t B, int32_t Lk, int32_t C, int32_t dtype, void* stream);
 
+/* The token bookkeeping of DeiT (reference backbones/deit.py:37-41 -- cat([cls_token, dist_token, patches + pe], 1) in front
+ * of the blocks, norm(out[:, :2]).mean(1) behind them), general in the number of prefix rows P, vt_prefix_tokens.hip.  bf16
+ * and f32, f32 arithmetic from storage-rounded operands, one rounding at the store.  Rows are [B][rows][C] with a row stride
+ * each (ld >= C, a multiple of 8 (bf16) / 4 (f32), like C: VT_ERR_UNSUPPORTED / VT_ERR_INVALID otherwise); 1 <= P <= 4.  Every
+ * global access is a 16-byte chunk per lane; no float atomics: every sum has one owner or goes through the fixed-point
+ * channel-sums buffer, so every result is bit-identical from run to run.
+ *   vt_prefix_tokens_fwd: out[b][p] = prefix[p] (p < P; `prefix` is a HOST array of P device pointers to f32 masters of C
+ *                         values each, broadcast over the batch; no position is added), out[b][P + t] = embed[b][t] + pe[t];
+ *                         embed is [B][T][C], out [B][P + T][C], pe the f32 master [T][C]
+ *   vt_prefix_tokens_bwd: dembed[b][t] = dout[b][P + t], dpe[t] += sum_b dout[b][P + t], dprefix[p] += sum_b dout[b][p]
+ *                         (f32, summed over the images in order by the one thread that owns the chunk).  dembed, dpe, the
+ *                         array dprefix and each of its P entries may be NULL, not all of them.
+ *   vt_prefix_pool_fwd:   y[b] = (1 / P) sum_{p < P} LayerNorm_C(x[b][p]; gamma, beta, eps); x is [B][L][C] (L >= P), y is
+ *                         [B][C]; C <= 3072 (a wave holds a row in registers)
+ *   vt_prefix_pool_bwd:   dx[b][p] (= | +=, `accumulate`) the LayerNorm backward of dy[b] / P through row p, mean and rstd
+ *                         recomputed from x; rows t >= P of dx are written ZERO with accumulate = 0 and left alone with
+ *                         accumulate = 1 (the gradient is rounded to the storage type before it is added).  `sums`
+ *                         (VT_CHANNEL_SUMS_BYTES(2, C) bytes, zeroed by the caller; vt_channel_sums_to_f32 folds it):
+ *                         row 0 += sum_{b,p} (dy[b] / P) xhat[b][p] (d gamma), row 1 += sum_b dy[b] (d beta) */
+int vt_prefix_tokens_fwd(const void* embed, int32_t lde, const float* pe, const float* const* prefix, int32_t P, void* out,
+                         int32_t ldo, int32_t B, int32_t T, int32_t C, int32_t dtype, void* stream);
+int vt_prefix_tokens_bwd(const void* dout, int32_t lddo, void* dembed, int32_t lde, float* dpe, float* const* dprefix, int32_t P,
+                         int32_t B, int32_t T, int32_t C, int32_t dtype, void* stream);
+int vt_prefix_pool_fwd(const void* x, int32_t ldx, const float* gamma, const float* beta, void* y, int32_t ldy, int32_t B,
+                       int32_t L, int32_t P, int32_t C, float eps, int32_t dtype, void* stream);
+int vt_prefix_pool_bwd(const void* dy, int32_t lddy, const void* x, int32_t ldx, const float* gamma, void* dx, int32_t lddx,
+                       int32_t accumulate, float* sums, int32_t B, int32_t L, int32_t P, int32_t C, float eps, int32_t dtype,
+                       void* stream);
+
 /* Filter gradient: dw[n][t][c] += sum_pixels dz(pix,n) * x_gathered(pix,t,c),
  * fp32 accumulation straight into the (channels_last) .grad of the weight.
  * `d` is the forward descriptor (ldy = pixel stride of dz).  Replaces the
@@ -835,6 +864,10 @@ enum vt_op_kind {
     VT_OP_CHANNEL_STATS,     /* vt_channel_stats */
     VT_OP_POOL_ATTN_FWD,     /* vt_pool_attn_fwd */
     VT_OP_POOL_ATTN_BWD,     /* vt_pool_attn_bwd */
+    VT_OP_PREFIX_TOKENS_FWD, /* vt_prefix_tokens_fwd */
+    VT_OP_PREFIX_TOKENS_BWD, /* vt_prefix_tokens_bwd */
+    VT_OP_PREFIX_POOL_FWD,   /* vt_prefix_pool_fwd */
+    VT_OP_PREFIX_POOL_BWD,   /* vt_prefix_pool_bwd */
     VT_OP_KIND_END
 };
 

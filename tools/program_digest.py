@@ -93,6 +93,30 @@ def convnext(name):
     return lambda: convnext_util.build(name)
 
 
+def vit(name):
+    import vit_util
+
+    return lambda: vit_util.build(name)
+
+
+def vit_size(name):
+    import vit_util
+
+    return vit_util.CASES[name][0][4]
+
+
+def deit(name):
+    import deit_util
+
+    return lambda: deit_util.build(name)
+
+
+def deit_size(name):
+    import deit_util
+
+    return deit_util.CASES[name][1][4]
+
+
 def _freeze_norm(m):
     m.norm.eval()
 
@@ -132,6 +156,10 @@ def all_module_cases():
     for c in "abc":
         module_cases(f"convnext_{c}", convnext(c), 64)
     module_cases("mlp_mixer", lambda: MLPMixer(2, 32, 4, 20), 20)
+    for c in "abc":  # (appended: the lines above keep their order)
+        module_cases(f"vit_{c}", vit(c), vit_size(c))
+    for c in "abc":
+        module_cases(f"deit_{c}", deit(c), deit_size(c))
     for label, make, cin, prep in UNITS:
         module_cases(f"unit {label}", make, 16, channels=cin, prep=prep)
         module_cases(f"unit {label}", make, 16, channels=cin, prep=prep, env={"VT_PW_MIN_MB": "0"}, dtypes=DTYPES[1:])

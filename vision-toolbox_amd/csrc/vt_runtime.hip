@@ -298,6 +298,20 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
         case VT_OP_POOL_ATTN_BWD:  // ptr: q k v o dout lse dq dk dv | i: ldq ldk ldv ldo lddo lddq lddk lddv B Lk C dtype | f: scale
             return vt_pool_attn_bwd(P[0], I[0], P[1], I[1], P[2], I[2], P[3], I[3], P[4], I[4], (const float*)P[5], P[6], I[5], P[7],
                                     I[6], P[8], I[7], (float)F[0], I[8], I[9], I[10], I[11], st);
+        case VT_OP_PREFIX_TOKENS_FWD: {  // ptr: embed pe out prefix0..3 | i: lde ldo P B T C dtype
+            const float* prefix[4] = {(const float*)P[3], (const float*)P[4], (const float*)P[5], (const float*)P[6]};
+            return vt_prefix_tokens_fwd(P[0], I[0], (const float*)P[1], prefix, I[2], P[2], I[1], I[3], I[4], I[5], I[6], st);
+        }
+        case VT_OP_PREFIX_TOKENS_BWD: {  // ptr: dout dembed dpe dprefix0..3 | i: lddo lde P B T C dtype
+            float* dprefix[4] = {(float*)P[3], (float*)P[4], (float*)P[5], (float*)P[6]};
+            return vt_prefix_tokens_bwd(P[0], I[0], P[1], I[1], (float*)P[2], dprefix, I[2], I[3], I[4], I[5], I[6], st);
+        }
+        case VT_OP_PREFIX_POOL_FWD:  // ptr: x gamma beta y | i: ldx ldy B L P C dtype | f: eps
+            return vt_prefix_pool_fwd(P[0], I[0], (const float*)P[1], (const float*)P[2], P[3], I[1], I[2], I[3], I[4], I[5],
+                                      (float)F[0], I[6], st);
+        case VT_OP_PREFIX_POOL_BWD:  // ptr: dy x gamma dx sums | i: lddy ldx lddx accumulate B L P C dtype | f: eps
+            return vt_prefix_pool_bwd(P[0], I[0], P[1], I[1], (const float*)P[2], P[3], I[2], I[3], (float*)P[4], I[4], I[5], I[6],
+                                      I[7], (float)F[0], I[8], st);
         case VT_OP_BN_FIN_APPLY:  // ptr: stats gamma beta rm rv nbt scale shift mean invstd z residual y | i: C ldz ldr ldy relu dtype | f: count eps momentum M
             return vt_bn_finalize_apply((const float*)P[0], I[0], F[0], (const float*)P[1], (const float*)P[2], (float)F[1], (float)F[2],
                                         (float*)P[3], (float*)P[4], (int64_t*)P[5], (float*)P[6], (float*)P[7], (float*)P[8],

@@ -138,7 +138,11 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_CHANNEL_STATS,
     OP_POOL_ATTN_FWD,
     OP_POOL_ATTN_BWD,
-) = range(1, 81)
+    OP_PREFIX_TOKENS_FWD,
+    OP_PREFIX_TOKENS_BWD,
+    OP_PREFIX_POOL_FWD,
+    OP_PREFIX_POOL_BWD,
+) = range(1, 85)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -203,6 +207,10 @@ OP_NAMES = {
     OP_CHANNEL_STATS: "channel_stats",
     OP_POOL_ATTN_FWD: "pool_attn_fwd",
     OP_POOL_ATTN_BWD: "pool_attn_bwd",
+    OP_PREFIX_TOKENS_FWD: "prefix_tokens_fwd",
+    OP_PREFIX_TOKENS_BWD: "prefix_tokens_bwd",
+    OP_PREFIX_POOL_FWD: "prefix_pool_fwd",
+    OP_PREFIX_POOL_BWD: "prefix_pool_bwd",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -353,6 +361,10 @@ SYMBOLS = {
     "vt_pool_attn_fwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _f32] + [_i32] * 4 + [_vp]),
     "vt_pool_attn_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _f32]
                          + [_i32] * 4 + [_vp]),
+    "vt_prefix_tokens_fwd": (_i32, [_vp, _i32, _vp, C.POINTER(_vp), _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vt_prefix_tokens_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, C.POINTER(_vp), _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vt_prefix_pool_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
+    "vt_prefix_pool_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp]),
     "vt_vit_tokens_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_vit_tokens_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_token_select_fwd": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -1,5 +1,5 @@
 """Backbones of the MI355X hot path: Darknet / CSPDarknet / DarknetYOLOv5 / VoVNet / ConvNeXt / MLP-Mixer / ViT / Swin / CaiT /
-PatchConvNet.
+PatchConvNet / DeiT.
 
 Both surfaces the reference snapshot exposes are exported: the classes with
 `from_config` (reference backbones/__init__.py:3,10, tests/test_backbones.py:25-30) and the
@@ -13,12 +13,15 @@ shifted-window kernels of vt_window_attention.hip.  CaiT (backbones/cait.py:101,
 CaiTCABlock / CaiTSABlock) runs its talking-heads and class attention on the kernels of vt_talking_attention.hip.
 PatchConvNet (backbones/patchconvnet.py:106, with PatchConvBlockLN / PatchConvBlockBN / AttentionPooling and a
 SqueezeExcitation of our own: torchvision is not imported) runs on the plane, gate and pooling kernels of vt_patchconv.hip.
-DeiT, the other family the reference builds on ViT, and its torchvision extractors are not part of this build yet.
+DeiT and DeiT3 (backbones/deit.py:14,118), the other family the reference builds on ViT, run on ViT's block path; DeiT's
+two prefix tokens and its two-token pooled head run on the kernels of vt_prefix_tokens.hip.  The reference's torchvision
+extractors are not part of this build (torchvision is not imported).
 """
 from .base import BaseBackbone
 from .convnext import ConvNeXt, ConvNeXtBlock, GlobalResponseNorm
 from .mlp_mixer import MLP, MixerBlock, MLPMixer
 from .vit import MHA, MHAPooling, ViT, ViTBlock
+from .deit import DeiT, DeiT3
 from .cait import CaiT, CaiTCABlock, CaiTSABlock, ClassAttention, TalkingHeadAttention
 from .patchconvnet import AttentionPooling, PatchConvBlockBN, PatchConvBlockLN, PatchConvNet, SqueezeExcitation
 from .swin import PatchMerging, SwinBlock, SwinTransformer, WindowAttention, window_partition, window_unpartition

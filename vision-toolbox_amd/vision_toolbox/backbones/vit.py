@@ -251,12 +251,19 @@ class ViT(HipModule):
         if self.d_model % _EPC[b.dtype]:
             raise NotImplementedError(f"d_model={self.d_model} must be a multiple of {_EPC[b.dtype]} for dtype {b.dtype}")
         e = b.patch_embed(x, self.patch_embed, name="patch_embed")
-        o = b.vit_tokens(e, self.pe, self.cls_token, name="tokens")
+        o = self._vt_emit_tokens(b, e)
         for i, blk in enumerate(self.layers):
             o = blk._vt_emit(b, o, name=f"layers.{i}")
+        return [self._vt_emit_pool(b, o)]
+
+    # (the two ends of the token map that a subclass with other prefix tokens replaces: DeiT)
+    def _vt_emit_tokens(self, b, e):
+        return b.vit_tokens(e, self.pe, self.cls_token, name="tokens")
+
+    def _vt_emit_pool(self, b, o):
         if self.pool_type == "cls_token":
-            return [b.layer_norm(b.token_select(o, 0, name="pool"), self.norm, name="norm")]
-        return [b.global_avgpool(b.layer_norm(o, self.norm, name="norm"), name="pool")]
+            return b.layer_norm(b.token_select(o, 0, name="pool"), self.norm, name="norm")
+        return b.global_avgpool(b.layer_norm(o, self.norm, name="norm"), name="pool")
 
     def _eager_maps(self, x: Tensor) -> "list[Tensor]":
         out = self.patch_embed(x).flatten(2).transpose(1, 2) + self.pe  # (B, C, gh, gw) -> (B, tokens, C)

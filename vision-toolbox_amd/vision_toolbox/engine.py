@@ -1968,6 +1968,80 @@ class Builder:
             self._node(y, bwd)
         return y
 
+    # -- DeiT pieces (reference backbones/deit.py:37-41): vt_prefix_tokens.hip ------------------------------------------
+    def prefix_tokens(self, embed: TRef, pe: nn.Parameter, prefix_params, name: str = "tokens") -> TRef:
+        """the token map of a DeiT: P learned rows (parameters of C values, read as f32 masters, broadcast over the batch, no
+        position) in front of the [B, gh, gw, C] patch embeddings + pe -> [B, 1, P + T, C] (vt_prefix_tokens_fwd).  Backward
+        copies the patch rows into d(embed) and sums d(pe) and every d(prefix) over the batch in a fixed order
+        (vt_prefix_tokens_bwd), as vit_tokens does for its one row."""
+        T, Cc, dt = embed.H * embed.W, embed.C, self.dtype
+        prefix_params = list(prefix_params)
+        P = len(prefix_params)
+        if not 1 <= P <= 4:
+            raise ValueError(f"{name}: {P} prefix tokens (1..4)")
+        if embed.logical_c != Cc or pe.numel() != T * Cc:
+            raise ValueError(f"{name}: pe holds {pe.numel()} values, the {embed.H}x{embed.W} map of {Cc} channels {T * Cc}")
+        for k, p in enumerate(prefix_params):
+            if p.numel() != Cc:
+                raise ValueError(f"{name}: prefix token {k} holds {p.numel()} values for {Cc} channels")
+        if Cc % _EPC[dt]:
+            raise NotImplementedError(f"{name}: {Cc} channels must be a multiple of {_EPC[dt]} for dtype {dt}")
+        self.tag += 1
+        B = embed.B
+        pad = [None] * (4 - P)
+        y = self.act(B, 1, P + T, Cc, name + ".y")
+        self.emit(N.OP_PREFIX_TOKENS_FWD, [embed.addr(), self.pref(pe), y.addr()] + [self.pref(p) for p in prefix_params] + pad,
+                  [embed.ld, y.ld, P, B, T, Cc, dt])
+        if self.need_grad:
+
+            def bwd(dy):
+                ge = None
+                if embed.needs_grad:
+                    ge, res = self.grad_target(embed)
+                    assert res is None and self._deferred_flush is None, "the patch embedding has one consumer"
+                dpe, dpre = self.pgrad(pe), [self.pgrad(p) for p in prefix_params]
+                if ge is None and dpe is None and all(d is None for d in dpre):
+                    return
+                self.emit(N.OP_PREFIX_TOKENS_BWD, [dy.addr(), _addr(ge), dpe] + dpre + pad, [dy.ld, _ld(ge), P, B, T, Cc, dt])
+
+            self._node(y, bwd)
+        return y
+
+    def prefix_pool(self, x: TRef, ln: nn.LayerNorm, n_prefix: int, name: str = "pool") -> TRef:
+        """the mean of LayerNorm over the first `n_prefix` rows of every image of a [B, 1, L, C] map -> [B, 1, 1, C]
+        (`norm(out[:, :P]).mean(1)`, vt_prefix_pool_fwd).  Backward in one launch (vt_prefix_pool_bwd): the LayerNorm backward
+        of the prefix rows, zeros in every other row (or an addition to a gradient that is already there), d gamma / d beta
+        through a fixed-point channel-sums buffer that vt_channel_sums_to_f32 adds to the gradients."""
+        if x.H != 1 or not 1 <= n_prefix <= min(4, x.W):
+            raise ValueError(f"{name}: the first {n_prefix} tokens (1..4) of a [B, {x.H}, {x.W}, C] map")
+        if tuple(ln.normalized_shape) != (x.C,) or not ln.elementwise_affine or ln.bias is None:
+            raise NotImplementedError(f"{name}: LayerNorm({ln.normalized_shape}) over a {x.C}-channel map with weight and bias")
+        if x.logical_c != x.C or x.C % _EPC[self.dtype]:
+            raise NotImplementedError(f"{name}: {x.C} channels must be a multiple of {_EPC[self.dtype]} for dtype {self.dtype}")
+        self.tag += 1
+        dt, B, L, Cc = self.dtype, x.B, x.W, x.C
+        y = self.act(B, 1, 1, Cc, name + ".y")
+        gm = self.pref(ln.weight)
+        self.emit(N.OP_PREFIX_POOL_FWD, [x.addr(), gm, self.pref(ln.bias), y.addr()], [x.ld, y.ld, B, L, n_prefix, Cc, dt], [ln.eps])
+        if self.need_grad:
+
+            def bwd(dy):
+                sums = self.zeroed_f32(N.channel_sums_floats(2, Cc), "poolsums")
+                if x.needs_grad:
+                    gx, acc = self.grad_accum_target(x)
+                else:
+                    gx, acc = self.act(B, 1, L, Cc, name + ".dx"), 0
+                self.emit(N.OP_PREFIX_POOL_BWD, [dy.addr(), x.addr(), gm, gx.addr(), self.bp(sums)],
+                          [dy.ld, x.ld, gx.ld, acc, B, L, n_prefix, Cc, dt], [ln.eps])
+                if x.needs_grad:
+                    self.grad_written(x)
+                dsts = [self.pgrad(ln.weight), self.pgrad(ln.bias)]
+                if any(d is not None for d in dsts):
+                    self.emit(N.OP_CHANNEL_SUMS, [self.bp(sums)] + dsts, [2, Cc])
+
+            self._node(y, bwd)
+        return y
+
     # -- CaiT pieces (reference backbones/cait.py:16-51, 74-77): vt_talking_attention.hip -----------------------------
     def talking_attention(self, q: TRef, k: TRef, v: TRef, n_heads: int, proj_l: nn.Conv2d, proj_w: nn.Conv2d,
                           name: str = "talking_attention") -> TRef:
