@@ -520,6 +520,51 @@ int vt_bn_bwd_finalize_apply(const float* sums, int32_t C, double count, double 
                              float* dbeta, float* coef, const void* dy, int32_t lddy, const void* z, int32_t ldz,
                              void* dz, int32_t lddz, int64_t M, int32_t relu, int32_t dtype, void* stream);
 
+/* ---- BatchNorm passes whose residual joins BEFORE the activation (vt_resnet.hip) ------------------------------------
+ * The last unit of a torchvision BasicBlock / Bottleneck: y = relu(bn(conv(h)) + identity).  The passes above implement
+ * relu(bn(conv)) + residual (a DarknetBlock): their mask is z*scale + shift > 0 and the residual's gradient is dy.  Here
+ * the mask depends on the sum and the identity's gradient is the masked dy:
+ *   vt_bn_add_act_apply                y  = relu(z*scale + shift + r)                        (r may alias y)
+ *   vt_bn_add_act_bwd_reduce           g  = dy * [y > 0]; sums[0][c] += sum g, sums[1][c] += sum g*xhat (statistics buffer)
+ *   vt_bn_add_act_bwd_apply            dz = coef0*g - coef1*z + coef2; dr = g, or dr += g with `accumulate`
+ * The mask is read from the STORED y in its own dtype (what torch's in-place ReLU does): exact against the forward's
+ * decision.  vt_bn_add_act_finalize_apply / vt_bn_add_act_bwd_finalize_apply run the finalize step inside the launch, with
+ * the arguments, the arithmetic (vt_bn_finalize / vt_bn_bwd_finalize, bit for bit) and the fall-back to two launches of
+ * vt_bn_finalize_apply / vt_bn_bwd_finalize_apply.  bf16 and f32, channel-last rows of ld* elements; dz and dr are two
+ * tensors; no float atomics: two runs give bit-identical results. */
+int vt_bn_add_act_apply(const void* z, int32_t ldz, const float* scale, const float* shift, const void* r, int32_t ldr, void* y,
+                        int32_t ldy, int64_t M, int32_t C, int32_t dtype, void* stream);
+int vt_bn_add_act_finalize_apply(const float* stats, int32_t C, double count, const float* gamma, const float* beta, float eps,
+                                 float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                 float* scale, float* shift, float* mean, float* invstd, const void* z, int32_t ldz, const void* r,
+                                 int32_t ldr, void* y, int32_t ldy, int64_t M, int32_t dtype, void* stream);
+int vt_bn_add_act_bwd_reduce(const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z, int32_t ldz,
+                             const float* mean, const float* invstd, int64_t M, int32_t C, int32_t dtype, float* sums,
+                             void* stream);
+int vt_bn_add_act_bwd_apply(const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z, int32_t ldz,
+                            const float* coef, void* dz, int32_t lddz, void* dr, int32_t lddr, int32_t accumulate, int64_t M,
+                            int32_t C, int32_t dtype, void* stream);
+int vt_bn_add_act_bwd_finalize_apply(const float* sums, int32_t C, double count, double pscale, const float* scale,
+                                     const float* mean, const float* invstd, int32_t train, float* dgamma, float* dbeta,
+                                     float* coef, const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z,
+                                     int32_t ldz, void* dz, int32_t lddz, void* dr, int32_t lddr, int32_t accumulate, int64_t M,
+                                     int32_t dtype, void* stream);
+
+/* ---- the ResNet stem Conv2d(3, Cout, 7, stride 2, padding 3) as a 4x4 stride-1 convolution (vt_resnet.hip) -----------
+ * 49 taps do not fit VT_MAX_TAPS.  Padded to 8x8 with a zero first row and column the filter is a 4x4 stride-1 filter over
+ * the space-to-depth image xs[b][hs][ws][(py, px, c)] = x[b][2hs + py][2ws + px][c] (12 channels, padded with zeros to
+ * vt_stem7_s2d_channels(dtype): 16 for bf16, 12 for f32), the sixteen taps at row / column offsets -2 .. +1: a vt_conv_desc
+ * with Hi = Ho = ceil(H / 2), h0 = w0 = -2, dh = t / 4, dw = t % 4, which vt_conv_igemm and vt_conv_wgrad run.  Odd H or W: a
+ * zero row / column at the far edge, which is what the convolution's own padding holds there.
+ *   vt_stem7_s2d           the image gather; x has its 3 channels in one 16-byte chunk per pixel (ldx elements apart)
+ *   vt_stem7_pack_filter   w [Cout][7][7][3] (f32 or bf16) -> out [Cout][4][4][Cs] (dst_dtype)
+ *   vt_stem7_unpack_wgrad  dw [Cout][7][7][3] += dws [Cout][4][4][Cs], both f32 (the transpose of the repack) */
+int32_t vt_stem7_s2d_channels(int32_t dtype);
+int vt_stem7_s2d(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t B, int32_t H, int32_t W, int32_t dtype,
+                 void* stream);
+int vt_stem7_pack_filter(const void* w, int32_t src_dtype, void* out, int32_t dst_dtype, int32_t Cout, void* stream);
+int vt_stem7_unpack_wgrad(const float* dws, int32_t Cs, float* dw, int32_t Cout, void* stream);
+
 /* Backward of the stem unit Conv3x3(3 -> C, s1, pad 1) -> BatchNorm2d -> ReLU in one streaming pass
  * (darknet.py:75 `ConvNormAct(3, 32, 3, 1)`; autograd backward of components.py:26-44 with respect to the
  * conv weight and the BatchNorm parameters -- the unit's input is the image, no data gradient exists).
@@ -868,6 +913,14 @@ enum vt_op_kind {
     VT_OP_PREFIX_TOKENS_BWD, /* vt_prefix_tokens_bwd */
     VT_OP_PREFIX_POOL_FWD,   /* vt_prefix_pool_fwd */
     VT_OP_PREFIX_POOL_BWD,   /* vt_prefix_pool_bwd */
+    VT_OP_BN_ADD_ACT_APPLY,         /* vt_bn_add_act_apply */
+    VT_OP_BN_ADD_ACT_FIN_APPLY,     /* vt_bn_add_act_finalize_apply */
+    VT_OP_BN_ADD_ACT_BWD_REDUCE,    /* vt_bn_add_act_bwd_reduce */
+    VT_OP_BN_ADD_ACT_BWD_APPLY,     /* vt_bn_add_act_bwd_apply */
+    VT_OP_BN_ADD_ACT_BWD_FIN_APPLY, /* vt_bn_add_act_bwd_finalize_apply */
+    VT_OP_STEM7_S2D,                /* vt_stem7_s2d */
+    VT_OP_STEM7_PACK_FILTER,        /* vt_stem7_pack_filter */
+    VT_OP_STEM7_UNPACK_WGRAD,       /* vt_stem7_unpack_wgrad */
     VT_OP_KIND_END
 };
 

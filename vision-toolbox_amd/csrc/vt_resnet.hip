@@ -1,0 +1,498 @@
+// vt_resnet.hip -- what a torchvision ResNet needs beyond the Darknet / VoVNet kernels.
+//
+// 1. BatchNorm passes whose residual joins BEFORE the activation.  A DarknetBlock is x + relu(bn(conv)) and every pass of
+//    vt_elementwise.hip implements that: the ReLU mask is z*scale + shift > 0 and the shortcut's gradient is dy.  A ResNet
+//    block ends in relu(bn(conv) + identity): the mask depends on the sum, and the identity's gradient is the MASKED dy.
+//      forward          y  = relu(z*scale + shift + r)                         (r may alias y)
+//      backward reduce  g  = dy * [y > 0];  sums[0][c] += sum g,  sums[1][c] += sum g * xhat
+//      backward apply   dz = coef0*g - coef1*z + coef2;  dr = g  or  dr += g   (one pass, two outputs)
+//    The mask is read from the STORED y in its own dtype -- what torch's in-place ReLU does; it is exact against the
+//    forward's decision, which a recomputed z*scale + shift + r (r rounded, the sum rounded again) would not be.
+//    Forward and backward apply exist with the finalize step inside the launch (vt_bn_fin.h: every workgroup finalizes the
+//    channels of its own channel group from the complete sums, row block 0 stores them) and with ready coefficients
+//    (eval mode, a frozen bn.eval(), SyncBatchNorm).  Streaming kernels on the RowMap of vt_elementwise.hip: 16 bytes per
+//    lane, kUnroll rows in flight, plain vector stores; the only atomics are the integer ones of the statistics buffer.
+// 2. The stem Conv2d(3, 64, 7, 2, 3): 49 taps against VT_MAX_TAPS = 36.  Padded to 8x8 with a zero first row and column it
+//    is a 4x4 stride-1 filter over the space-to-depth image (12 channels (py, px, c)), taps at offsets -2 .. +1, which the
+//    convolution descriptor expresses and the existing forward and filter-gradient kernels run.  Here: the image gather,
+//    the filter repack [Cout][7][7][3] -> [Cout][4][4][Cs] and its transpose for the filter gradient.
+#include "vt_bn_fin.h"
+#include "vt_common.h"
+#include "vt_rowmap.h"
+
+namespace {
+
+// ---------------------------------------------------------------------------------
+// y = relu(z*scale + shift + r); kFin: grid (row blocks, channel groups of Cg channels), coefficients finalized in the launch
+// (r and y are not __restrict__: they may be the same tensor -- every element is read and written by one thread)
+// ---------------------------------------------------------------------------------
+template <typename T, bool kFin>
+__global__ void __launch_bounds__(kThreads)
+bn_add_act_kernel(const VtFinFwd f, const float* __restrict__ scale, const float* __restrict__ shift, const T* __restrict__ z,
+                  int ldz, const T* r, int ldr, T* y, int ldy, long M, RowMap rm, int Cg) {
+    constexpr int EPC = VecIO<T>::EPC;
+    __shared__ float s_sc[kFinCg], s_sf[kFinCg];
+    const int t = threadIdx.x;
+    const int cg0 = blockIdx.y * Cg;
+    if constexpr (kFin) {
+        vt_pair_sums<false>(f.stats, f.C, cg0, cg0 + Cg, [&](int c) { return vt_fin_fwd_pre(f, c); },
+                            [&](int c, double s, double ss, const VtFinFwdPre& p) {
+                                float sc, sf;
+                                vt_fin_fwd_channel(f, c, s, ss, p.g, p.b, p.rm, p.rv, sc, sf, blockIdx.x == 0);
+                                s_sc[c - cg0] = sc, s_sf[c - cg0] = sf;
+                            });
+        __syncthreads();
+    }
+    z += cg0, y += cg0, r += cg0;
+    const int rl = t / rm.CT;
+    if (rl >= rm.RT) return;
+    const long row0 = (long)blockIdx.x * rm.RT * rm.iters + rl;
+    for (int col = t % rm.CT; col < rm.CPR; col += rm.CT) {
+        float sc[EPC], sf[EPC];
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) {
+            if constexpr (kFin) sc[e] = s_sc[col * EPC + e], sf[e] = s_sf[col * EPC + e];
+            else sc[e] = scale[col * EPC + e], sf[e] = shift[col * EPC + e];
+        }
+        const T* pz = z + row0 * ldz + col * EPC;
+        const T* pr = r + row0 * ldr + col * EPC;
+        T* py = y + row0 * ldy + col * EPC;
+        const long sz = (long)rm.RT * ldz, sr = (long)rm.RT * ldr, sy = (long)rm.RT * ldy;
+        // kUnroll rows per trip: all loads are issued before the first use (bytes in flight)
+        for (int it = 0; it < rm.iters; it += kUnroll) {
+            uint4 vz[kUnroll], vr[kUnroll];
+            bool ok[kUnroll];
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) {
+                ok[u] = (it + u < rm.iters) && (row0 + (long)(it + u) * rm.RT < M);
+                vz[u] = vr[u] = make_uint4(0, 0, 0, 0);
+                if (ok[u]) {
+                    vz[u] = ld16(pz + (it + u) * sz);
+                    vr[u] = ld16(pr + (it + u) * sr);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) {
+                float v[EPC], rr[EPC];
+                VecIO<T>::unpack(vz[u], v);
+                VecIO<T>::unpack(vr[u], rr);
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) v[e] = fmaxf(fmaf(v[e], sc[e], sf[e]) + rr[e], 0.f);
+                if (ok[u]) st16(py + (it + u) * sy, VecIO<T>::pack(v));
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// backward, pass 1: per-channel sum(g) and sum(g*xhat), g = dy * [y > 0] (the structure of bn_bwd_reduce_kernel)
+// ---------------------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+bn_add_act_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ y, int ldy, const T* __restrict__ z, int ldz,
+                             const float* __restrict__ mean, const float* __restrict__ invstd, long M, int C, RowMap rm,
+                             float* __restrict__ sums, int Ctot) {
+    constexpr int EPC = VecIO<T>::EPC;
+    // [rows][2][CT*EPC] partial sums, folded by the first 2*CT*EPC threads (no LDS atomics)
+    extern __shared__ __attribute__((aligned(16))) float sred[];
+    const int t = threadIdx.x;
+    const int r = t / rm.CT;
+    const int tc = t % rm.CT;
+    const int W = rm.CT * EPC;  // channels covered per pass
+    const long row0 = (long)blockIdx.x * rm.RT * rm.iters + r;
+    const int rep = blockIdx.x % kStatReplicas;
+    const int cg0 = blockIdx.y * rm.CPR;  // first 16-byte chunk of this channel group (C channels each of Ctot)
+    dy += (long)cg0 * EPC, y += (long)cg0 * EPC, z += (long)cg0 * EPC;
+    mean += cg0 * EPC, invstd += cg0 * EPC;
+    for (int cbase = 0; cbase < rm.CPR; cbase += rm.CT) {
+        const int col = cbase + tc;
+        const bool active = (r < rm.RT) && (col < rm.CPR);
+        float s1[EPC], s2[EPC];
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) s1[e] = s2[e] = 0.f;
+        if (active) {
+            float mu[EPC];
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) mu[e] = mean[col * EPC + e];
+            const T* pg = dy + row0 * lddy + col * EPC;
+            const T* py = y + row0 * ldy + col * EPC;
+            const T* pz = z + row0 * ldz + col * EPC;
+            const long sg = (long)rm.RT * lddy, sy = (long)rm.RT * ldy, sz = (long)rm.RT * ldz;
+            for (int it = 0; it < rm.iters; it += kUnroll) {
+                uint4 vg[kUnroll], vy[kUnroll], vz[kUnroll];
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u) {
+                    const long row = row0 + (long)(it + u) * rm.RT;
+                    vg[u] = vy[u] = vz[u] = make_uint4(0, 0, 0, 0);  // y = 0 masks the row out
+                    if ((it + u < rm.iters) && row < M) {
+                        vg[u] = ld16(pg + (it + u) * sg);
+                        vy[u] = ld16(py + (it + u) * sy);
+                        vz[u] = ld16(pz + (it + u) * sz);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u) {
+                    float g[EPC], yy[EPC], zz[EPC];
+                    VecIO<T>::unpack(vg[u], g);
+                    VecIO<T>::unpack(vy[u], yy);
+                    VecIO<T>::unpack(vz[u], zz);
+#pragma unroll
+                    for (int e = 0; e < EPC; ++e) {
+                        const float gg = yy[e] > 0.f ? g[e] : 0.f;
+                        s1[e] += gg;
+                        s2[e] = fmaf(gg, zz[e] - mu[e], s2[e]);  // invstd applied once, below
+                    }
+                }
+            }
+        }
+        // with CT a power of two below 64 a wave holds 64 / CT row lanes of every column it touches: folded in registers
+        // first (xor shuffles), so the LDS staging is kThreads / 64 rows instead of RT
+        const bool inwave = rm.CT < 64 && (rm.CT & (rm.CT - 1)) == 0;
+        int rows_l = rm.RT, r_l = r;
+        if (inwave) {
+            for (int off = rm.CT; off < 64; off <<= 1) {
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) {
+                    s1[e] += __shfl_xor(s1[e], off, 64);
+                    s2[e] += __shfl_xor(s2[e], off, 64);
+                }
+            }
+            rows_l = kThreads / 64;
+            r_l = (t & 63) < rm.CT ? (t >> 6) : -1;  // one writer per (wave, column)
+        } else if (r >= rm.RT) {
+            r_l = -1;
+        }
+        if (r_l >= 0) {
+            float4* d1 = (float4*)(sred + ((long)(r_l * 2 + 0) * W + tc * EPC));
+            float4* d2 = (float4*)(sred + ((long)(r_l * 2 + 1) * W + tc * EPC));
+#pragma unroll
+            for (int q = 0; q < EPC / 4; ++q) {
+                d1[q] = make_float4(s1[4 * q], s1[4 * q + 1], s1[4 * q + 2], s1[4 * q + 3]);
+                d2[q] = make_float4(s2[4 * q], s2[4 * q + 1], s2[4 * q + 2], s2[4 * q + 3]);
+            }
+        }
+        __syncthreads();
+        for (int i = t; i < 2 * W; i += kThreads) {
+            const int which = i / W, lc = i % W;
+            const int c = cbase * EPC + lc;
+            if (c < C) {
+                float acc = 0.f;
+                for (int rr = 0; rr < rows_l; ++rr) acc += sred[(long)(rr * 2 + which) * W + lc];
+                if (which) acc *= invstd[c];
+                vt_stat_add(sums, ((long)rep * 2 + which) * Ctot + cg0 * EPC + c, acc);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// backward, pass 2: dz = a*g - b*z + d and dr (=|+=) g, g = dy * [y > 0]; kFin: grid (row blocks, channel groups), the
+// backward finalize step inside the launch.  (dr is not __restrict__: with `acc` it is read and written by one thread.)
+// ---------------------------------------------------------------------------------
+template <typename T, bool kFin>
+__global__ void __launch_bounds__(kThreads)
+bn_add_act_bwd_apply_kernel(const VtFinBwd f, const float* __restrict__ coef, const T* __restrict__ dy, int lddy,
+                            const T* __restrict__ y, int ldy, const T* __restrict__ z, int ldz, T* __restrict__ dz, int lddz, T* dr,
+                            int lddr, int acc, long M, int C, RowMap rm, int Cg) {
+    constexpr int EPC = VecIO<T>::EPC;
+    __shared__ float s_a[kFinCg], s_b[kFinCg], s_d[kFinCg];
+    const int t = threadIdx.x;
+    const int cg0 = blockIdx.y * Cg;
+    if constexpr (kFin) {
+        vt_pair_sums<false>(f.sums, f.C, cg0, cg0 + Cg, [&](int c) { return vt_fin_bwd_pre(f, c); },
+                            [&](int c, double s1, double s2, const VtFinBwdPre& p) {
+                                float b, d;
+                                vt_fin_bwd_channel(f, c, s1, s2, p.a, p.mu, p.istd, p.dg, p.db, b, d, blockIdx.x == 0);
+                                s_a[c - cg0] = p.a, s_b[c - cg0] = b, s_d[c - cg0] = d;
+                            });
+        __syncthreads();
+    }
+    dy += cg0, y += cg0, z += cg0, dz += cg0, dr += cg0;
+    const int r = t / rm.CT;
+    if (r >= rm.RT) return;
+    const long row0 = (long)blockIdx.x * rm.RT * rm.iters + r;
+    for (int col = t % rm.CT; col < rm.CPR; col += rm.CT) {
+        float ca[EPC], cb[EPC], cd[EPC];
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) {
+            const int c = col * EPC + e;
+            if constexpr (kFin) ca[e] = s_a[c], cb[e] = s_b[c], cd[e] = s_d[c];
+            else ca[e] = coef[c], cb[e] = coef[C + c], cd[e] = coef[2 * C + c];
+        }
+        for (int it = 0; it < rm.iters; it += kUnroll) {
+            uint4 vg[kUnroll], vy[kUnroll], vz[kUnroll], va[kUnroll];
+            bool ok[kUnroll];
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) {
+                const long row = row0 + (long)(it + u) * rm.RT;
+                ok[u] = (it + u < rm.iters) && row < M;
+                vg[u] = vy[u] = vz[u] = va[u] = make_uint4(0, 0, 0, 0);
+                if (ok[u]) {
+                    vg[u] = ld16(dy + row * lddy + col * EPC);
+                    vy[u] = ld16(y + row * ldy + col * EPC);
+                    vz[u] = ld16(z + row * ldz + col * EPC);
+                    if (acc) va[u] = ld16(dr + row * lddr + col * EPC);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) {
+                if (!ok[u]) continue;
+                const long row = row0 + (long)(it + u) * rm.RT;
+                float g[EPC], yy[EPC], zz[EPC], aa[EPC], o[EPC];
+                VecIO<T>::unpack(vg[u], g);
+                VecIO<T>::unpack(vy[u], yy);
+                VecIO<T>::unpack(vz[u], zz);
+                VecIO<T>::unpack(va[u], aa);
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) {
+                    const float gg = yy[e] > 0.f ? g[e] : 0.f;
+                    o[e] = fmaf(ca[e], gg, fmaf(-cb[e], zz[e], cd[e]));
+                    aa[e] += gg;  // (acc = 0: aa was zero)
+                }
+                st16(dz + row * lddz + col * EPC, VecIO<T>::pack(o));
+                st16(dr + row * lddr + col * EPC, VecIO<T>::pack(aa));
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// The 7x7 stride-2 stem as a 4x4 stride-1 convolution over the space-to-depth image
+// ---------------------------------------------------------------------------------
+// channel j < 12 of the space-to-depth image is (py, px, c) = (j / 6, j / 3 % 2, j % 3); Cs >= 12 channels, the rest zero
+constexpr int kS2dReal = 12;
+
+// out[b][hs][ws][(py, px, c)] = x[b][2 hs + py][2 ws + px][c] (zero outside the image: odd H or W); a thread per output
+// pixel: four 16-byte pixel loads (3 real channels in the first chunk), Cs / EPC 16-byte stores
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+stem7_s2d_kernel(const T* __restrict__ x, int ldx, T* __restrict__ out, int ldo, int B, int H, int W, int Hs, int Ws) {
+    constexpr int EPC = VecIO<T>::EPC;
+    constexpr int CS = (kS2dReal + EPC - 1) / EPC * EPC;
+    const long n = (long)B * Hs * Ws;
+    const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const int ws = (int)(i % Ws);
+    const long t2 = i / Ws;
+    const int hs = (int)(t2 % Hs);
+    const long b = t2 / Hs;
+    float v[CS];
+#pragma unroll
+    for (int j = 0; j < CS; ++j) v[j] = 0.f;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int h = 2 * hs + (p >> 1), w = 2 * ws + (p & 1);
+        if (h < H && w < W) {
+            float px[EPC];
+            VecIO<T>::unpack(ld16(x + ((b * H + h) * W + w) * ldx), px);
+            v[3 * p] = px[0], v[3 * p + 1] = px[1], v[3 * p + 2] = px[2];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < CS / EPC; ++q) st16(out + i * ldo + q * EPC, VecIO<T>::pack(v + q * EPC));
+}
+
+// out[n][a][b][j] = w[n][2a + py - 1][2b + px - 1][c] (zero where an index is -1: the padded first row / column, and for
+// j >= 12); w is the channels_last filter image [Cout][7][7][3]
+template <typename S, typename D>
+__global__ void __launch_bounds__(kThreads)
+stem7_pack_filter_kernel(const S* __restrict__ w, D* __restrict__ out, int Cout, int Cs) {
+    const int n = Cout * 16 * Cs;
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const int j = i % Cs, tap = (i / Cs) % 16, o = i / (16 * Cs);
+    float v = 0.f;
+    if (j < kS2dReal) {
+        const int kh = 2 * (tap >> 2) + j / 6 - 1, kw = 2 * (tap & 3) + (j / 3) % 2 - 1;
+        if (kh >= 0 && kw >= 0) v = (float)w[((o * 7 + kh) * 7 + kw) * 3 + j % 3];
+    }
+    out[i] = from_float<D>(v);
+}
+
+// the transpose: dw[n][kh][kw][c] += dws[n][a][b][j], every tap of the 7x7 filter has exactly one source
+__global__ void __launch_bounds__(kThreads)
+stem7_unpack_wgrad_kernel(const float* __restrict__ dws, int Cs, float* __restrict__ dw, int Cout) {
+    const int n = Cout * 49 * 3;
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const int c = i % 3, kw = (i / 3) % 7, kh = (i / 21) % 7, o = i / 147;
+    const int a = (kh + 1) >> 1, py = (kh + 1) & 1, b = (kw + 1) >> 1, px = (kw + 1) & 1;
+    dw[i] += dws[(o * 16 + a * 4 + b) * Cs + py * 6 + px * 3 + c];
+}
+
+// the grid of a pass: as vt_bn_finalize_apply cuts it (VT_BN_FIN_APPLY_WGS workgroups over the channel groups)
+inline RowMap fin_rowmap(int Cg, int groups, int epc, long M) {
+    const int wgs = VT_KNOB("VT_BN_FIN_APPLY_WGS", 1536);
+    return RowMap::make(Cg, epc, M, wgs / groups > 0 ? wgs / groups : 1);
+}
+
+}  // namespace
+
+extern "C" {
+
+int vt_bn_add_act_apply(const void* z, int32_t ldz, const float* scale, const float* shift, const void* r, int32_t ldr, void* y,
+                        int32_t ldy, int64_t M, int32_t C, int32_t dtype, void* stream) {
+    VT_REQUIRE(M > 0 && scale && shift, VT_ERR_INVALID, "vt_bn_add_act_apply: bad argument");
+    VT_TRY(check_mat("vt_bn_add_act_apply(z)", z, ldz, C, dtype));
+    VT_TRY(check_mat("vt_bn_add_act_apply(r)", r, ldr, C, dtype));
+    VT_TRY(check_mat("vt_bn_add_act_apply(y)", y, ldy, C, dtype));
+    const RowMap rm = RowMap::make(C, vt_epc(dtype), M);
+    const VtFinFwd f{};
+    VT_DISPATCH_T(dtype, "vt_bn_add_act_apply",
+                  hipLaunchKernelGGL((bn_add_act_kernel<T, false>), dim3(rm.blocks(M)), dim3(kThreads), 0, (hipStream_t)stream, f,
+                                     scale, shift, (const T*)z, ldz, (const T*)r, ldr, (T*)y, ldy, (long)M, rm, C));
+    VT_CHECK_LAUNCH("vt_bn_add_act_apply");
+    return VT_OK;
+}
+
+int vt_bn_add_act_finalize_apply(const float* stats, int32_t C, double count, const float* gamma, const float* beta, float eps,
+                                 float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                 float* scale, float* shift, float* mean, float* invstd, const void* z, int32_t ldz, const void* r,
+                                 int32_t ldr, void* y, int32_t ldy, int64_t M, int32_t dtype, void* stream) {
+    VT_REQUIRE(stats && scale && shift && mean && invstd && C > 0 && count > 0 && M > 0, VT_ERR_INVALID,
+               "vt_bn_add_act_finalize_apply: bad argument");
+    VT_REQUIRE((running_mean == nullptr) == (running_var == nullptr), VT_ERR_INVALID,
+               "vt_bn_add_act_finalize_apply: running_mean/var must both be given or both NULL");
+    VT_TRY(check_mat("vt_bn_add_act_finalize_apply(z)", z, ldz, C, dtype));
+    VT_TRY(check_mat("vt_bn_add_act_finalize_apply(r)", r, ldr, C, dtype));
+    VT_TRY(check_mat("vt_bn_add_act_finalize_apply(y)", y, ldy, C, dtype));
+    const int Cg = fin_group(C, vt_epc(dtype));
+    if (!Cg || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {  // (no channel group: the two launches)
+        VT_TRY(vt_bn_finalize(stats, C, count, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, scale,
+                              shift, mean, invstd, stream));
+        return vt_bn_add_act_apply(z, ldz, scale, shift, r, ldr, y, ldy, M, C, dtype, stream);
+    }
+    const int groups = C / Cg;
+    const RowMap rm = fin_rowmap(Cg, groups, vt_epc(dtype), M);
+    const VtFinFwd f{stats, gamma, beta, running_mean, running_var, num_batches_tracked, scale, shift, mean, invstd,
+                     1.0 / count, count > 1.0 ? count / (count - 1.0) : 1.0, eps, momentum, C};
+    VT_DISPATCH_T(dtype, "vt_bn_add_act_finalize_apply",
+                  hipLaunchKernelGGL((bn_add_act_kernel<T, true>), dim3(rm.blocks(M), groups), dim3(kThreads), 0,
+                                     (hipStream_t)stream, f, (const float*)nullptr, (const float*)nullptr, (const T*)z, ldz,
+                                     (const T*)r, ldr, (T*)y, ldy, (long)M, rm, Cg));
+    VT_CHECK_LAUNCH("vt_bn_add_act_finalize_apply");
+    return VT_OK;
+}
+
+int vt_bn_add_act_bwd_reduce(const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z, int32_t ldz,
+                             const float* mean, const float* invstd, int64_t M, int32_t C, int32_t dtype, float* sums,
+                             void* stream) {
+    VT_REQUIRE(M > 0 && mean && invstd && sums, VT_ERR_INVALID, "vt_bn_add_act_bwd_reduce: bad argument");
+    VT_TRY(check_mat("vt_bn_add_act_bwd_reduce(dy)", dy, lddy, C, dtype));
+    VT_TRY(check_mat("vt_bn_add_act_bwd_reduce(y)", y, ldy, C, dtype));
+    VT_TRY(check_mat("vt_bn_add_act_bwd_reduce(z)", z, ldz, C, dtype));
+    const int epc = vt_epc(dtype);
+    // the grid of vt_bn_act_bwd_reduce: few, long blocks (each ends with 2*C 64-bit atomics), channel groups of 64 on the
+    // small maps with many channels
+    const int cgroups = (M <= 65536 && C >= 256 && C % 64 == 0) ? C / 64 : 1;
+    const int Cg = C / cgroups;
+    const int blocks_knob = VT_KNOB("VT_BN_RED_BLOCKS", 1024);
+    const RowMap rm = RowMap::make(Cg, epc, M, blocks_knob / cgroups > 0 ? blocks_knob / cgroups : 1);
+    const bool inwave = rm.CT < 64 && (rm.CT & (rm.CT - 1)) == 0;  // (as in the kernel)
+    const int smem = (inwave ? kThreads / 64 : rm.RT) * 2 * rm.CT * epc * (int)sizeof(float);
+    VT_DISPATCH_T(dtype, "vt_bn_add_act_bwd_reduce",
+                  hipLaunchKernelGGL(bn_add_act_bwd_reduce_kernel<T>, dim3(rm.blocks(M), cgroups), dim3(kThreads), smem,
+                                     (hipStream_t)stream, (const T*)dy, lddy, (const T*)y, ldy, (const T*)z, ldz, mean, invstd,
+                                     (long)M, Cg, rm, sums, C));
+    VT_CHECK_LAUNCH("vt_bn_add_act_bwd_reduce");
+    return VT_OK;
+}
+
+int vt_bn_add_act_bwd_apply(const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z, int32_t ldz,
+                            const float* coef, void* dz, int32_t lddz, void* dr, int32_t lddr, int32_t accumulate, int64_t M,
+                            int32_t C, int32_t dtype, void* stream) {
+    VT_REQUIRE(M > 0 && coef, VT_ERR_INVALID, "vt_bn_add_act_bwd_apply: bad argument");
+    VT_TRY(check_mat("vt_bn_add_act_bwd_apply(dy)", dy, lddy, C, dtype));
+    VT_TRY(check_mat("vt_bn_add_act_bwd_apply(y)", y, ldy, C, dtype));
+    VT_TRY(check_mat("vt_bn_add_act_bwd_apply(z)", z, ldz, C, dtype));
+    VT_TRY(check_mat("vt_bn_add_act_bwd_apply(dz)", dz, lddz, C, dtype));
+    VT_TRY(check_mat("vt_bn_add_act_bwd_apply(dr)", dr, lddr, C, dtype));
+    VT_REQUIRE(dz != dr, VT_ERR_INVALID, "vt_bn_add_act_bwd_apply: dz and dr are two outputs");
+    const RowMap rm = RowMap::make(C, vt_epc(dtype), M);
+    const VtFinBwd f{};
+    VT_DISPATCH_T(dtype, "vt_bn_add_act_bwd_apply",
+                  hipLaunchKernelGGL((bn_add_act_bwd_apply_kernel<T, false>), dim3(rm.blocks(M)), dim3(kThreads), 0,
+                                     (hipStream_t)stream, f, coef, (const T*)dy, lddy, (const T*)y, ldy, (const T*)z, ldz, (T*)dz,
+                                     lddz, (T*)dr, lddr, accumulate ? 1 : 0, (long)M, C, rm, C));
+    VT_CHECK_LAUNCH("vt_bn_add_act_bwd_apply");
+    return VT_OK;
+}
+
+int vt_bn_add_act_bwd_finalize_apply(const float* sums, int32_t C, double count, double pscale, const float* scale,
+                                     const float* mean, const float* invstd, int32_t train, float* dgamma, float* dbeta,
+                                     float* coef, const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z,
+                                     int32_t ldz, void* dz, int32_t lddz, void* dr, int32_t lddr, int32_t accumulate, int64_t M,
+                                     int32_t dtype, void* stream) {
+    VT_REQUIRE(sums && scale && mean && invstd && coef && C > 0 && count > 0 && M > 0, VT_ERR_INVALID,
+               "vt_bn_add_act_bwd_finalize_apply: bad argument");
+    VT_TRY(check_mat("vt_bn_add_act_bwd_finalize_apply(dy)", dy, lddy, C, dtype));
+    VT_TRY(check_mat("vt_bn_add_act_bwd_finalize_apply(y)", y, ldy, C, dtype));
+    VT_TRY(check_mat("vt_bn_add_act_bwd_finalize_apply(z)", z, ldz, C, dtype));
+    VT_TRY(check_mat("vt_bn_add_act_bwd_finalize_apply(dz)", dz, lddz, C, dtype));
+    VT_TRY(check_mat("vt_bn_add_act_bwd_finalize_apply(dr)", dr, lddr, C, dtype));
+    VT_REQUIRE(dz != dr, VT_ERR_INVALID, "vt_bn_add_act_bwd_finalize_apply: dz and dr are two outputs");
+    const int Cg = fin_group(C, vt_epc(dtype));
+    if (!Cg || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {  // (no channel group: the two launches)
+        VT_TRY(vt_bn_bwd_finalize(sums, C, count, pscale, scale, mean, invstd, train, dgamma, dbeta, coef, stream));
+        return vt_bn_add_act_bwd_apply(dy, lddy, y, ldy, z, ldz, coef, dz, lddz, dr, lddr, accumulate, M, C, dtype, stream);
+    }
+    const int groups = C / Cg;
+    const RowMap rm = fin_rowmap(Cg, groups, vt_epc(dtype), M);
+    const VtFinBwd f{sums, scale, mean, invstd, dgamma, dbeta, coef, 1.0 / count, pscale, C, train};
+    VT_DISPATCH_T(dtype, "vt_bn_add_act_bwd_finalize_apply",
+                  hipLaunchKernelGGL((bn_add_act_bwd_apply_kernel<T, true>), dim3(rm.blocks(M), groups), dim3(kThreads), 0,
+                                     (hipStream_t)stream, f, (const float*)nullptr, (const T*)dy, lddy, (const T*)y, ldy,
+                                     (const T*)z, ldz, (T*)dz, lddz, (T*)dr, lddr, accumulate ? 1 : 0, (long)M, C, rm, Cg));
+    VT_CHECK_LAUNCH("vt_bn_add_act_bwd_finalize_apply");
+    return VT_OK;
+}
+
+int32_t vt_stem7_s2d_channels(int32_t dtype) { return dtype == VT_BF16 ? 16 : 12; }
+
+int vt_stem7_s2d(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t B, int32_t H, int32_t W, int32_t dtype,
+                 void* stream) {
+    VT_REQUIRE(dtype == VT_BF16 || dtype == VT_F32, VT_ERR_UNSUPPORTED, "vt_stem7_s2d: unsupported dtype %d", dtype);
+    const int epc = vt_epc(dtype), Cs = vt_stem7_s2d_channels(dtype);
+    VT_REQUIRE(x && out && vt_aligned16(x) && vt_aligned16(out), VT_ERR_INVALID, "vt_stem7_s2d: null or misaligned pointer");
+    VT_REQUIRE(B > 0 && H > 0 && W > 0, VT_ERR_INVALID, "vt_stem7_s2d: non-positive extent");
+    VT_REQUIRE(ldx >= epc && ldx % epc == 0 && ldo >= Cs && ldo % epc == 0, VT_ERR_INVALID,
+               "vt_stem7_s2d: ldx=%d ldo=%d: the image has one 16-byte chunk of channels, the output %d", ldx, ldo, Cs);
+    const int Hs = (H + 1) / 2, Ws = (W + 1) / 2;
+    const long n = (long)B * Hs * Ws;
+    VT_REQUIRE((long)B * H * W * ldx < 0x7fffffffL && n * ldo < 0x7fffffffL, VT_ERR_UNSUPPORTED,
+               "vt_stem7_s2d: tensor exceeds 2^31 elements");  // (the bound of vt_conv_igemm, which reads the output)
+    VT_DISPATCH_T(dtype, "vt_stem7_s2d",
+                  hipLaunchKernelGGL(stem7_s2d_kernel<T>, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                                     (hipStream_t)stream, (const T*)x, ldx, (T*)out, ldo, B, H, W, Hs, Ws));
+    VT_CHECK_LAUNCH("vt_stem7_s2d");
+    return VT_OK;
+}
+
+int vt_stem7_pack_filter(const void* w, int32_t src_dtype, void* out, int32_t dst_dtype, int32_t Cout, void* stream) {
+    VT_REQUIRE(w && out && Cout > 0 && Cout <= 65536, VT_ERR_INVALID, "vt_stem7_pack_filter: bad argument");
+    VT_REQUIRE((src_dtype == VT_F32 || src_dtype == VT_BF16) && (dst_dtype == VT_F32 || dst_dtype == VT_BF16) &&
+                   (src_dtype == dst_dtype || src_dtype == VT_F32),
+               VT_ERR_UNSUPPORTED, "vt_stem7_pack_filter: dtypes %d -> %d", src_dtype, dst_dtype);
+    const int Cs = vt_stem7_s2d_channels(dst_dtype);
+    const dim3 grid((unsigned)((Cout * 16 * Cs + kThreads - 1) / kThreads));
+    hipStream_t st = (hipStream_t)stream;
+    if (src_dtype == VT_BF16)
+        hipLaunchKernelGGL((stem7_pack_filter_kernel<bf16_t, bf16_t>), grid, dim3(kThreads), 0, st, (const bf16_t*)w, (bf16_t*)out, Cout, Cs);
+    else if (dst_dtype == VT_BF16)
+        hipLaunchKernelGGL((stem7_pack_filter_kernel<float, bf16_t>), grid, dim3(kThreads), 0, st, (const float*)w, (bf16_t*)out, Cout, Cs);
+    else
+        hipLaunchKernelGGL((stem7_pack_filter_kernel<float, float>), grid, dim3(kThreads), 0, st, (const float*)w, (float*)out, Cout, Cs);
+    VT_CHECK_LAUNCH("vt_stem7_pack_filter");
+    return VT_OK;
+}
+
+int vt_stem7_unpack_wgrad(const float* dws, int32_t Cs, float* dw, int32_t Cout, void* stream) {
+    VT_REQUIRE(dws && dw && Cout > 0 && Cout <= 65536 && Cs >= kS2dReal, VT_ERR_INVALID, "vt_stem7_unpack_wgrad: bad argument");
+    hipLaunchKernelGGL(stem7_unpack_wgrad_kernel, dim3((unsigned)((Cout * 147 + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                       (hipStream_t)stream, dws, Cs, dw, Cout);
+    VT_CHECK_LAUNCH("vt_stem7_unpack_wgrad");
+    return VT_OK;
+}
+
+}  // extern "C"

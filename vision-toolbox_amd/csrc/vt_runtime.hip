@@ -321,6 +321,31 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
                                             (const float*)P[2], (const float*)P[3], (const float*)P[4], I[1], (float*)P[5],
                                             (float*)P[6], (float*)P[7], P[8], I[2], P[9], I[3], P[10], I[4], (int64_t)F[2],
                                             I[5], I[6], st);
+        case VT_OP_BN_ADD_ACT_APPLY:  // ptr: z scale shift r y | i: ldz ldr ldy C dtype | f: M
+            return vt_bn_add_act_apply(P[0], I[0], (const float*)P[1], (const float*)P[2], P[3], I[1], P[4], I[2], (int64_t)F[0], I[3],
+                                       I[4], st);
+        case VT_OP_BN_ADD_ACT_FIN_APPLY:  // ptr: stats gamma beta rm rv nbt scale shift mean invstd z r y | i: C ldz ldr ldy dtype | f: count eps momentum M
+            return vt_bn_add_act_finalize_apply((const float*)P[0], I[0], F[0], (const float*)P[1], (const float*)P[2], (float)F[1],
+                                                (float)F[2], (float*)P[3], (float*)P[4], (int64_t*)P[5], (float*)P[6], (float*)P[7],
+                                                (float*)P[8], (float*)P[9], P[10], I[1], P[11], I[2], P[12], I[3], (int64_t)F[3],
+                                                I[4], st);
+        case VT_OP_BN_ADD_ACT_BWD_REDUCE:  // ptr: dy y z mean invstd sums | i: lddy ldy ldz C dtype | f: M
+            return vt_bn_add_act_bwd_reduce(P[0], I[0], P[1], I[1], P[2], I[2], (const float*)P[3], (const float*)P[4], (int64_t)F[0],
+                                            I[3], I[4], (float*)P[5], st);
+        case VT_OP_BN_ADD_ACT_BWD_APPLY:  // ptr: dy y z coef dz dr | i: lddy ldy ldz lddz lddr accumulate C dtype | f: M
+            return vt_bn_add_act_bwd_apply(P[0], I[0], P[1], I[1], P[2], I[2], (const float*)P[3], P[4], I[3], P[5], I[4], I[5],
+                                           (int64_t)F[0], I[6], I[7], st);
+        case VT_OP_BN_ADD_ACT_BWD_FIN_APPLY:  // ptr: sums scale mean invstd dgamma dbeta coef dy y z dz dr | i: C train lddy ldy ldz lddz lddr accumulate dtype | f: count pscale(0 = 1) M
+            return vt_bn_add_act_bwd_finalize_apply((const float*)P[0], I[0], F[0], F[1] == 0.0 ? 1.0 : F[1], (const float*)P[1],
+                                                    (const float*)P[2], (const float*)P[3], I[1], (float*)P[4], (float*)P[5],
+                                                    (float*)P[6], P[7], I[2], P[8], I[3], P[9], I[4], P[10], I[5], P[11], I[6], I[7],
+                                                    (int64_t)F[2], I[8], st);
+        case VT_OP_STEM7_S2D:  // ptr: x out | i: ldx ldo B H W dtype
+            return vt_stem7_s2d(P[0], I[0], P[1], I[1], I[2], I[3], I[4], I[5], st);
+        case VT_OP_STEM7_PACK_FILTER:  // ptr: w out | i: src_dtype dst_dtype Cout
+            return vt_stem7_pack_filter(P[0], I[0], P[1], I[1], I[2], st);
+        case VT_OP_STEM7_UNPACK_WGRAD:  // ptr: dws dw | i: Cs Cout
+            return vt_stem7_unpack_wgrad((const float*)P[0], I[0], (float*)P[1], I[1], st);
         case VT_OP_BN_BWD_FUSED:  // ptr: dy z scale shift mean invstd sums sync dgamma dbeta coef dz | i: lddy ldz lddz C relu dtype train | f: M count pscale(0 = 1)
             return vt_bn_act_bwd_fused(P[0], I[0], P[1], I[1], (const float*)P[2], (const float*)P[3], (const float*)P[4],
                                        (const float*)P[5], (int64_t)F[0], I[3], I[4], I[5], F[1], F[2] == 0.0 ? 1.0 : F[2], I[6],
@@ -476,7 +501,7 @@ struct Graph {
 
 extern "C" {
 
-int vt_version(void) { return 104; }  // 104: round 6 (finalize inside the passes, vt_op carries 24 pointers; 103: vt_conv_dgrad_bnred, vt_debug_hog left the library)
+int vt_version(void) { return 105; }  // 105: vt_resnet.hip (add-then-ReLU BatchNorm passes, the 7x7 stem as a 4x4 convolution); 104: round 6 (finalize inside the passes, vt_op carries 24 pointers; 103: vt_conv_dgrad_bnred, vt_debug_hog left the library)
 int vt_set_knob(const char* name, int32_t value) {
     VT_REQUIRE(name && strlen(name) < 48, VT_ERR_INVALID, "vt_set_knob: bad name");
     // (a knob set before its first use overrides the environment: the slot exists from here on)

@@ -142,7 +142,15 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_PREFIX_TOKENS_BWD,
     OP_PREFIX_POOL_FWD,
     OP_PREFIX_POOL_BWD,
-) = range(1, 85)
+    OP_BN_ADD_ACT_APPLY,
+    OP_BN_ADD_ACT_FIN_APPLY,
+    OP_BN_ADD_ACT_BWD_REDUCE,
+    OP_BN_ADD_ACT_BWD_APPLY,
+    OP_BN_ADD_ACT_BWD_FIN_APPLY,
+    OP_STEM7_S2D,
+    OP_STEM7_PACK_FILTER,
+    OP_STEM7_UNPACK_WGRAD,
+) = range(1, 93)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -211,6 +219,14 @@ OP_NAMES = {
     OP_PREFIX_TOKENS_BWD: "prefix_tokens_bwd",
     OP_PREFIX_POOL_FWD: "prefix_pool_fwd",
     OP_PREFIX_POOL_BWD: "prefix_pool_bwd",
+    OP_BN_ADD_ACT_APPLY: "bn_add_act_apply",
+    OP_BN_ADD_ACT_FIN_APPLY: "bn_add_act_fin_apply",
+    OP_BN_ADD_ACT_BWD_REDUCE: "bn_add_act_bwd_reduce",
+    OP_BN_ADD_ACT_BWD_APPLY: "bn_add_act_bwd_apply",
+    OP_BN_ADD_ACT_BWD_FIN_APPLY: "bn_add_act_bwd_fin_apply",
+    OP_STEM7_S2D: "stem7_s2d",
+    OP_STEM7_PACK_FILTER: "stem7_pack_filter",
+    OP_STEM7_UNPACK_WGRAD: "stem7_unpack_wgrad",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -376,6 +392,17 @@ SYMBOLS = {
                                     _vp, _i32, _i64, _i32, _i32, _vp]),
     "vt_bn_bwd_finalize_apply": (_i32, [_vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
                                         _i32, _i64, _i32, _i32, _vp]),
+    "vt_bn_add_act_apply": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i32, _i32, _vp]),
+    "vt_bn_add_act_finalize_apply": (_i32, [_vp, _i32, _f64, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp,
+                                            _i32, _vp, _i32, _i64, _i32, _vp]),
+    "vt_bn_add_act_bwd_reduce": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "vt_bn_add_act_bwd_apply": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i64, _i32, _i32, _vp]),
+    "vt_bn_add_act_bwd_finalize_apply": (_i32, [_vp, _i32, _f64, _f64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
+                                                _i32, _vp, _i32, _vp, _i32, _i32, _i64, _i32, _vp]),
+    "vt_stem7_s2d_channels": (_i32, [_i32]),
+    "vt_stem7_s2d": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "vt_stem7_pack_filter": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp]),
+    "vt_stem7_unpack_wgrad": (_i32, [_vp, _i32, _vp, _i32, _vp]),
     "vt_pack_dgrad_filter_batch": (_i32, [_vp, _i32, _vp]),
     "vt_bn_eval_coeffs_batch": (_i32, [_vp, _i32, _vp]),
     "vt_pack_dgrad_filter": (_i32, [_vp, _i32, _i32, _vp, _i32, C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp]),

@@ -14,8 +14,10 @@ CaiTCABlock / CaiTSABlock) runs its talking-heads and class attention on the ker
 PatchConvNet (backbones/patchconvnet.py:106, with PatchConvBlockLN / PatchConvBlockBN / AttentionPooling and a
 SqueezeExcitation of our own: torchvision is not imported) runs on the plane, gate and pooling kernels of vt_patchconv.hip.
 DeiT and DeiT3 (backbones/deit.py:14,118), the other family the reference builds on ViT, run on ViT's block path; DeiT's
-two prefix tokens and its two-token pooled head run on the kernels of vt_prefix_tokens.hip.  The reference's torchvision
-extractors are not part of this build (torchvision is not imported).
+two prefix tokens and its two-token pooled head run on the kernels of vt_prefix_tokens.hip.  ResNetExtractor
+(backbones/torchvision_models.py:22, with BasicBlock / Bottleneck written out under torchvision's child names: torchvision
+is not imported) runs its add-then-ReLU block ends and its 7x7 stem on the kernels of vt_resnet.hip.  The reference's other
+torchvision extractors (RegNet, MobileNet, EfficientNet) are not part of this build.
 """
 from .base import BaseBackbone
 from .convnext import ConvNeXt, ConvNeXtBlock, GlobalResponseNorm
@@ -25,6 +27,7 @@ from .deit import DeiT, DeiT3
 from .cait import CaiT, CaiTCABlock, CaiTSABlock, ClassAttention, TalkingHeadAttention
 from .patchconvnet import AttentionPooling, PatchConvBlockBN, PatchConvBlockLN, PatchConvNet, SqueezeExcitation
 from .swin import PatchMerging, SwinBlock, SwinTransformer, WindowAttention, window_partition, window_unpartition
+from .resnet import BasicBlock, Bottleneck, ResNetExtractor
 from .darknet import (
     CSPDarknetStage,
     Darknet,

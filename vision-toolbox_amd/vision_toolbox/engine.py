@@ -241,6 +241,7 @@ class ConvSpec:
     weight: object
     bias: object = None
     is_slice: bool = False
+    crop: int = 0  # output rows / columns left out at the far edge (Builder.stem7_unit: a window that is not centred)
 
     def __post_init__(self):
         if self.dilation * (self.k - 1) > 127:
@@ -270,7 +271,7 @@ class ConvSpec:
 
     def out_size(self, H: int, W: int) -> "tuple[int, int]":
         reach = 2 * self.padding - self.dilation * (self.k - 1) - 1
-        return (H + reach) // self.stride + 1, (W + reach) // self.stride + 1
+        return (H + reach) // self.stride + 1 - self.crop, (W + reach) // self.stride + 1 - self.crop
 
 
 @dataclass(frozen=True, eq=False)
@@ -411,6 +412,8 @@ class _ConvUnit:
     pool_am: Optional[Buf] = None  # ... and its arg-max taps
     wg_key: Optional[tuple] = None  # shape group of held-back filter gradients
     defer: bool = False  # the normalise pass is held back (_DeferredNorm)
+    pre_act: bool = False  # the residual joins BEFORE the activation: y = relu(bn(conv) + residual) (vt_resnet.hip)
+    stem7: bool = False  # the 7x7 stride-2 stem as a 4x4 convolution over the space-to-depth image (Builder.stem7_unit)
 
     @property
     def padded(self) -> bool:
@@ -857,16 +860,26 @@ class Builder:
         return conv, BNSpec.from_bn(norm)
 
     def conv_unit(self, x: TRef, conv, norm, relu, residual: Optional[TRef] = None, out: Optional[TRef] = None,
-                  name: str = "", pool_out: Optional[TRef] = None, defer_norm: bool = False) -> TRef:
+                  name: str = "", pool_out: Optional[TRef] = None, defer_norm: bool = False, residual_pre_act: bool = False,
+                  _stem7: Optional[Buf] = None) -> TRef:
         """y = [relu]([bn](conv(x))) [+ residual], written to `out` when given.  `conv`: nn.Conv2d or ConvSpec, `norm`:
         nn.BatchNorm2d, BNSpec, nn.Identity or None.  `pool_out`: MaxPool2d(3, 2, 1) of y goes there as well -- from the
         unit's own normalise pass where it has one (vt_bn_act_apply_pool), and then the unit's BatchNorm backward reads the
         pooled gradient through the arg-max taps instead of a materialised d(y).
         `defer_norm`: the caller hands y to conv_unit_pair, which may take over the normalise pass (_DeferredNorm); where
         the unit qualifies, the pass is held back until something asks for y's address.
+        `residual_pre_act`: the residual joins BEFORE the activation, y = relu(bn(conv(x)) + residual) -- the last unit of a
+        torchvision BasicBlock / Bottleneck.  The general, strided and pointwise-shaped convolutions produce z and its
+        statistics as always; the normalise pass and the BatchNorm backward are the add-then-ReLU passes of vt_resnet.hip.
+        The paths that cannot honour the mode (the pointwise fold, the fused inference epilogue, a deferred normalise
+        pass) are not taken: the unit runs the general kernel plus those passes.
         Validation and dispatch: grouped -> depthwise -> pointwise -> the general kernels."""
         conv, bn_spec = self._specs(conv, norm)
         relu = int(relu)  # activation code: 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 SiLU, 4 GELU (include/vt_amd.h)
+        pre_act = bool(residual_pre_act)
+        if pre_act and (residual is None or bn_spec is None or relu != 1 or conv.groups != 1 or pool_out is not None):
+            raise NotImplementedError(f"{name}: residual_pre_act is relu(bn(conv(x)) + residual): it needs a residual, a "
+                                      "BatchNorm, ReLU, groups = 1 and no fused pool")
         if conv.groups != 1:
             return self._grouped_unit(x, conv, bn_spec, relu, residual, out, name, pool_out)
         dt, epc = self.dtype, _EPC[self.dtype]
@@ -882,7 +895,7 @@ class Builder:
             raise ValueError(f"{name}: a {x.H}x{x.W} map is smaller than the dilated {k}x{k} kernel")
         if bn_spec is not None:
             spec = (conv, bn_spec, relu, residual, out, name)
-            if self._pw_ok(x, [spec]):
+            if not pre_act and self._pw_ok(x, [spec]):  # (the pointwise passes add the residual behind the ReLU)
                 y_pw = self.pw_units(x, [spec])[0]
                 if pool_out is not None:
                     self.maxpool3x3s2(y_pw, out=pool_out, name=name + ".max_pool")
@@ -892,13 +905,13 @@ class Builder:
 
         self.tag += 1
         self.n_units += 1
-        wptr, wpack, ldw = self._filter_operand(conv, x)
+        wptr, wpack, ldw = self._filter_operand(conv, x) if _stem7 is None else (self.bp(_stem7), _stem7, conv.k ** 2 * x.C)
         has_bn, generic_act = bn_spec is not None, relu >= 2  # (generic: only the unfused BatchNorm passes implement these)
         track, w, s, pad = self.need_grad, conv.weight, conv.stride, conv.padding
         # the unit follows ITS BatchNorm's flag (a frozen bn.eval() inside a training model uses the
         # running statistics and leaves them untouched, like nn.BatchNorm2d)
         unit_training = bn_spec.training if has_bn else self.training
-        fused = has_bn and not unit_training and not track and not generic_act
+        fused = has_bn and not unit_training and not track and not generic_act and not pre_act
         # (a training-mode BatchNorm with activation code < 2, no residual, no pool, no SyncBatchNorm, finalize-in-apply on,
         #  a tensor beyond the memory-side cache; see pw_fold_min_mb)
         defer = (defer_norm and has_bn and unit_training and not fused and not generic_act and residual is None and
@@ -910,7 +923,7 @@ class Builder:
         else:
             y = out if out is not None else self.act(x.B, Ho, Wo, Cout, name + ".y")
         u = _ConvUnit(conv, relu, x, y, residual, name, self.tag, wptr, wpack, ldw)
-        u.defer = defer
+        u.defer, u.pre_act, u.stem7 = defer, pre_act, _stem7 is not None
         u.stem_fused = stem_fused = (
             track and u.padded and has_bn and not fused and residual is None and not generic_act and
             not x.needs_grad and w.requires_grad and dt == N.VT_BF16 and Cout == 32 and k == 3 and s == 1 and
@@ -1008,6 +1021,13 @@ class Builder:
             u.pool_out, u.pool_am = pool_out, self.alloc(y.B * pool_out.H * pool_out.W * y.C, "argmax")
             self._act_apply(z, bn.cp[0], bn.cp[1], res, y, relu, [pool_out.addr(), self.bp(u.pool_am)],
                             [pool_out.ld, y.B, y.H, y.W])
+        elif u.pre_act and fin_fwd:
+            ptrs, flts = bn.finalize_operands(stats, y.M)
+            self.emit(N.OP_BN_ADD_ACT_FIN_APPLY, ptrs + [z.addr(), res.addr(), y.addr()], [y.C, z.ld, res.ld, y.ld, self.dtype],
+                      flts + [y.M])
+        elif u.pre_act:
+            self.emit(N.OP_BN_ADD_ACT_APPLY, [z.addr(), bn.cp[0], bn.cp[1], res.addr(), y.addr()],
+                      [z.ld, res.ld, y.ld, y.C, self.dtype], [y.M])
         elif fin_fwd:
             ptrs, flts = bn.finalize_operands(stats, y.M)
             self.emit(N.OP_BN_FIN_APPLY, ptrs + [z.addr(), _addr(res), y.addr()],
@@ -1056,10 +1076,14 @@ class Builder:
         dy = self.grad_read(y) if pool_grad is None else None
         if dy is None and pool_grad is None:
             return
-        self.grad_add(u.residual, dy)
+        if not u.pre_act:  # (pre_act: the identity's gradient is the MASKED d(y), an output of the backward apply pass)
+            self.grad_add(u.residual, dy)
         if u.stem_fused:
             return self._stem_bwd(u, dy)
-        dz = self._bn_bwd(u, dy, pool_grad) if u.bn is not None else self._act_bias_bwd(u, dy)
+        if u.pre_act:
+            dz = self._bn_add_act_bwd(u, dy)
+        else:
+            dz = self._bn_bwd(u, dy, pool_grad) if u.bn is not None else self._act_bias_bwd(u, dy)
         # Released BEFORE the unit's data gradient, except behind the stem (see __init__): there the data gradient
         # runs first and the filter gradient beside the stem's one-pass backward.
         late = x.needs_grad and x.stem_out
@@ -1130,6 +1154,32 @@ class Builder:
             bn.bwd_three_launches(g, z, relu, sums, bcoef, dz, taps, reduce=not fused_red)
         return dz
 
+    def _bn_add_act_bwd(self, u: "_ConvUnit", dy: TRef) -> TRef:
+        """dz and d(residual) of a unit y = relu(bn(conv) + residual): reduce (mask from the stored y) -> finalize -> ONE apply
+        pass with two outputs, dz and the identity's gradient g = dy * [y > 0].  The identity usually feeds the block's first
+        convolution too: d(residual) is written where it is the first contribution and accumulated where something
+        already wrote it (grad_accum_target)."""
+        bn, z, y, r, M, dt = u.bn, u.z, u.y, u.residual, u.y.M, self.dtype
+        sums, bcoef, dz = bn.bwd_buffers(y, u.name + ".dz")
+        if r.needs_grad:
+            dr, acc = self.grad_accum_target(r)
+        else:  # (nothing reads it: the pass has two outputs)
+            dr, acc = self.act(r.B, r.H, r.W, r.C, u.name + ".dr"), 0
+        self.emit(N.OP_BN_ADD_ACT_BWD_REDUCE, [dy.addr(), y.addr(), z.addr(), bn.cp[2], bn.cp[3], self.bp(sums)],
+                  [dy.ld, y.ld, z.ld, y.C, dt], [M])
+        if self.bn_fin_apply and not self.bn_sync:
+            self.emit(N.OP_BN_ADD_ACT_BWD_FIN_APPLY,
+                      [self.bp(sums), bn.cp[0], bn.cp[2], bn.cp[3], *bn.grads(), self.bp(bcoef), dy.addr(), y.addr(), z.addr(),
+                       dz.addr(), dr.addr()],
+                      [y.C, int(bn.spec.training), dy.ld, y.ld, z.ld, dz.ld, dr.ld, acc, dt], [M * self.bn_world, 1.0 / self.bn_world, M])
+        else:
+            bn.bwd_finalize(sums, bcoef, M)
+            self.emit(N.OP_BN_ADD_ACT_BWD_APPLY, [dy.addr(), y.addr(), z.addr(), self.bp(bcoef), dz.addr(), dr.addr()],
+                      [dy.ld, y.ld, z.ld, dz.ld, dr.ld, acc, y.C, dt], [M])
+        if r.needs_grad:
+            self.grad_written(r)
+        return dz
+
     def _act_bias_bwd(self, u: "_ConvUnit", dy: TRef) -> TRef:
         """dz of a unit without BatchNorm (dz = dy * act'(z)), and the bias gradient"""
         dz, bias = dy, u.conv.bias
@@ -1167,9 +1217,41 @@ class Builder:
             ws = self.bp(self.zeroed_f32(rows * x.C, "dwpad", bwd=True))
         self.emit(N.OP_CONV_WGRAD, [x.addr(), dz.addr(), ws or self.pgrad(w), slab], desc=dfwd,
                   extra_ints=[u.ldw, slab_mb], side=True)
-        if u.padded:
+        if u.stem7:  # the transpose of the filter repack: [Cout][4][4][Cs] -> += [Cout][7][7][3]
+            self.emit(N.OP_STEM7_UNPACK_WGRAD, [ws, self.pgrad(w)], [x.C, u.conv.out_channels], side=True)
+        elif u.padded:
             self.emit(N.OP_COPY2D, [ws, self.pgrad(w)], [N.VT_F32, N.VT_F32, u.conv.in_channels, 1],
                       [x.C, u.conv.in_channels, rows], side=True)
+
+    def stem7_unit(self, x: TRef, conv: nn.Conv2d, norm: nn.BatchNorm2d, relu=1, pool_out: Optional[TRef] = None,
+                   name: str = "conv1") -> TRef:
+        """The ResNet stem Conv2d(3, C, 7, stride 2, padding 3, bias=False) -> BatchNorm2d -> ReLU [-> MaxPool2d(3, 2, 1) into
+        `pool_out`].  49 taps exceed VT_MAX_TAPS; padded to 8 x 8 with a zero first row and column the filter is a 4 x 4
+        stride-1 filter over the space-to-depth image (12 channels (py, px, c), zero-padded to whole 16-byte chunks) whose
+        taps sit at offsets -2 .. +1 -- a window the descriptor's per-tap offsets express, so forward and filter gradient run
+        the existing kernels.  New launches: the image gather, the filter repack and, in backward, its transpose.
+        The image gets no gradient."""
+        spec, _ = self._specs(conv, norm)
+        if ((spec.k, spec.stride, spec.padding, spec.dilation, spec.groups, spec.in_channels) != (7, 2, 3, 1, 1, 3) or
+                spec.bias is not None):
+            raise NotImplementedError(f"{name}: the stem path is Conv2d(3, C, 7, stride=2, padding=3, bias=False)")
+        if x.needs_grad:
+            raise NotImplementedError(f"{name}: x.requires_grad -- the 7x7 stem forms no gradient of the image (its input is "
+                                      "the data; pass images that do not require a gradient)")
+        dt, epc = self.dtype, _EPC[self.dtype]
+        if x.logical_c != 3 or x.C != epc:
+            raise ValueError(f"{name}: expects the 3-channel image in one 16-byte chunk per pixel, got {x.logical_c} of {x.C}")
+        Cs, Cout = int(N.lib().vt_stem7_s2d_channels(dt)), spec.out_channels
+        self.tag += 1
+        xs = self.act(x.B, (x.H + 1) // 2, (x.W + 1) // 2, Cs, name + ".s2d", needs_grad=False)
+        self.emit(N.OP_STEM7_S2D, [x.addr(), xs.addr()], [x.ld, xs.ld, x.B, x.H, x.W, dt])
+        w4 = self.alloc(Cout * 16 * Cs * _ESIZE[dt], "w4x4")
+        # (bf16: from the mirror, as _filter_operand's padded copy -- the sharded exchange refreshes the mirror on every rank)
+        wsrc, wsrc_dt = (self.pref(spec.weight, mirror=True), dt) if dt == N.VT_BF16 else (self.pref(spec.weight), N.VT_F32)
+        self.emit(N.OP_STEM7_PACK_FILTER, [wsrc, self.bp(w4)], [wsrc_dt, dt, Cout])
+        self.tag -= 1  # (conv_unit advances it: the gather, the repack and the unit share one tag)
+        conv4 = ConvSpec(4, 1, 2, 1, 1, Cs, Cout, spec.weight, None, crop=1)
+        return self.conv_unit(xs, conv4, norm, relu, name=name, pool_out=pool_out, _stem7=w4)
 
     def _grouped_unit(self, x: TRef, conv: "ConvSpec", bn: "Optional[BNSpec]", relu, residual, out, name, pool_out) -> TRef:
         """nn.Conv2d(groups=G) inside a ConvNormAct (reference components.py:32): G independent units over channel slices
