@@ -565,6 +565,38 @@ int vt_stem7_s2d(const void* x, int32_t ldx, void* out, int32_t ldo, int32_t B, 
 int vt_stem7_pack_filter(const void* w, int32_t src_dtype, void* out, int32_t dst_dtype, int32_t Cout, void* stream);
 int vt_stem7_unpack_wgrad(const float* dws, int32_t Cs, float* dw, int32_t Cout, void* stream);
 
+/* ---- grouped 3x3 convolution of the RegNet blocks, and their Squeeze-Excitation MLP (vt_gconv.hip) --------------------
+ * 3x3, padding 1, dilation 1, stride 1 or 2, Cin = Cout = C in C / gw groups of gw channels; gw a multiple of 8 from 8 to 64
+ * (VT_ERR_UNSUPPORTED otherwise).  x, z, dz, dx are channel-last maps with pixel strides ld >= C (channel slices of wider
+ * buffers work); Ho = (Hi - 1) / stride + 1.  The filter is [C][3][3][gw] in the compute dtype (torch's grouped OIHW weight
+ * with the taps in front of the group's input channels).  bf16 (matrix unit, f32 accumulation) and f32 (exact FMA over the
+ * same index maps).  ONE launch over the whole map each; no float atomics: two runs give bit-identical results.
+ *   vt_gconv3_fwd    z = conv(x, w); `stats` (or NULL): per-channel sum and sum of squares of the STORED z into a
+ *                    statistics buffer, the contract of VT_CONV_STATS (fixed point, zeroed by the caller)
+ *   vt_gconv3_dgrad  dx = conv_transpose(dz, w) [+ residual, which may alias dx]; every pixel of dx is written, also the
+ *                    ones no tap reaches under stride 2
+ *   vt_gconv3_wgrad  dw [C][3][3][gw] f32 += sum over the pixels of dz (x) x: the pixels are cut into slabs, a workgroup
+ *                    stores its slab's partial filter into `scratch` (vt_gconv3_wgrad_scratch_bytes), a second kernel adds
+ *                    the slabs in slab order with one owner per filter element
+ *   vt_se_mlp_fwd    per image: hidden = relu(W1 pooled + b1) (S values, any S >= 1; kept as f32 [B][S] holding the
+ *                    values rounded to the compute dtype), logits = W2 hidden + b2, a [B][C] row in the compute dtype: the
+ *                    operand `s` of vt_se_gate_fwd.  W1 [S][C], W2 [C][S], b1, b2 are the f32 masters (bf16 launches round
+ *                    the weights as the bf16 mirror does).  C <= 8192, S <= 2048.
+ *   vt_se_mlp_bwd    from d(logits): d(pooled) (or NULL), and dW1, db1, dW2, db2 (f32, +=; each may be NULL) with one owner
+ *                    per parameter element adding the images in image order.  `dhidden` is f32 [B][S] scratch. */
+int vt_gconv3_fwd(const void* x, int32_t ldx, const void* w, void* z, int32_t ldz, float* stats, int32_t B, int32_t Hi, int32_t Wi,
+                  int32_t C, int32_t gw, int32_t stride, int32_t dtype, void* stream);
+int vt_gconv3_dgrad(const void* dz, int32_t lddz, const void* w, void* dx, int32_t lddx, const void* residual, int32_t ldr,
+                    int32_t B, int32_t Hi, int32_t Wi, int32_t C, int32_t gw, int32_t stride, int32_t dtype, void* stream);
+int64_t vt_gconv3_wgrad_scratch_bytes(int32_t B, int32_t Hi, int32_t Wi, int32_t C, int32_t gw, int32_t stride);
+int vt_gconv3_wgrad(const void* x, int32_t ldx, const void* dz, int32_t lddz, float* dw, void* scratch, int64_t scratch_bytes,
+                    int32_t B, int32_t Hi, int32_t Wi, int32_t C, int32_t gw, int32_t stride, int32_t dtype, void* stream);
+int vt_se_mlp_fwd(const void* pooled, int32_t ldp, const float* w1, const float* b1, const float* w2, const float* b2, float* hidden,
+                  void* logits, int32_t ldl, int32_t B, int32_t C, int32_t S, int32_t dtype, void* stream);
+int vt_se_mlp_bwd(const void* dlogits, int32_t ldg, const void* pooled, int32_t ldp, const float* w1, const float* w2,
+                  const float* hidden, float* dhidden, void* dpooled, int32_t lddp, float* dw1, float* db1, float* dw2, float* db2,
+                  int32_t B, int32_t C, int32_t S, int32_t dtype, void* stream);
+
 /* Backward of the stem unit Conv3x3(3 -> C, s1, pad 1) -> BatchNorm2d -> ReLU in one streaming pass
  * (darknet.py:75 `ConvNormAct(3, 32, 3, 1)`; autograd backward of components.py:26-44 with respect to the
  * conv weight and the BatchNorm parameters -- the unit's input is the image, no data gradient exists).
@@ -921,6 +953,11 @@ enum vt_op_kind {
     VT_OP_STEM7_S2D,                /* vt_stem7_s2d */
     VT_OP_STEM7_PACK_FILTER,        /* vt_stem7_pack_filter */
     VT_OP_STEM7_UNPACK_WGRAD,       /* vt_stem7_unpack_wgrad */
+    VT_OP_GCONV3_FWD,               /* vt_gconv3_fwd */
+    VT_OP_GCONV3_DGRAD,             /* vt_gconv3_dgrad */
+    VT_OP_GCONV3_WGRAD,             /* vt_gconv3_wgrad */
+    VT_OP_SE_MLP_FWD,               /* vt_se_mlp_fwd */
+    VT_OP_SE_MLP_BWD,               /* vt_se_mlp_bwd */
     VT_OP_KIND_END
 };
 

@@ -346,6 +346,19 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
             return vt_stem7_pack_filter(P[0], I[0], P[1], I[1], I[2], st);
         case VT_OP_STEM7_UNPACK_WGRAD:  // ptr: dws dw | i: Cs Cout
             return vt_stem7_unpack_wgrad((const float*)P[0], I[0], (float*)P[1], I[1], st);
+        case VT_OP_GCONV3_FWD:  // ptr: x w z stats | i: ldx ldz B Hi Wi C gw stride dtype
+            return vt_gconv3_fwd(P[0], I[0], P[1], P[2], I[1], (float*)P[3], I[2], I[3], I[4], I[5], I[6], I[7], I[8], st);
+        case VT_OP_GCONV3_DGRAD:  // ptr: dz w dx residual | i: lddz lddx ldr B Hi Wi C gw stride dtype
+            return vt_gconv3_dgrad(P[0], I[0], P[1], P[2], I[1], P[3], I[2], I[3], I[4], I[5], I[6], I[7], I[8], I[9], st);
+        case VT_OP_GCONV3_WGRAD:  // ptr: x dz dw scratch | i: ldx lddz B Hi Wi C gw stride dtype | f: scratch bytes
+            return vt_gconv3_wgrad(P[0], I[0], P[1], I[1], (float*)P[2], P[3], (int64_t)F[0], I[2], I[3], I[4], I[5], I[6], I[7], I[8],
+                                   st);
+        case VT_OP_SE_MLP_FWD:  // ptr: pooled w1 b1 w2 b2 hidden logits | i: ldp ldl B C S dtype
+            return vt_se_mlp_fwd(P[0], I[0], (const float*)P[1], (const float*)P[2], (const float*)P[3], (const float*)P[4],
+                                 (float*)P[5], P[6], I[1], I[2], I[3], I[4], I[5], st);
+        case VT_OP_SE_MLP_BWD:  // ptr: dlogits pooled w1 w2 hidden dhidden dpooled dw1 db1 dw2 db2 | i: ldg ldp lddp B C S dtype
+            return vt_se_mlp_bwd(P[0], I[0], P[1], I[1], (const float*)P[2], (const float*)P[3], (const float*)P[4], (float*)P[5],
+                                 P[6], I[2], (float*)P[7], (float*)P[8], (float*)P[9], (float*)P[10], I[3], I[4], I[5], I[6], st);
         case VT_OP_BN_BWD_FUSED:  // ptr: dy z scale shift mean invstd sums sync dgamma dbeta coef dz | i: lddy ldz lddz C relu dtype train | f: M count pscale(0 = 1)
             return vt_bn_act_bwd_fused(P[0], I[0], P[1], I[1], (const float*)P[2], (const float*)P[3], (const float*)P[4],
                                        (const float*)P[5], (int64_t)F[0], I[3], I[4], I[5], F[1], F[2] == 0.0 ? 1.0 : F[2], I[6],
@@ -501,7 +514,7 @@ struct Graph {
 
 extern "C" {
 
-int vt_version(void) { return 105; }  // 105: vt_resnet.hip (add-then-ReLU BatchNorm passes, the 7x7 stem as a 4x4 convolution); 104: round 6 (finalize inside the passes, vt_op carries 24 pointers; 103: vt_conv_dgrad_bnred, vt_debug_hog left the library)
+int vt_version(void) { return 106; }  // 106: vt_gconv.hip (grouped 3x3 convolution in one launch, the Squeeze-Excitation MLP); 105: vt_resnet.hip (add-then-ReLU BatchNorm passes, the 7x7 stem as a 4x4 convolution); 104: round 6 (finalize inside the passes, vt_op carries 24 pointers; 103: vt_conv_dgrad_bnred, vt_debug_hog left the library)
 int vt_set_knob(const char* name, int32_t value) {
     VT_REQUIRE(name && strlen(name) < 48, VT_ERR_INVALID, "vt_set_knob: bad name");
     // (a knob set before its first use overrides the environment: the slot exists from here on)

@@ -150,7 +150,12 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_STEM7_S2D,
     OP_STEM7_PACK_FILTER,
     OP_STEM7_UNPACK_WGRAD,
-) = range(1, 93)
+    OP_GCONV3_FWD,
+    OP_GCONV3_DGRAD,
+    OP_GCONV3_WGRAD,
+    OP_SE_MLP_FWD,
+    OP_SE_MLP_BWD,
+) = range(1, 98)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -227,6 +232,11 @@ OP_NAMES = {
     OP_STEM7_S2D: "stem7_s2d",
     OP_STEM7_PACK_FILTER: "stem7_pack_filter",
     OP_STEM7_UNPACK_WGRAD: "stem7_unpack_wgrad",
+    OP_GCONV3_FWD: "gconv3_fwd",
+    OP_GCONV3_DGRAD: "gconv3_dgrad",
+    OP_GCONV3_WGRAD: "gconv3_wgrad",
+    OP_SE_MLP_FWD: "se_mlp_fwd",
+    OP_SE_MLP_BWD: "se_mlp_bwd",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -403,6 +413,12 @@ SYMBOLS = {
     "vt_stem7_s2d": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_stem7_pack_filter": (_i32, [_vp, _i32, _vp, _i32, _i32, _vp]),
     "vt_stem7_unpack_wgrad": (_i32, [_vp, _i32, _vp, _i32, _vp]),
+    "vt_gconv3_fwd": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp] + [_i32] * 7 + [_vp]),
+    "vt_gconv3_dgrad": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _i32] + [_i32] * 7 + [_vp]),
+    "vt_gconv3_wgrad_scratch_bytes": (_i64, [_i32] * 6),
+    "vt_gconv3_wgrad": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i64] + [_i32] * 7 + [_vp]),
+    "vt_se_mlp_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32] + [_i32] * 4 + [_vp]),
+    "vt_se_mlp_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp] + [_i32] * 4 + [_vp]),
     "vt_pack_dgrad_filter_batch": (_i32, [_vp, _i32, _vp]),
     "vt_bn_eval_coeffs_batch": (_i32, [_vp, _i32, _vp]),
     "vt_pack_dgrad_filter": (_i32, [_vp, _i32, _i32, _vp, _i32, C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp]),

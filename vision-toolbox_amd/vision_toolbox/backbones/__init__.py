@@ -16,8 +16,10 @@ SqueezeExcitation of our own: torchvision is not imported) runs on the plane, ga
 DeiT and DeiT3 (backbones/deit.py:14,118), the other family the reference builds on ViT, run on ViT's block path; DeiT's
 two prefix tokens and its two-token pooled head run on the kernels of vt_prefix_tokens.hip.  ResNetExtractor
 (backbones/torchvision_models.py:22, with BasicBlock / Bottleneck written out under torchvision's child names: torchvision
-is not imported) runs its add-then-ReLU block ends and its 7x7 stem on the kernels of vt_resnet.hip.  The reference's other
-torchvision extractors (RegNet, MobileNet, EfficientNet) are not part of this build.
+is not imported) runs its add-then-ReLU block ends and its 7x7 stem on the kernels of vt_resnet.hip.  RegNetExtractor
+(the next class of that file, RegNetBlock written out the same way) runs its grouped 3x3 convolutions in one launch per pass
+and its Squeeze-Excitation MLP on the kernels of vt_gconv.hip.  The reference's other torchvision extractors (MobileNet,
+EfficientNet) are not part of this build.
 """
 from .base import BaseBackbone
 from .convnext import ConvNeXt, ConvNeXtBlock, GlobalResponseNorm
@@ -28,6 +30,7 @@ from .cait import CaiT, CaiTCABlock, CaiTSABlock, ClassAttention, TalkingHeadAtt
 from .patchconvnet import AttentionPooling, PatchConvBlockBN, PatchConvBlockLN, PatchConvNet, SqueezeExcitation
 from .swin import PatchMerging, SwinBlock, SwinTransformer, WindowAttention, window_partition, window_unpartition
 from .resnet import BasicBlock, Bottleneck, ResNetExtractor
+from .regnet import RegNetBlock, RegNetExtractor, regnet_block_params
 from .darknet import (
     CSPDarknetStage,
     Darknet,

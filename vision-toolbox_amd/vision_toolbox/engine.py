@@ -573,6 +573,7 @@ class Builder:
         self._win_scratch: dict[int, Buf] = {}  # window attention: the per-window shares of the table gradient, per size
         self._talk_scratch: dict[int, Buf] = {}  # talking-heads attention: delta and the parameter-gradient shares, per size
         self._dw3_scratch: dict[int, Buf] = {}  # depthwise 3x3 + GELU + pool: the per-image filter-gradient shares, per size
+        self._gconv_scratch: dict[int, Buf] = {}  # grouped 3x3: the filter gradient's slabs, per size
 
     # -- memory -----------------------------------------------------------------
     def alloc(self, nbytes: int, name: str = "") -> Buf:
@@ -1346,6 +1347,108 @@ class Builder:
 
             self._node(y, bwd)
         return y
+
+    # -- grouped 3x3 units in one launch, and the Squeeze-Excitation MLP (vt_gconv.hip) -------------------------------
+    GCONV3_WIDTHS = tuple(range(8, 65, 8))  # channels per group the one-launch kernels take
+
+    def grouped3x3_unit(self, x: TRef, conv, norm, relu=1, out: Optional[TRef] = None, name: str = "gconv") -> TRef:
+        """y = [relu](bn(conv(x))) for nn.Conv2d(C, C, 3, stride 1 | 2, padding 1, groups = C / gw, bias=False) with gw in
+        GCONV3_WIDTHS -- the `f.b` unit of a RegNet block -- as ONE launch per pass over all groups: vt_gconv3_fwd (+ batch
+        statistics) -> the ordinary BatchNorm finalize / normalise passes over all C channels; backward: the ordinary BatchNorm
+        backward -> vt_gconv3_wgrad (side stream; slabs + an ordered reducer, so it is the same in deterministic mode) and
+        vt_gconv3_dgrad.  ConvNormAct(groups=...) does not come here: it keeps _grouped_unit."""
+        conv, bn_spec = self._specs(conv, norm)
+        relu, dt, epc = int(relu), self.dtype, _EPC[self.dtype]
+        Cc, G = conv.in_channels, conv.groups
+        gw = Cc // max(G, 1)
+        if ((conv.k, conv.padding, conv.dilation) != (3, 1, 1) or conv.stride not in (1, 2) or conv.out_channels != Cc or
+                conv.bias is not None or bn_spec is None or Cc % max(G, 1)):
+            raise NotImplementedError(f"{name}: the one-launch grouped unit is Conv2d(C, C, 3, stride 1 or 2, padding 1, groups, "
+                                      "bias=False) -> BatchNorm2d")
+        if gw not in self.GCONV3_WIDTHS:
+            raise NotImplementedError(f"{name}: {gw} channels per group -- vt_gconv3_* take a multiple of 8 from 8 to 64")
+        if x.logical_c != Cc or x.C != Cc:
+            raise ValueError(f"{name}: conv expects {Cc} (unpadded) input channels, got {x.logical_c}")
+        if relu >= 2:
+            raise NotImplementedError(f"{name}: activation code {relu} (none or ReLU)")
+        B, s = x.B, conv.stride
+        Ho, Wo = conv.out_size(x.H, x.W)
+        M = B * Ho * Wo
+        y = out if out is not None else self.act(B, Ho, Wo, Cc, name + ".y")
+        assert (y.B, y.H, y.W, y.C) == (B, Ho, Wo, Cc), "out geometry mismatch"
+        self.tag += 1
+        self.n_units += 1
+        w = conv.weight
+        wptr = self.pref(w, mirror=dt != N.VT_F32)
+        geo = [B, x.H, x.W, Cc, gw, s, dt]
+        u = _ConvUnit(conv, relu, x, y, None, name, self.tag, wptr, None, 9 * gw)
+        u.bn = bn = _BNEmitter(self, bn_spec, Cc)
+        u.z = z = self.act(B, Ho, Wo, Cc, name + ".z")
+        if bn_spec.training:
+            stats = self.zeroed_f32(N.stat_floats(Cc), "stats")
+            self.emit(N.OP_GCONV3_FWD, [x.addr(), wptr, z.addr(), self.bp(stats)], [x.ld, z.ld] + geo)
+            if self.bn_fin_apply and not self.bn_sync:
+                ptrs, flts = bn.finalize_operands(stats, M)
+                self.emit(N.OP_BN_FIN_APPLY, ptrs + [z.addr(), None, y.addr()], [Cc, z.ld, 0, y.ld, relu, dt], flts + [M])
+            else:
+                bn.finalize(stats, M)
+                self._act_apply(z, bn.cp[0], bn.cp[1], None, y, relu)
+        else:
+            self.emit(N.OP_GCONV3_FWD, [x.addr(), wptr, z.addr(), None], [x.ld, z.ld] + geo)
+            bn.eval_coeffs()
+            self._act_apply(z, bn.cp[0], bn.cp[1], None, y, relu)
+        if self.need_grad:
+
+            def bwd(dy):
+                dz = self._bn_bwd(u, dy, None)
+                if w.requires_grad:
+                    nbytes = int(N.lib().vt_gconv3_wgrad_scratch_bytes(B, x.H, x.W, Cc, gw, s))
+                    # (one scratch per size: every filter gradient of this kind runs on the one side stream, in order)
+                    scratch = self._gconv_scratch.get(nbytes)
+                    if scratch is None:
+                        scratch = self._gconv_scratch[nbytes] = self.alloc(nbytes, "gconv_slabs")
+                    self.emit(N.OP_FORK)
+                    self.emit(N.OP_GCONV3_WGRAD, [x.addr(), dz.addr(), self.pgrad(w), self.bp(scratch)], [x.ld, dz.ld] + geo,
+                              [nbytes], side=True)
+                if x.needs_grad:
+                    gx, res = self.grad_target(x)
+                    self.emit(N.OP_GCONV3_DGRAD, [dz.addr(), wptr, gx.addr(), _addr(res)], [dz.ld, gx.ld, _ld(res)] + geo)
+                    self.grad_written(x)
+
+            self._node(y, bwd)
+        return y
+
+    def se_mlp(self, pooled: TRef, fc1: nn.Conv2d, fc2: nn.Conv2d, name: str = "se") -> TRef:
+        """The Squeeze-Excitation MLP on a pooled [B, 1, 1, C] row: fc2(relu(fc1(pooled))) with 1x1 biased convolutions of ANY
+        squeeze width (RegNetY: round(0.25 * width_in) = 12, 26, 110 ..., no whole 16-byte chunks, which the 1x1 units need) in
+        one launch (vt_se_mlp_fwd); the result is the operand `s` of se_gate.  Backward: vt_se_mlp_bwd (d(pooled) and the four
+        parameter gradients, one owner per element).  The weights are read from the f32 masters."""
+        Cc, S = fc1.in_channels, fc1.out_channels
+        if ((pooled.H, pooled.W, pooled.C) != (1, 1, Cc) or pooled.logical_c != Cc or fc2.in_channels != S or
+                fc2.out_channels != Cc or fc1.kernel_size != (1, 1) or fc2.kernel_size != (1, 1) or fc1.bias is None or
+                fc2.bias is None or fc1.groups != 1 or fc2.groups != 1):
+            raise NotImplementedError(f"{name}: fc1 / fc2 are biased 1x1 convolutions C -> S -> C on a pooled [B, 1, 1, C] row")
+        self.tag += 1
+        B, dt = pooled.B, self.dtype
+        logits = self.act(B, 1, 1, Cc, name + ".logits")
+        hidden = self.f32(B * S, name + ".hidden")
+        wts = [self.pref(fc1.weight), self.pref(fc1.bias), self.pref(fc2.weight), self.pref(fc2.bias)]
+        self.emit(N.OP_SE_MLP_FWD, [pooled.addr(), *wts, self.bp(hidden), logits.addr()], [pooled.ld, logits.ld, B, Cc, S, dt])
+        if self.need_grad:
+
+            def bwd(dl):
+                gp = None
+                if pooled.needs_grad:
+                    gp, res = self.grad_target(pooled)
+                    assert res is None and self._deferred_flush is None, "the pooled row has one consumer, the MLP"
+                dhid = self.f32(B * S, name + ".dhidden")
+                self.emit(N.OP_SE_MLP_BWD,
+                          [dl.addr(), pooled.addr(), wts[0], wts[2], self.bp(hidden), self.bp(dhid), _addr(gp),
+                           self.pgrad(fc1.weight), self.pgrad(fc1.bias), self.pgrad(fc2.weight), self.pgrad(fc2.bias)],
+                          [dl.ld, pooled.ld, _ld(gp), B, Cc, S, dt])
+
+            self._node(logits, bwd)
+        return logits
 
     # -- pointwise (1x1) units without stored pre-activations (vt_pointwise.hip) ------------------------------------
     def _unit_specs(self, specs) -> list:

@@ -256,6 +256,12 @@ class TrainStep:
             if isinstance(backbone, PatchConvNet):
                 raise NotImplementedError("exchange='sharded' with a PatchConvNet: its depthwise filters, class token and layer "
                                           "scales are read in f32 outside the head bucket (use exchange='allreduce')")
+            from .backbones.regnet import RegNetExtractor
+
+            # (... and for the Squeeze-Excitation weights of a RegNetY, which vt_se_mlp_fwd reads as f32 masters)
+            if isinstance(backbone, RegNetExtractor) and backbone.se_ratio:
+                raise NotImplementedError(f"exchange='sharded' with {backbone.model_name}: its Squeeze-Excitation weights are "
+                                          "read in f32 outside the head bucket (use exchange='allreduce')")
         # who issues the collectives: "torch" = torch.distributed calls between segments of the launch lists (any
         # backend: gloo in the CPU tests); "rccl" = the library's own RCCL communicator (vt_comm_init), the collectives are
         # OPS of the lists (VT_OP_STAT_SYNC in front of every BatchNorm finalize, FORK + VT_OP_ALLREDUCE on the
