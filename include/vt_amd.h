@@ -459,8 +459,9 @@ typedef struct vt_bn_eval_item {
 } vt_bn_eval_item;
 int vt_bn_eval_coeffs_batch(const vt_bn_eval_item* items, int32_t n, void* stream);
 /* y = act(z*scale + shift) [+ residual].  `relu` here and in vt_bn_act_bwd_reduce / _bwd_apply is an ACTIVATION CODE
- * (ConvNormAct's `act`, components.py:37-44): 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 SiLU ("swish"), 4 GELU (exact).  Codes 0 / 1
- * are the Darknet / VoVNet path; 2-4 run generic instantiations of the same kernels (round 5). */
+ * (ConvNormAct's `act`, components.py:37-44): 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 SiLU ("swish"), 4 GELU (exact), 5 ReLU6, 6 Hardswish
+ * (torchvision's MobileNets; derivatives as torch: ReLU6' = 1 on 0 < u < 6, Hardswish' = (2u + 3) / 6 on -3 <= u <= 3).  Codes 0 / 1
+ * are the Darknet / VoVNet path; 2-6 run generic instantiations of the same kernels (round 5). */
 int vt_bn_act_apply(const void* z, int32_t ldz, const float* scale, const float* shift,
                     const void* residual, int32_t ldr, void* y, int32_t ldy, int64_t M,
                     int32_t C, int32_t relu, int32_t dtype, void* stream);
@@ -596,6 +597,33 @@ int vt_se_mlp_fwd(const void* pooled, int32_t ldp, const float* w1, const float*
 int vt_se_mlp_bwd(const void* dlogits, int32_t ldg, const void* pooled, int32_t ldp, const float* w1, const float* w2,
                   const float* hidden, float* dhidden, void* dpooled, int32_t lddp, float* dw1, float* db1, float* dw2, float* db2,
                   int32_t B, int32_t C, int32_t S, int32_t dtype, void* stream);
+
+/* ---- tiled depthwise convolution of the MobileNet Conv-BN-act units (vt_dwtile.hip) -------------------------------------
+ * k in {3, 5}, stride s in {1, 2}, padding (k - 1) / 2, dilation 1; C a multiple of 8 (bf16) / 4 (f32); any Hi, Wi >= 1 whose
+ * one-row tile fits 64 KiB of LDS (Wi up to ~400 at k = 5); x, z, dz, dx channel-last with pixel strides ld >= C (channel
+ * slices of wider buffers work); Ho = (Hi - 1) / s + 1.  The filter is the f32 master [C][k*k] of vt_dwconv_*, rounded for
+ * bf16 launches as vt_dwconv_fwd rounds it.  Anything else: VT_ERR_UNSUPPORTED with the argument named.  A workgroup owns
+ * (image, band of output rows, slab of channels) and stages its inputs with their halo in LDS once; no float atomics.
+ *   vt_dwt_fwd           z = conv(x, w), f32 accumulation from 0 in ascending tap order: bit-identical to vt_dwconv_fwd on
+ *                        the same operands.  `stats` (or NULL): the VT_CONV_STATS contract (fixed point, zeroed by the caller)
+ *   vt_dwt_bwd           ONE launch: dx = conv_transpose(dz, w) [+ residual, which may alias dx; the sum is rounded to the
+ *                        storage type first], every input pixel written; and the workgroup's filter-gradient share, f32
+ *                        [k*k][slab channels], into shares[image][band][tap][c] (vt_dwt_shares_bytes; every element the
+ *                        reducer reads is written)
+ *   vt_dwt_wgrad_reduce  dw[c][t] += the shares of that element added in (image, band) order by one owner thread (the +=
+ *                        contract of vt_dwconv_wgrad).  Takes the dtype of the vt_dwt_bwd launch: the band height, and with
+ *                        it the share count, follows from the tile, which depends on the bytes per channel
+ *   vt_dwt_tile          the tile all three use for a geometry: output rows per band, channels per slab */
+int vt_dwt_fwd(const void* x, int32_t ldx, const float* w, void* z, int32_t ldz, float* stats, int32_t B, int32_t Hi, int32_t Wi,
+               int32_t C, int32_t k, int32_t s, int32_t dtype, void* stream);
+int vt_dwt_bwd(const void* dz, int32_t lddz, const void* x, int32_t ldx, const float* w, void* dx, int32_t lddx, const void* residual,
+               int32_t ldr, float* shares, int64_t shares_bytes, int32_t B, int32_t Hi, int32_t Wi, int32_t C, int32_t k, int32_t s,
+               int32_t dtype, void* stream);
+int vt_dwt_wgrad_reduce(const float* shares, int64_t shares_bytes, float* dw, int32_t B, int32_t Hi, int32_t Wi, int32_t C,
+                        int32_t k, int32_t s, int32_t dtype, void* stream);
+int64_t vt_dwt_shares_bytes(int32_t B, int32_t Hi, int32_t Wi, int32_t C, int32_t k, int32_t s, int32_t dtype); /* < 0: refused */
+int vt_dwt_tile(int32_t Hi, int32_t Wi, int32_t C, int32_t k, int32_t s, int32_t dtype, int32_t* rows_per_band,
+                int32_t* channels_per_slab);
 
 /* Backward of the stem unit Conv3x3(3 -> C, s1, pad 1) -> BatchNorm2d -> ReLU in one streaming pass
  * (darknet.py:75 `ConvNormAct(3, 32, 3, 1)`; autograd backward of components.py:26-44 with respect to the
@@ -958,6 +986,9 @@ enum vt_op_kind {
     VT_OP_GCONV3_WGRAD,             /* vt_gconv3_wgrad */
     VT_OP_SE_MLP_FWD,               /* vt_se_mlp_fwd */
     VT_OP_SE_MLP_BWD,               /* vt_se_mlp_bwd */
+    VT_OP_DWT_FWD,                  /* vt_dwt_fwd */
+    VT_OP_DWT_BWD,                  /* vt_dwt_bwd */
+    VT_OP_DWT_WGRAD_REDUCE,         /* vt_dwt_wgrad_reduce */
     VT_OP_KIND_END
 };
 

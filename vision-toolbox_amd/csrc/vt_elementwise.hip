@@ -87,7 +87,7 @@ __global__ void __launch_bounds__(256) bn_eval_coeffs_batch_kernel(const BnEvalB
 
 // ---------------------------------------------------------------------------------
 // Activation codes of the `relu` argument of vt_bn_act_apply / _bwd_reduce / _bwd_apply (components.py:37-44): 0 none, 1 ReLU,
-// 2 LeakyReLU(0.2), 3 SiLU ("swish"), 4 GELU (exact, erf).  Codes 0 / 1 run the kernels' original instantiations (the hot
+// 2 LeakyReLU(0.2), 3 SiLU ("swish"), 4 GELU (exact, erf), 5 ReLU6, 6 Hardswish (the MobileNets).  Codes 0 / 1 run the kernels' original instantiations (the hot
 // path); codes >= 2 a GEN instantiation of the same kernels, so that the Darknet / VoVNet launches keep their code.
 __device__ __forceinline__ float act_fwd(int code, float u) {
     switch (code) {
@@ -95,6 +95,8 @@ __device__ __forceinline__ float act_fwd(int code, float u) {
         case 2: return u > 0.f ? u : 0.2f * u;
         case 3: return u / (1.f + expf(-u));
         case 4: return 0.5f * u * (1.f + erff(u * 0.70710678118654752f));
+        case 5: return fminf(fmaxf(u, 0.f), 6.f);
+        case 6: return u * fminf(fmaxf(u + 3.f, 0.f), 6.f) * (1.f / 6.f);
         default: return u;
     }
 }
@@ -108,6 +110,8 @@ __device__ __forceinline__ float act_grad(int code, float u) {
             return s * (1.f + u * (1.f - s));
         }
         case 4: return 0.5f * (1.f + erff(u * 0.70710678118654752f)) + u * 0.3989422804014327f * expf(-0.5f * u * u);
+        case 5: return (u > 0.f && u < 6.f) ? 1.f : 0.f;
+        case 6: return u < -3.f ? 0.f : (u <= 3.f ? (2.f * u + 3.f) * (1.f / 6.f) : 1.f);  // (torch's hardswish_backward)
         default: return 1.f;
     }
 }
@@ -1684,7 +1688,7 @@ int vt_bn_act_apply(const void* z, int32_t ldz, const float* scale, const float*
     if (residual) VT_TRY(check_mat("vt_bn_act_apply(residual)", residual, ldr, C, dtype));
     RowMap rm = RowMap::make(C, vt_epc(dtype), M);
     rm.rev = (vt_bn_order() >> 0) & 1;
-    VT_REQUIRE(relu >= 0 && relu <= 4, VT_ERR_INVALID, "vt_bn_act_apply: activation code %d", relu);
+    VT_REQUIRE(relu >= 0 && relu <= 6, VT_ERR_INVALID, "vt_bn_act_apply: activation code %d", relu);
     if (relu >= 2) {  // LeakyReLU(0.2) / SiLU / GELU: the generic instantiation (off the Darknet / VoVNet path)
         if (residual) {
             VT_DISPATCH_T(dtype, "vt_bn_act_apply",
@@ -1726,7 +1730,7 @@ int vt_bn_finalize_apply(const float* stats, int32_t C, double count, const floa
                "vt_bn_finalize_apply: bad argument");
     VT_REQUIRE((running_mean == nullptr) == (running_var == nullptr), VT_ERR_INVALID,
                "vt_bn_finalize_apply: running_mean/var must both be given or both NULL");
-    VT_REQUIRE(relu >= 0 && relu <= 4, VT_ERR_INVALID, "vt_bn_finalize_apply: activation code %d", relu);
+    VT_REQUIRE(relu >= 0 && relu <= 6, VT_ERR_INVALID, "vt_bn_finalize_apply: activation code %d", relu);
     const int Cg = fin_group(C, vt_epc(dtype));
     if (relu >= 2 || !Cg || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {
         const int rc = vt_bn_finalize(stats, C, count, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked,
@@ -1763,7 +1767,7 @@ int vt_bn_bwd_finalize_apply(const float* sums, int32_t C, double count, double 
                              void* dz, int32_t lddz, int64_t M, int32_t relu, int32_t dtype, void* stream) {
     VT_REQUIRE(sums && scale && shift && mean && invstd && coef && C > 0 && count > 0 && M > 0, VT_ERR_INVALID,
                "vt_bn_bwd_finalize_apply: bad argument");
-    VT_REQUIRE(relu >= 0 && relu <= 4, VT_ERR_INVALID, "vt_bn_bwd_finalize_apply: activation code %d", relu);
+    VT_REQUIRE(relu >= 0 && relu <= 6, VT_ERR_INVALID, "vt_bn_bwd_finalize_apply: activation code %d", relu);
     const int Cg = fin_group(C, vt_epc(dtype));
     if (relu >= 2 || !Cg || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {
         const int rc = vt_bn_bwd_finalize(sums, C, count, pscale, scale, mean, invstd, train, dgamma, dbeta, coef, stream);
@@ -1809,7 +1813,7 @@ int vt_bn_act_bwd_reduce(const void* dy, int32_t lddy, const void* z, int32_t ld
     const int inwave_env = (1);
     const bool inwave = inwave_env && rm.CT < 64 && (rm.CT & (rm.CT - 1)) == 0;  // (as in the kernel)
     const int smem = (inwave ? kThreads / 64 : rm.RT) * 2 * rm.CT * epc * (int)sizeof(float);
-    VT_REQUIRE(relu >= 0 && relu <= 4, VT_ERR_INVALID, "vt_bn_act_bwd_reduce: activation code %d", relu);
+    VT_REQUIRE(relu >= 0 && relu <= 6, VT_ERR_INVALID, "vt_bn_act_bwd_reduce: activation code %d", relu);
     if (relu >= 2) {
         VT_DISPATCH_T(dtype, "vt_bn_act_bwd_reduce",
                       hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true>), dim3(rm.blocks(M), cgroups), dim3(kThreads), smem,
@@ -1848,7 +1852,7 @@ int vt_bn_act_bwd_apply(const void* dy, int32_t lddy, const void* z, int32_t ldz
     VT_TRY(check_mat("vt_bn_act_bwd_apply(dz)", dz, lddz, C, dtype));
     RowMap rm = RowMap::make(C, vt_epc(dtype), M);
     rm.rev = (vt_bn_order() >> 2) & 1;
-    VT_REQUIRE(relu >= 0 && relu <= 4, VT_ERR_INVALID, "vt_bn_act_bwd_apply: activation code %d", relu);
+    VT_REQUIRE(relu >= 0 && relu <= 6, VT_ERR_INVALID, "vt_bn_act_bwd_apply: activation code %d", relu);
     if (relu >= 2 || act_only) {
         VT_DISPATCH_T(dtype, "vt_bn_act_bwd_apply",
                       hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true>), dim3(rm.blocks(M)), dim3(kThreads), 0,

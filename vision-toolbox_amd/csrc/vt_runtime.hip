@@ -353,6 +353,13 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
         case VT_OP_GCONV3_WGRAD:  // ptr: x dz dw scratch | i: ldx lddz B Hi Wi C gw stride dtype | f: scratch bytes
             return vt_gconv3_wgrad(P[0], I[0], P[1], I[1], (float*)P[2], P[3], (int64_t)F[0], I[2], I[3], I[4], I[5], I[6], I[7], I[8],
                                    st);
+        case VT_OP_DWT_FWD:  // ptr: x w z stats | i: ldx ldz B Hi Wi C k s dtype
+            return vt_dwt_fwd(P[0], I[0], (const float*)P[1], P[2], I[1], (float*)P[3], I[2], I[3], I[4], I[5], I[6], I[7], I[8], st);
+        case VT_OP_DWT_BWD:  // ptr: dz x w dx residual shares | i: lddz ldx lddx ldr B Hi Wi C k s dtype | f: shares bytes
+            return vt_dwt_bwd(P[0], I[0], P[1], I[1], (const float*)P[2], P[3], I[2], P[4], I[3], (float*)P[5], (int64_t)F[0], I[4],
+                              I[5], I[6], I[7], I[8], I[9], I[10], st);
+        case VT_OP_DWT_WGRAD_REDUCE:  // ptr: shares dw | i: B Hi Wi C k s dtype | f: shares bytes
+            return vt_dwt_wgrad_reduce((const float*)P[0], (int64_t)F[0], (float*)P[1], I[0], I[1], I[2], I[3], I[4], I[5], I[6], st);
         case VT_OP_SE_MLP_FWD:  // ptr: pooled w1 b1 w2 b2 hidden logits | i: ldp ldl B C S dtype
             return vt_se_mlp_fwd(P[0], I[0], (const float*)P[1], (const float*)P[2], (const float*)P[3], (const float*)P[4],
                                  (float*)P[5], P[6], I[1], I[2], I[3], I[4], I[5], st);

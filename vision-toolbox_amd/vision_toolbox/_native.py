@@ -155,7 +155,10 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_GCONV3_WGRAD,
     OP_SE_MLP_FWD,
     OP_SE_MLP_BWD,
-) = range(1, 98)
+    OP_DWT_FWD,
+    OP_DWT_BWD,
+    OP_DWT_WGRAD_REDUCE,
+) = range(1, 101)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -237,6 +240,9 @@ OP_NAMES = {
     OP_GCONV3_WGRAD: "gconv3_wgrad",
     OP_SE_MLP_FWD: "se_mlp_fwd",
     OP_SE_MLP_BWD: "se_mlp_bwd",
+    OP_DWT_FWD: "dwt_fwd",
+    OP_DWT_BWD: "dwt_bwd",
+    OP_DWT_WGRAD_REDUCE: "dwt_wgrad_reduce",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -419,6 +425,11 @@ SYMBOLS = {
     "vt_gconv3_wgrad": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i64] + [_i32] * 7 + [_vp]),
     "vt_se_mlp_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32] + [_i32] * 4 + [_vp]),
     "vt_se_mlp_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp] + [_i32] * 4 + [_vp]),
+    "vt_dwt_fwd": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp] + [_i32] * 7 + [_vp]),
+    "vt_dwt_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i64] + [_i32] * 7 + [_vp]),
+    "vt_dwt_wgrad_reduce": (_i32, [_vp, _i64, _vp] + [_i32] * 7 + [_vp]),
+    "vt_dwt_shares_bytes": (_i64, [_i32] * 7),
+    "vt_dwt_tile": (_i32, [_i32] * 6 + [C.POINTER(_i32), C.POINTER(_i32)]),
     "vt_pack_dgrad_filter_batch": (_i32, [_vp, _i32, _vp]),
     "vt_bn_eval_coeffs_batch": (_i32, [_vp, _i32, _vp]),
     "vt_pack_dgrad_filter": (_i32, [_vp, _i32, _i32, _vp, _i32, C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp]),

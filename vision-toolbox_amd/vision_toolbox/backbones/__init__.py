@@ -1,5 +1,5 @@
 """Backbones of the MI355X hot path: Darknet / CSPDarknet / DarknetYOLOv5 / VoVNet / ConvNeXt / MLP-Mixer / ViT / Swin / CaiT /
-PatchConvNet / DeiT.
+PatchConvNet / DeiT / ResNet / RegNet / MobileNet.
 
 Both surfaces the reference snapshot exposes are exported: the classes with
 `from_config` (reference backbones/__init__.py:3,10, tests/test_backbones.py:25-30) and the
@@ -18,8 +18,10 @@ two prefix tokens and its two-token pooled head run on the kernels of vt_prefix_
 (backbones/torchvision_models.py:22, with BasicBlock / Bottleneck written out under torchvision's child names: torchvision
 is not imported) runs its add-then-ReLU block ends and its 7x7 stem on the kernels of vt_resnet.hip.  RegNetExtractor
 (the next class of that file, RegNetBlock written out the same way) runs its grouped 3x3 convolutions in one launch per pass
-and its Squeeze-Excitation MLP on the kernels of vt_gconv.hip.  The reference's other torchvision extractors (MobileNet,
-EfficientNet) are not part of this build.
+and its Squeeze-Excitation MLP on the kernels of vt_gconv.hip.  MobileNetExtractor (the class after it: mobilenet_v2,
+mobilenet_v3_large, mobilenet_v3_small, InvertedResidual written out the same way) runs its depthwise Conv-BN-act units on the
+tiled kernels of vt_dwtile.hip, with ReLU6 / Hardswish in the BatchNorm passes and the hardsigmoid gate of VoVNet's eSE.  The
+reference's last torchvision extractor (EfficientNet) is not part of this build.
 """
 from .base import BaseBackbone
 from .convnext import ConvNeXt, ConvNeXtBlock, GlobalResponseNorm
@@ -31,6 +33,7 @@ from .patchconvnet import AttentionPooling, PatchConvBlockBN, PatchConvBlockLN, 
 from .swin import PatchMerging, SwinBlock, SwinTransformer, WindowAttention, window_partition, window_unpartition
 from .resnet import BasicBlock, Bottleneck, ResNetExtractor
 from .regnet import RegNetBlock, RegNetExtractor, regnet_block_params
+from .mobilenet import InvertedResidualV2, InvertedResidualV3, MobileNetExtractor
 from .darknet import (
     CSPDarknetStage,
     Darknet,

@@ -110,7 +110,8 @@ class ConvNormAct(nn.Sequential, HipModule):
 
     # -- launch-list emission ----------------------------------------------------------
     def _vt_relu(self) -> int:
-        """activation code of the kernels (include/vt_amd.h): 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 SiLU, 4 GELU (exact)"""
+        """activation code of the kernels (include/vt_amd.h): 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 SiLU, 4 GELU (exact); the kernels
+        also take 5 ReLU6 and 6 Hardswish (the MobileNets), which the reference's ConvNormAct does not have"""
         a = self.act
         if isinstance(a, nn.Identity):
             return 0

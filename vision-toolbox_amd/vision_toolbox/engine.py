@@ -574,6 +574,7 @@ class Builder:
         self._talk_scratch: dict[int, Buf] = {}  # talking-heads attention: delta and the parameter-gradient shares, per size
         self._dw3_scratch: dict[int, Buf] = {}  # depthwise 3x3 + GELU + pool: the per-image filter-gradient shares, per size
         self._gconv_scratch: dict[int, Buf] = {}  # grouped 3x3: the filter gradient's slabs, per size
+        self._dwt_scratch: dict[int, Buf] = {}  # tiled depthwise: the filter-gradient shares of the bands, per size
 
     # -- memory -----------------------------------------------------------------
     def alloc(self, nbytes: int, name: str = "") -> Buf:
@@ -876,7 +877,7 @@ class Builder:
         pass) are not taken: the unit runs the general kernel plus those passes.
         Validation and dispatch: grouped -> depthwise -> pointwise -> the general kernels."""
         conv, bn_spec = self._specs(conv, norm)
-        relu = int(relu)  # activation code: 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 SiLU, 4 GELU (include/vt_amd.h)
+        relu = int(relu)  # activation code: 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 SiLU, 4 GELU, 5 ReLU6, 6 Hardswish (include/vt_amd.h)
         pre_act = bool(residual_pre_act)
         if pre_act and (residual is None or bn_spec is None or relu != 1 or conv.groups != 1 or pool_out is not None):
             raise NotImplementedError(f"{name}: residual_pre_act is relu(bn(conv(x)) + residual): it needs a residual, a "
@@ -1414,6 +1415,76 @@ class Builder:
                     gx, res = self.grad_target(x)
                     self.emit(N.OP_GCONV3_DGRAD, [dz.addr(), wptr, gx.addr(), _addr(res)], [dz.ld, gx.ld, _ld(res)] + geo)
                     self.grad_written(x)
+
+            self._node(y, bwd)
+        return y
+
+    # -- tiled depthwise units (vt_dwtile.hip) --------------------------------------------------------------------------
+    def depthwise_unit(self, x: TRef, conv, norm, act, out: Optional[TRef] = None, name: str = "dw") -> TRef:
+        """y = act(bn(conv(x))) for nn.Conv2d(C, C, k, stride, (k - 1) / 2, groups=C, bias=False) with k in {3, 5} and stride in
+        {1, 2} -- the depthwise unit of a MobileNet block -- on the tiled kernels: vt_dwt_fwd (+ batch statistics) -> the ordinary
+        BatchNorm finalize (or eval coefficients) -> the normalise pass with any activation code; backward: the ordinary BatchNorm
+        backward -> vt_dwt_bwd (d(x) and the filter-gradient shares of the bands in one launch) -> vt_dwt_wgrad_reduce, both on
+        the main stream (the shares scratch is one per size).  No float atomics: it is the same program in deterministic mode.
+        ConvNormAct(groups=C) does not come here: it keeps _depthwise_unit.  A geometry the kernels do not take is refused."""
+        conv, bn_spec = self._specs(conv, norm)
+        act, dt, epc = int(act), self.dtype, _EPC[self.dtype]
+        Cc, k, s = conv.in_channels, conv.k, conv.stride
+        if conv.groups != Cc or conv.out_channels != Cc or conv.bias is not None or bn_spec is None:
+            raise NotImplementedError(f"{name}: the tiled depthwise unit is Conv2d(C, C, k, groups=C, bias=False) -> BatchNorm2d")
+        if k not in (3, 5) or s not in (1, 2) or conv.padding != (k - 1) // 2 or conv.dilation != 1:
+            raise NotImplementedError(f"{name}: kernel_size={k}, stride={s}, padding={conv.padding}, dilation={conv.dilation} -- "
+                                      "vt_dwt_* take kernel_size 3 or 5, stride 1 or 2, padding (k - 1) / 2, dilation 1")
+        if Cc % epc:
+            raise NotImplementedError(f"{name}: {Cc} channels must be a multiple of {epc} for dtype {dt}")
+        if x.logical_c != Cc or x.C != Cc:
+            raise ValueError(f"{name}: conv expects {Cc} (unpadded) input channels, got {x.logical_c}")
+        if not 0 <= act <= 6:
+            raise NotImplementedError(f"{name}: activation code {act}")
+        B = x.B
+        nbytes = int(N.lib().vt_dwt_shares_bytes(B, x.H, x.W, Cc, k, s, dt))
+        if nbytes < 0:
+            raise NotImplementedError(f"{name}: {N.last_error()}")
+        Ho, Wo = conv.out_size(x.H, x.W)
+        M = B * Ho * Wo
+        y = out if out is not None else self.act(B, Ho, Wo, Cc, name + ".y")
+        assert (y.B, y.H, y.W, y.C) == (B, Ho, Wo, Cc), "out geometry mismatch"
+        self.tag += 1
+        self.n_units += 1
+        w = conv.weight
+        wptr = self.pref(w)  # the f32 master [C][k*k] (the kernels round it for bf16 launches)
+        geo = [B, x.H, x.W, Cc, k, s, dt]
+        bn = _BNEmitter(self, bn_spec, Cc)
+        z = self.act(B, Ho, Wo, Cc, name + ".z")
+        # (the unit follows ITS BatchNorm's flag, as conv_unit does)
+        stats = self.zeroed_f32(N.stat_floats(Cc), "stats") if bn_spec.training else None
+        self.emit(N.OP_DWT_FWD, [x.addr(), wptr, z.addr(), self.bp(stats) if stats is not None else None], [x.ld, z.ld] + geo)
+        if stats is not None:
+            bn.finalize(stats, M)
+        else:
+            bn.eval_coeffs()
+        self._act_apply(z, bn.cp[0], bn.cp[1], None, y, act)
+        if self.need_grad:
+
+            def bwd(dy):
+                sums, bcoef, dz = bn.bwd_buffers(y, name + ".dz")
+                bn.bwd_three_launches(dy, z, act, sums, bcoef, dz)
+                if not (w.requires_grad or x.needs_grad):
+                    return
+                # (one scratch per size: the launch that fills it and the one that reads it follow each other on one stream)
+                scratch = self._dwt_scratch.get(nbytes)
+                if scratch is None:
+                    scratch = self._dwt_scratch[nbytes] = self.alloc(nbytes, "dwt_shares")
+                if x.needs_grad:
+                    gx, res = self.grad_target(x)
+                else:  # (the launch always forms d(x))
+                    gx, res = self.act(B, x.H, x.W, Cc, name + ".dx", needs_grad=False), None
+                self.emit(N.OP_DWT_BWD, [dz.addr(), x.addr(), wptr, gx.addr(), _addr(res), self.bp(scratch)],
+                          [dz.ld, x.ld, gx.ld, _ld(res)] + geo, [nbytes])
+                if x.needs_grad:
+                    self.grad_written(x)
+                if w.requires_grad:
+                    self.emit(N.OP_DWT_WGRAD_REDUCE, [self.bp(scratch), self.pgrad(w)], geo, [nbytes])
 
             self._node(y, bwd)
         return y
@@ -2524,6 +2595,31 @@ class Builder:
                 self.grad_written(x)
                 gs_, _ = self.grad_target(s)
                 self.emit(N.OP_COPY2D, [self.bp(ds32), gs_.addr()], [N.VT_F32, self.dtype, x.C, 0], [x.C, gs_.ld, x.B])
+
+            self._node(y, bwd)
+        return y
+
+    def hsig_gate(self, a: TRef, s: TRef, out: Optional[TRef] = None, name: str = "se") -> TRef:
+        """y = a * hardsigmoid(s): the Squeeze-Excitation scale of MobileNetV3, s a [B, 1, 1, C] row per image -- the gate of
+        `ese` without a residual (vt_ese_gate_fwd).  Backward (vt_ese_gate_bwd): d(a), and the f32 d(s) of an (image, column
+        group) summed by its one workgroup in fixed point -- order-free, so deterministic mode keeps it."""
+        if (s.B, s.H, s.W, s.C) != (a.B, 1, 1, a.C):
+            raise ValueError(f"{name}: s is a [B, 1, 1, {a.C}] row per image")
+        self.tag += 1
+        dt = self.dtype
+        y = out if out is not None else self.act(a.B, a.H, a.W, a.C, name + ".y")
+        assert y.same_geom(a), "out geometry mismatch"
+        self.emit(N.OP_ESE_FWD, [a.addr(), s.addr(), None, y.addr()], [a.ld, s.ld, 0, y.ld, a.B, a.H * a.W, a.C, dt])
+        if self.need_grad:
+
+            def bwd(dy):
+                ga, acc = self.grad_accum_target(a)
+                ds32 = self.f32(a.B * a.C, "ds32")
+                self.emit(N.OP_ESE_BWD, [dy.addr(), a.addr(), s.addr(), ga.addr(), self.bp(ds32)],
+                          [dy.ld, a.ld, s.ld, ga.ld, a.B, a.H * a.W, a.C, acc, dt])
+                self.grad_written(a)
+                gs_, _ = self.grad_target(s)
+                self.emit(N.OP_COPY2D, [self.bp(ds32), gs_.addr()], [N.VT_F32, dt, a.C, 0], [a.C, gs_.ld, a.B])
 
             self._node(y, bwd)
         return y

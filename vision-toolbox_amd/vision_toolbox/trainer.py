@@ -262,6 +262,14 @@ class TrainStep:
             if isinstance(backbone, RegNetExtractor) and backbone.se_ratio:
                 raise NotImplementedError(f"exchange='sharded' with {backbone.model_name}: its Squeeze-Excitation weights are "
                                           "read in f32 outside the head bucket (use exchange='allreduce')")
+            from .backbones.mobilenet import MobileNetExtractor
+
+            # (... and for the depthwise filters and Squeeze-Excitation weights of a MobileNet, which vt_dwt_* and vt_se_mlp_fwd
+            #  read as f32 masters)
+            if isinstance(backbone, MobileNetExtractor):
+                raise NotImplementedError(f"exchange='sharded' with {backbone.model_name}: its depthwise filters and "
+                                          "Squeeze-Excitation weights are read in f32 outside the head bucket (use "
+                                          "exchange='allreduce')")
         # who issues the collectives: "torch" = torch.distributed calls between segments of the launch lists (any
         # backend: gloo in the CPU tests); "rccl" = the library's own RCCL communicator (vt_comm_init), the collectives are
         # OPS of the lists (VT_OP_STAT_SYNC in front of every BatchNorm finalize, FORK + VT_OP_ALLREDUCE on the
