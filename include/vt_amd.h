@@ -597,6 +597,66 @@ int vt_se_mlp_fwd(const void* pooled, int32_t ldp, const float* w1, const float*
 int vt_se_mlp_bwd(const void* dlogits, int32_t ldg, const void* pooled, int32_t ldp, const float* w1, const float* w2,
                   const float* hidden, float* dhidden, void* dpooled, int32_t lddp, float* dw1, float* db1, float* dw2, float* db2,
                   int32_t B, int32_t C, int32_t S, int32_t dtype, void* stream);
+/* The same MLP with the squeeze activation given by code: `act` = 1 ReLU (exactly the two entry points above) or 3 SiLU
+ * (EfficientNet).  SiLU's backward needs the pre-activation: with act = 3 `hidden` is f32 [2][B][S], the rounded hidden values
+ * (the operand of dW2) followed by the f32 pre-activations W1 pooled + b1 (the operand of silu'). */
+int vt_se_mlp_act_fwd(const void* pooled, int32_t ldp, const float* w1, const float* b1, const float* w2, const float* b2,
+                      float* hidden, void* logits, int32_t ldl, int32_t B, int32_t C, int32_t S, int32_t act, int32_t dtype,
+                      void* stream);
+int vt_se_mlp_act_bwd(const void* dlogits, int32_t ldg, const void* pooled, int32_t ldp, const float* w1, const float* w2,
+                      const float* hidden, float* dhidden, void* dpooled, int32_t lddp, float* dw1, float* db1, float* dw2,
+                      float* db2, int32_t B, int32_t C, int32_t S, int32_t act, int32_t dtype, void* stream);
+
+/* ---- what an EfficientNet block needs beyond the MobileNet kernels (vt_mbconv.hip) --------------------------------------
+ * BatchNorm passes with a per-image keep factor -- stochastic depth in "row" mode, x + keep[b] * f(x), on the Conv ->
+ * BatchNorm [-> act] unit that closes f.  z, r, y, dy, dz are [M][C] channel-last with row strides ld >= C, M = B * HW rows,
+ * image b = m / HW; `keep` is a device float[B] of any values; `act` is an activation code 0 .. 6 of vt_bn_act_apply.
+ *   vt_bn_keep_apply               y = keep[b] * act(z*scale + shift) + r (r may alias y).  Where keep[b] == 0 the rows of z
+ *                                  are not read and y = r bit for bit
+ *   vt_bn_keep_finalize_apply      the same with vt_bn_finalize inside the launch (the arguments of vt_bn_finalize_apply)
+ *   vt_bn_keep_bwd_reduce          sums (the fixed-point buffer of vt_bn_act_bwd_reduce) += sum g, sum g * xhat with
+ *                                  g = keep[b] * dy * act'(z*scale + shift); a dropped image's dy and z are not read
+ *   vt_bn_keep_bwd_apply           dz = coef0*g - coef1*z + coef2 from the coefficients of vt_bn_bwd_finalize (coef0 is the
+ *                                  scale); a dropped image's z IS read (dz = -coef1*z + coef2 under batch statistics)
+ *   vt_bn_keep_bwd_finalize_apply  the same with vt_bn_bwd_finalize inside the launch
+ * The three backward entries also take `add` (or NULL), a [M / HW][C] row of stride lda in the compute dtype: g = (keep[b] * dy +
+ * add[b][c] / HW) * act'(.), the gradient of a per-image average pool of y joining d(y) in f32; with `add` given `keep` may be NULL
+ * (factor 1), and a dropped image's z is read.
+ * The residual's gradient is dy itself.  No float atomics: two runs of any launch are bit-identical.
+ * Normalise + activation + per-image average pool in one pass (the Squeeze-Excitation pool over the expanded map):
+ *   vt_bn_act_avgpool_apply           y = act(z*scale + shift), bit-identical to vt_bn_act_apply's, and pooled[b][c] = the
+ *                                     mean over the HW rows of image b of y as stored (rounded to dtype): a [B][C] row of
+ *                                     stride ldp in the compute dtype.  `scratch`: vt_bn_act_avgpool_scratch_bytes bytes,
+ *                                     zeroed by the caller (0 bytes: may be NULL) -- where an image is cut into several row
+ *                                     slabs their sums meet there in fixed point
+ *   vt_bn_act_avgpool_finalize_apply  the same with vt_bn_finalize inside the launch */
+int vt_bn_keep_apply(const void* z, int32_t ldz, const float* scale, const float* shift, const void* r, int32_t ldr, void* y,
+                     int32_t ldy, const float* keep, int32_t HW, int64_t M, int32_t C, int32_t act, int32_t dtype, void* stream);
+int vt_bn_keep_finalize_apply(const float* stats, int32_t C, double count, const float* gamma, const float* beta, float eps,
+                              float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked, float* scale,
+                              float* shift, float* mean, float* invstd, const void* z, int32_t ldz, const void* r, int32_t ldr,
+                              void* y, int32_t ldy, const float* keep, int32_t HW, int64_t M, int32_t act, int32_t dtype,
+                              void* stream);
+int vt_bn_keep_bwd_reduce(const void* dy, int32_t lddy, const void* z, int32_t ldz, const float* scale, const float* shift,
+                          const float* mean, const float* invstd, const float* keep, const void* add, int32_t lda, int32_t HW,
+                          int64_t M, int32_t C, int32_t act, int32_t dtype, float* sums, void* stream);
+int vt_bn_keep_bwd_apply(const void* dy, int32_t lddy, const void* z, int32_t ldz, const float* shift, const float* coef,
+                         const float* keep, const void* add, int32_t lda, int32_t HW, void* dz, int32_t lddz, int64_t M, int32_t C,
+                         int32_t act, int32_t dtype, void* stream);
+int vt_bn_keep_bwd_finalize_apply(const float* sums, int32_t C, double count, double pscale, const float* scale, const float* shift,
+                                  const float* mean, const float* invstd, int32_t train, float* dgamma, float* dbeta, float* coef,
+                                  const void* dy, int32_t lddy, const void* z, int32_t ldz, const float* keep, const void* add,
+                                  int32_t lda, int32_t HW, void* dz, int32_t lddz, int64_t M, int32_t act, int32_t dtype,
+                                  void* stream);
+int64_t vt_bn_act_avgpool_scratch_bytes(int32_t B, int32_t HW, int32_t C, int32_t dtype); /* < 0: bad geometry */
+int vt_bn_act_avgpool_apply(const void* z, int32_t ldz, const float* scale, const float* shift, void* y, int32_t ldy, void* pooled,
+                            int32_t ldp, void* scratch, int32_t B, int32_t HW, int32_t C, int32_t act, int32_t dtype,
+                            void* stream);
+int vt_bn_act_avgpool_finalize_apply(const float* stats, int32_t C, double count, const float* gamma, const float* beta, float eps,
+                                     float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                     float* scale, float* shift, float* mean, float* invstd, const void* z, int32_t ldz, void* y,
+                                     int32_t ldy, void* pooled, int32_t ldp, void* scratch, int32_t B, int32_t HW, int32_t act,
+                                     int32_t dtype, void* stream);
 
 /* ---- tiled depthwise convolution of the MobileNet Conv-BN-act units (vt_dwtile.hip) -------------------------------------
  * k in {3, 5}, stride s in {1, 2}, padding (k - 1) / 2, dilation 1; C a multiple of 8 (bf16) / 4 (f32); any Hi, Wi >= 1 whose
@@ -989,6 +1049,13 @@ enum vt_op_kind {
     VT_OP_DWT_FWD,                  /* vt_dwt_fwd */
     VT_OP_DWT_BWD,                  /* vt_dwt_bwd */
     VT_OP_DWT_WGRAD_REDUCE,         /* vt_dwt_wgrad_reduce */
+    VT_OP_BN_KEEP_APPLY,            /* vt_bn_keep_apply */
+    VT_OP_BN_KEEP_FIN_APPLY,        /* vt_bn_keep_finalize_apply */
+    VT_OP_BN_KEEP_BWD_REDUCE,       /* vt_bn_keep_bwd_reduce */
+    VT_OP_BN_KEEP_BWD_APPLY,        /* vt_bn_keep_bwd_apply */
+    VT_OP_BN_KEEP_BWD_FIN_APPLY,    /* vt_bn_keep_bwd_finalize_apply */
+    VT_OP_BN_ACT_AVGPOOL_APPLY,     /* vt_bn_act_avgpool_apply */
+    VT_OP_BN_ACT_AVGPOOL_FIN_APPLY, /* vt_bn_act_avgpool_finalize_apply */
     VT_OP_KIND_END
 };
 

@@ -28,6 +28,7 @@
 // VT_CONV_STATS.  Filter gradient: the pixels are cut into S slabs, a wave owns (slab, group, 16 filter rows, filter row
 // kh) and stores its partial tile into scratch [S][C][9][gw]; a second kernel adds the slabs in slab order, one owner per
 // filter element (dw += sum).  No float atomics anywhere: two runs are bit-identical.
+#include "vt_act.h"
 #include "vt_common.h"
 
 namespace {
@@ -414,11 +415,12 @@ struct SeArgs {
     const void* pooled;   // fwd: [B][C]; bwd: the same rows again
     const void* dlogits;  // bwd
     const float *w1, *b1, *w2, *b2;
-    float* hidden;        // [B][S] f32, holds storage-rounded values
+    float* hidden;        // [B][S] f32, holds storage-rounded values; act = 3: followed by the [B][S] f32 pre-activations
     void* out;            // fwd: logits; bwd: dpooled
     float* dhid;          // bwd: [B][S] d(pre-activation)
     float *dw1, *db1, *dw2, *db2;
     int B, C, S, ldp, ldo, ldg;
+    int act;              // the squeeze activation: 1 ReLU, 3 SiLU (vt_act.h)
 };
 
 template <typename T>
@@ -437,8 +439,11 @@ __global__ void __launch_bounds__(kT) se_mlp_fwd_kernel(const SeArgs a) {
         float acc = 0.f;
         for (int c = lane; c < a.C; c += 64) acc = fmaf(VecIO<T>::round(wr[c]), sp[c], acc);
         acc = wave_sum(acc) + a.b1[s];
-        const float h = VecIO<T>::round(acc > 0.f ? acc : 0.f);
-        if (lane == 0) sh[s] = h, a.hidden[(long)b * a.S + s] = h;
+        const float h = VecIO<T>::round(a.act == 3 ? act_fwd(3, acc) : (acc > 0.f ? acc : 0.f));
+        if (lane == 0) {
+            sh[s] = h, a.hidden[(long)b * a.S + s] = h;
+            if (a.act == 3) a.hidden[((long)a.B + b) * a.S + s] = acc;  // silu' needs the pre-activation
+        }
     }
     __syncthreads();
     T* o = (T*)a.out + (long)b * a.ldo;
@@ -450,7 +455,7 @@ __global__ void __launch_bounds__(kT) se_mlp_fwd_kernel(const SeArgs a) {
     }
 }
 
-// backward, per image: d(pre) = (W2^T dl) * [h > 0] -> dhid, then d(pooled) = W1^T d(pre)
+// backward, per image: d(pre) = (W2^T dl) * [h > 0] (SiLU: * silu'(pre)) -> dhid, then d(pooled) = W1^T d(pre)
 template <typename T>
 __global__ void __launch_bounds__(kT) se_mlp_bwd_kernel(const SeArgs a) {
     __shared__ float sg[kSeMaxC];
@@ -462,7 +467,8 @@ __global__ void __launch_bounds__(kT) se_mlp_bwd_kernel(const SeArgs a) {
     for (int s = t; s < a.S; s += kT) {  // one owner per hidden value, channels in order
         float acc = 0.f;
         for (int c = 0; c < a.C; ++c) acc = fmaf(VecIO<T>::round(a.w2[(long)c * a.S + s]), sg[c], acc);
-        const float d = a.hidden[(long)b * a.S + s] > 0.f ? acc : 0.f;
+        const float d = a.act == 3 ? acc * act_grad(3, a.hidden[((long)a.B + b) * a.S + s])
+                                   : (a.hidden[(long)b * a.S + s] > 0.f ? acc : 0.f);
         sd[s] = d, a.dhid[(long)b * a.S + s] = d;
     }
     __syncthreads();
@@ -596,13 +602,20 @@ int vt_gconv3_wgrad(const void* x, int32_t ldx, const void* dz, int32_t lddz, fl
 
 int vt_se_mlp_fwd(const void* pooled, int32_t ldp, const float* w1, const float* b1, const float* w2, const float* b2, float* hidden,
                   void* logits, int32_t ldl, int32_t B, int32_t C, int32_t S, int32_t dtype, void* stream) {
+    return vt_se_mlp_act_fwd(pooled, ldp, w1, b1, w2, b2, hidden, logits, ldl, B, C, S, 1, dtype, stream);
+}
+
+int vt_se_mlp_act_fwd(const void* pooled, int32_t ldp, const float* w1, const float* b1, const float* w2, const float* b2,
+                      float* hidden, void* logits, int32_t ldl, int32_t B, int32_t C, int32_t S, int32_t act, int32_t dtype,
+                      void* stream) {
     VT_TRY(se_check("vt_se_mlp_fwd", B, C, S, dtype));
+    VT_REQUIRE(act == 1 || act == 3, VT_ERR_UNSUPPORTED, "vt_se_mlp_fwd: activation code %d (1 ReLU, 3 SiLU)", act);
     VT_REQUIRE(pooled && w1 && b1 && w2 && b2 && hidden && logits && ldp >= C && ldl >= C, VT_ERR_INVALID,
                "vt_se_mlp_fwd: null argument or bad strides");
     SeArgs a;
     memset(&a, 0, sizeof(a));
     a.pooled = pooled, a.w1 = w1, a.b1 = b1, a.w2 = w2, a.b2 = b2, a.hidden = hidden, a.out = logits;
-    a.B = B, a.C = C, a.S = S, a.ldp = ldp, a.ldo = ldl;
+    a.B = B, a.C = C, a.S = S, a.ldp = ldp, a.ldo = ldl, a.act = act;
     if (dtype == VT_BF16) hipLaunchKernelGGL(se_mlp_fwd_kernel<bf16_t>, dim3(B), dim3(kT), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(se_mlp_fwd_kernel<float>, dim3(B), dim3(kT), 0, (hipStream_t)stream, a);
     VT_CHECK_LAUNCH("vt_se_mlp_fwd");
@@ -612,14 +625,22 @@ int vt_se_mlp_fwd(const void* pooled, int32_t ldp, const float* w1, const float*
 int vt_se_mlp_bwd(const void* dlogits, int32_t ldg, const void* pooled, int32_t ldp, const float* w1, const float* w2,
                   const float* hidden, float* dhidden, void* dpooled, int32_t lddp, float* dw1, float* db1, float* dw2, float* db2,
                   int32_t B, int32_t C, int32_t S, int32_t dtype, void* stream) {
+    return vt_se_mlp_act_bwd(dlogits, ldg, pooled, ldp, w1, w2, hidden, dhidden, dpooled, lddp, dw1, db1, dw2, db2, B, C, S, 1, dtype,
+                             stream);
+}
+
+int vt_se_mlp_act_bwd(const void* dlogits, int32_t ldg, const void* pooled, int32_t ldp, const float* w1, const float* w2,
+                      const float* hidden, float* dhidden, void* dpooled, int32_t lddp, float* dw1, float* db1, float* dw2,
+                      float* db2, int32_t B, int32_t C, int32_t S, int32_t act, int32_t dtype, void* stream) {
     VT_TRY(se_check("vt_se_mlp_bwd", B, C, S, dtype));
+    VT_REQUIRE(act == 1 || act == 3, VT_ERR_UNSUPPORTED, "vt_se_mlp_bwd: activation code %d (1 ReLU, 3 SiLU)", act);
     VT_REQUIRE(dlogits && pooled && w1 && w2 && hidden && dhidden && ldg >= C && ldp >= C && (!dpooled || lddp >= C),
                VT_ERR_INVALID, "vt_se_mlp_bwd: null argument or bad strides");
     SeArgs a;
     memset(&a, 0, sizeof(a));
     a.dlogits = dlogits, a.pooled = pooled, a.w1 = w1, a.w2 = w2, a.hidden = const_cast<float*>(hidden), a.dhid = dhidden;
     a.out = dpooled, a.dw1 = dw1, a.db1 = db1, a.dw2 = dw2, a.db2 = db2;
-    a.B = B, a.C = C, a.S = S, a.ldp = ldp, a.ldo = lddp, a.ldg = ldg;
+    a.B = B, a.C = C, a.S = S, a.ldp = ldp, a.ldo = lddp, a.ldg = ldg, a.act = act;
     hipStream_t st = (hipStream_t)stream;
     const long n = 2L * S * C + S + C;
     if (dtype == VT_BF16) {

@@ -1,0 +1,657 @@
+// vt_mbconv.hip -- what a torchvision EfficientNet block needs beyond the MobileNet kernels.
+//
+// 1. BatchNorm passes with a per-image keep factor (stochastic depth, "row" mode).  A residual MBConv / FusedMBConv block is
+//    x + keep[b] * f(x) in training mode; f ends in a Conv -> BatchNorm [-> act] unit, so the factor rides on that unit's
+//    normalise pass and on its BatchNorm backward.  With b = m / HW the image of row m:
+//      forward          y  = keep[b] * act(z*scale + shift) + r                 (r may alias y)
+//      backward reduce  g  = keep[b] * dy * act'(z*scale + shift);  sums[0][c] += sum g,  sums[1][c] += sum g * xhat
+//      backward apply   dz = coef0*g - coef1*z + coef2
+//    `keep` is a device float[B] of ANY values (0 and 1 / (1 - p) in training).  Where keep[b] == 0 the forward copies r and
+//    never reads z, the backward reduce reads neither dy nor z; the backward apply still reads z (under batch statistics dz of
+//    a dropped image is -coef1*z + coef2, not zero) and skips dy.  The residual's gradient is dy itself (the caller's).
+//    The two backward passes also take a per-(image, channel) ADDEND: g = (keep[b] * dy + add[b][c] / HW) * act'(.), keep NULL
+//    meaning 1 -- the gradient of a per-image average pool of y (the Squeeze-Excitation pool of pass 2 below) joins d(y) in f32
+//    inside the BatchNorm backward, instead of being added to an already rounded d(y) by a pass of its own.
+//    Forward and backward apply exist with the finalize step inside the launch (vt_bn_fin.h) and with ready coefficients,
+//    as in vt_resnet.hip; every activation code of vt_act.h is taken.  Streaming kernels on the RowMap: 16 bytes per lane,
+//    kUnroll rows in flight, plain vector stores; the only atomics are the integer ones of the statistics buffer.
+// 2. Normalise + activation + per-image average pool in one pass: y = act(z*scale + shift) and pooled[b][c] = the mean over
+//    the image's pixels of y AS STORED (rounded to the compute dtype) -- the operand of the Squeeze-Excitation MLP, which
+//    otherwise costs one more read of the expanded map (vt_global_avgpool_fwd).  A workgroup owns one (image, row slab,
+//    channel group): with one slab per image it writes the pooled row itself; with several the slabs' sums meet in a zeroed
+//    fixed-point scratch (integer atomics: order-free) that a B x C finishing launch turns into the row.
+#include "vt_act.h"
+#include "vt_bn_fin.h"
+#include "vt_common.h"
+#include "vt_rowmap.h"
+
+namespace {
+
+// ---------------------------------------------------------------------------------
+// y = keep[b] * act(z*scale + shift) + r; kFin: grid (row blocks, channel groups of Cg channels), coefficients finalized in
+// the launch (r and y are not __restrict__: they may be the same tensor -- every element is read and written by one thread)
+// ---------------------------------------------------------------------------------
+template <typename T, bool kFin>
+__global__ void __launch_bounds__(kThreads)
+bn_keep_apply_kernel(const VtFinFwd f, const float* __restrict__ scale, const float* __restrict__ shift, const T* __restrict__ z,
+                     int ldz, const T* r, int ldr, T* y, int ldy, const float* __restrict__ keep, unsigned HW, long M, RowMap rm,
+                     int Cg, int act) {
+    constexpr int EPC = VecIO<T>::EPC;
+    __shared__ float s_sc[kFinCg], s_sf[kFinCg];
+    const int t = threadIdx.x;
+    const int cg0 = blockIdx.y * Cg;
+    if constexpr (kFin) {
+        vt_pair_sums<false>(f.stats, f.C, cg0, cg0 + Cg, [&](int c) { return vt_fin_fwd_pre(f, c); },
+                            [&](int c, double s, double ss, const VtFinFwdPre& p) {
+                                float sc, sf;
+                                vt_fin_fwd_channel(f, c, s, ss, p.g, p.b, p.rm, p.rv, sc, sf, blockIdx.x == 0);
+                                s_sc[c - cg0] = sc, s_sf[c - cg0] = sf;
+                            });
+        __syncthreads();
+    }
+    z += cg0, y += cg0, r += cg0;
+    const int rl = t / rm.CT;
+    if (rl >= rm.RT) return;
+    const long row0 = (long)blockIdx.x * rm.RT * rm.iters + rl;
+    for (int col = t % rm.CT; col < rm.CPR; col += rm.CT) {
+        float sc[EPC], sf[EPC];
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) {
+            if constexpr (kFin) sc[e] = s_sc[col * EPC + e], sf[e] = s_sf[col * EPC + e];
+            else sc[e] = scale[col * EPC + e], sf[e] = shift[col * EPC + e];
+        }
+        const T* pz = z + row0 * ldz + col * EPC;
+        const T* pr = r + row0 * ldr + col * EPC;
+        T* py = y + row0 * ldy + col * EPC;
+        const long sz = (long)rm.RT * ldz, sr = (long)rm.RT * ldr, sy = (long)rm.RT * ldy;
+        for (int it = 0; it < rm.iters; it += kUnroll) {
+            uint4 vz[kUnroll], vr[kUnroll];
+            float kp[kUnroll];
+            bool ok[kUnroll];
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) {
+                const long row = row0 + (long)(it + u) * rm.RT;
+                ok[u] = (it + u < rm.iters) && row < M;
+                vz[u] = vr[u] = make_uint4(0, 0, 0, 0);
+                kp[u] = 0.f;
+                if (ok[u]) {
+                    kp[u] = keep[(unsigned)row / HW];
+                    vr[u] = ld16(pr + (it + u) * sr);
+                    if (kp[u] != 0.f) vz[u] = ld16(pz + (it + u) * sz);  // (a dropped image's z is never read)
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) {
+                if (!ok[u]) continue;
+                if (kp[u] == 0.f) {  // y = r, bit for bit
+                    st16(py + (it + u) * sy, vr[u]);
+                    continue;
+                }
+                float v[EPC], rr[EPC];
+                VecIO<T>::unpack(vz[u], v);
+                VecIO<T>::unpack(vr[u], rr);
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) v[e] = fmaf(kp[u], act_fwd(act, fmaf(v[e], sc[e], sf[e])), rr[e]);
+                st16(py + (it + u) * sy, VecIO<T>::pack(v));
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// backward, pass 1: per-channel sum(g) and sum(g*xhat), g = keep[b] * dy * act'(z*scale + shift) (the structure of
+// bn_bwd_reduce_kernel, vt_elementwise.hip); grid (row blocks, channel groups of C channels each of Ctot)
+// ---------------------------------------------------------------------------------
+// (kAdd: the addend form is an instantiation of its own, so that the passes of a residual block keep their registers)
+template <typename T, bool kAdd>
+__global__ void __launch_bounds__(kThreads)
+bn_keep_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ z, int ldz, const float* __restrict__ scale,
+                          const float* __restrict__ shift, const float* __restrict__ mean, const float* __restrict__ invstd,
+                          const float* __restrict__ keep, const T* __restrict__ add, int lda, unsigned HW, long M, int C, RowMap rm,
+                          int act, float* __restrict__ sums, int Ctot) {
+    constexpr int EPC = VecIO<T>::EPC;
+    // [rows][2][CT*EPC] partial sums, folded by the first 2*CT*EPC threads (no LDS atomics)
+    extern __shared__ __attribute__((aligned(16))) float sred[];
+    const int t = threadIdx.x;
+    const int r = t / rm.CT;
+    const int tc = t % rm.CT;
+    const int W = rm.CT * EPC;  // channels covered per pass
+    const long row0 = (long)blockIdx.x * rm.RT * rm.iters + r;
+    const int rep = blockIdx.x % kStatReplicas;
+    const int cg0 = blockIdx.y * rm.CPR;  // first 16-byte chunk of this channel group
+    dy += (long)cg0 * EPC, z += (long)cg0 * EPC;
+    if constexpr (kAdd) add += (long)cg0 * EPC;
+    const float ascale = 1.f / (float)HW;
+    scale += cg0 * EPC, shift += cg0 * EPC, mean += cg0 * EPC, invstd += cg0 * EPC;
+    for (int cbase = 0; cbase < rm.CPR; cbase += rm.CT) {
+        const int col = cbase + tc;
+        const bool active = (r < rm.RT) && (col < rm.CPR);
+        float s1[EPC], s2[EPC];
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) s1[e] = s2[e] = 0.f;
+        if (active) {
+            float sc[EPC], sf[EPC], mu[EPC];
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) {
+                sc[e] = scale[col * EPC + e];
+                sf[e] = shift[col * EPC + e];
+                mu[e] = mean[col * EPC + e];
+            }
+            const T* pg = dy + row0 * lddy + col * EPC;
+            const T* pz = z + row0 * ldz + col * EPC;
+            const long sg = (long)rm.RT * lddy, sz = (long)rm.RT * ldz;
+            for (int it = 0; it < rm.iters; it += kUnroll) {
+                uint4 vg[kUnroll], vz[kUnroll], va[kUnroll];
+                float kp[kUnroll];
+                bool on[kUnroll];
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u) {
+                    const long row = row0 + (long)(it + u) * rm.RT;
+                    vg[u] = vz[u] = va[u] = make_uint4(0, 0, 0, 0);
+                    kp[u] = 0.f;
+                    on[u] = false;
+                    if ((it + u < rm.iters) && row < M) {
+                        const unsigned b = (unsigned)row / HW;
+                        kp[u] = keep ? keep[b] : 1.f;
+                        if constexpr (kAdd) va[u] = ld16(add + (long)b * lda + col * EPC);
+                        on[u] = kAdd || kp[u] != 0.f;
+                        if (kp[u] != 0.f) vg[u] = ld16(pg + (it + u) * sg);
+                        if (on[u]) vz[u] = ld16(pz + (it + u) * sz);  // (a dropped image without an addend: neither is read)
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u) {
+                    if (!on[u]) continue;
+                    float g[EPC], zz[EPC], aa[EPC];
+                    VecIO<T>::unpack(vg[u], g);
+                    VecIO<T>::unpack(vz[u], zz);
+                    VecIO<T>::unpack(va[u], aa);
+#pragma unroll
+                    for (int e = 0; e < EPC; ++e) {
+                        float d = kp[u] * g[e];
+                        if constexpr (kAdd) d = kp[u] != 0.f ? fmaf(kp[u], g[e], aa[e] * ascale) : aa[e] * ascale;
+                        const float gg = d * act_grad(act, fmaf(zz[e], sc[e], sf[e]));
+                        s1[e] += gg;
+                        s2[e] = fmaf(gg, zz[e] - mu[e], s2[e]);  // invstd applied once, below
+                    }
+                }
+            }
+        }
+        // with CT a power of two below 64 a wave holds 64 / CT row lanes of every column it touches: folded in registers
+        // first (xor shuffles), so the LDS staging is kThreads / 64 rows instead of RT
+        const bool inwave = rm.CT < 64 && (rm.CT & (rm.CT - 1)) == 0;
+        int rows_l = rm.RT, r_l = r;
+        if (inwave) {
+            for (int off = rm.CT; off < 64; off <<= 1) {
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) {
+                    s1[e] += __shfl_xor(s1[e], off, 64);
+                    s2[e] += __shfl_xor(s2[e], off, 64);
+                }
+            }
+            rows_l = kThreads / 64;
+            r_l = (t & 63) < rm.CT ? (t >> 6) : -1;  // one writer per (wave, column)
+        } else if (r >= rm.RT) {
+            r_l = -1;
+        }
+        if (r_l >= 0) {
+            float4* d1 = (float4*)(sred + ((long)(r_l * 2 + 0) * W + tc * EPC));
+            float4* d2 = (float4*)(sred + ((long)(r_l * 2 + 1) * W + tc * EPC));
+#pragma unroll
+            for (int q = 0; q < EPC / 4; ++q) {
+                d1[q] = make_float4(s1[4 * q], s1[4 * q + 1], s1[4 * q + 2], s1[4 * q + 3]);
+                d2[q] = make_float4(s2[4 * q], s2[4 * q + 1], s2[4 * q + 2], s2[4 * q + 3]);
+            }
+        }
+        __syncthreads();
+        for (int i = t; i < 2 * W; i += kThreads) {
+            const int which = i / W, lc = i % W;
+            const int c = cbase * EPC + lc;
+            if (c < C) {
+                float acc = 0.f;
+                for (int rr = 0; rr < rows_l; ++rr) acc += sred[(long)(rr * 2 + which) * W + lc];
+                if (which) acc *= invstd[c];
+                vt_stat_add(sums, ((long)rep * 2 + which) * Ctot + cg0 * EPC + c, acc);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// backward, pass 2: dz = a*g - b*z + d, g = keep[b] * dy * act'(z*a + shift) (a = scale is the first coefficient); kFin: grid
+// (row blocks, channel groups), the backward finalize step inside the launch
+// ---------------------------------------------------------------------------------
+template <typename T, bool kFin, bool kAdd>
+__global__ void __launch_bounds__(kThreads)
+bn_keep_bwd_apply_kernel(const VtFinBwd f, const float* __restrict__ coef, const float* __restrict__ shift,
+                         const T* __restrict__ dy, int lddy, const T* __restrict__ z, int ldz, const float* __restrict__ keep,
+                         const T* __restrict__ add, int lda, unsigned HW, T* __restrict__ dz, int lddz, long M, int C, RowMap rm,
+                         int Cg, int act) {
+    constexpr int EPC = VecIO<T>::EPC;
+    __shared__ float s_a[kFinCg], s_b[kFinCg], s_d[kFinCg];
+    const int t = threadIdx.x;
+    const int cg0 = blockIdx.y * Cg;
+    if constexpr (kFin) {
+        vt_pair_sums<false>(f.sums, f.C, cg0, cg0 + Cg, [&](int c) { return vt_fin_bwd_pre(f, c); },
+                            [&](int c, double s1, double s2, const VtFinBwdPre& p) {
+                                float b, d;
+                                vt_fin_bwd_channel(f, c, s1, s2, p.a, p.mu, p.istd, p.dg, p.db, b, d, blockIdx.x == 0);
+                                s_a[c - cg0] = p.a, s_b[c - cg0] = b, s_d[c - cg0] = d;
+                            });
+        __syncthreads();
+    }
+    dy += cg0, z += cg0, dz += cg0, shift += cg0;
+    if constexpr (kAdd) add += cg0;
+    const float ascale = 1.f / (float)HW;
+    const int r = t / rm.CT;
+    if (r >= rm.RT) return;
+    const long row0 = (long)blockIdx.x * rm.RT * rm.iters + r;
+    for (int col = t % rm.CT; col < rm.CPR; col += rm.CT) {
+        float ca[EPC], cb[EPC], cd[EPC], sf[EPC];
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) {
+            const int c = col * EPC + e;
+            if constexpr (kFin) ca[e] = s_a[c], cb[e] = s_b[c], cd[e] = s_d[c];
+            else ca[e] = coef[c], cb[e] = coef[C + c], cd[e] = coef[2 * C + c];
+            sf[e] = shift[c];
+        }
+        for (int it = 0; it < rm.iters; it += kUnroll) {
+            uint4 vg[kUnroll], vz[kUnroll], va[kUnroll];
+            float kp[kUnroll];
+            bool ok[kUnroll];
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) {
+                const long row = row0 + (long)(it + u) * rm.RT;
+                ok[u] = (it + u < rm.iters) && row < M;
+                vg[u] = vz[u] = va[u] = make_uint4(0, 0, 0, 0);
+                kp[u] = 0.f;
+                if (ok[u]) {
+                    const unsigned b = (unsigned)row / HW;
+                    kp[u] = keep ? keep[b] : 1.f;
+                    if constexpr (kAdd) va[u] = ld16(add + (long)b * lda + col * EPC);
+                    vz[u] = ld16(z + row * ldz + col * EPC);
+                    if (kp[u] != 0.f) vg[u] = ld16(dy + row * lddy + col * EPC);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) {
+                if (!ok[u]) continue;
+                const long row = row0 + (long)(it + u) * rm.RT;
+                float g[EPC], zz[EPC], aa[EPC], o[EPC];
+                VecIO<T>::unpack(vg[u], g);
+                VecIO<T>::unpack(vz[u], zz);
+                VecIO<T>::unpack(va[u], aa);
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) {
+                    float gg;
+                    if constexpr (kAdd) {
+                        const float d = kp[u] != 0.f ? fmaf(kp[u], g[e], aa[e] * ascale) : aa[e] * ascale;
+                        gg = d * act_grad(act, fmaf(zz[e], ca[e], sf[e]));
+                    } else {
+                        gg = kp[u] != 0.f ? kp[u] * g[e] * act_grad(act, fmaf(zz[e], ca[e], sf[e])) : 0.f;
+                    }
+                    o[e] = fmaf(ca[e], gg, fmaf(-cb[e], zz[e], cd[e]));
+                }
+                st16(dz + row * lddz + col * EPC, VecIO<T>::pack(o));
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// y = act(z*scale + shift) and the per-image mean of the stored y.  Grid (B * S, channel groups of Cg channels): workgroup
+// (b, slab) walks rows [slab * rps, (slab + 1) * rps) of image b.  S == 1: the owner writes pooled[b][c]; S > 1: the slab's
+// sums are added to the fixed-point scratch int64[B][C][2] (vt_stat_add) and pool_finish_kernel forms the row.
+// ---------------------------------------------------------------------------------
+struct PoolPlan {
+    int Cg, groups, CPR, CT, RT, S, rps;
+};
+
+template <typename T, bool kFin>
+__global__ void __launch_bounds__(kThreads)
+bn_act_avgpool_kernel(const VtFinFwd f, const float* __restrict__ scale, const float* __restrict__ shift, const T* __restrict__ z,
+                      int ldz, T* __restrict__ y, int ldy, T* __restrict__ pooled, int ldp, float* __restrict__ scratch, int HW,
+                      int Ctot, PoolPlan pp, int act) {
+    constexpr int EPC = VecIO<T>::EPC;
+    __shared__ float s_sc[kFinCg], s_sf[kFinCg];
+    __shared__ float sred[kThreads * EPC];  // [rows][CT*EPC] partial sums of the row lanes
+    const int t = threadIdx.x;
+    const int cg0 = blockIdx.y * pp.Cg;
+    if constexpr (kFin) {
+        vt_pair_sums<false>(f.stats, f.C, cg0, cg0 + pp.Cg, [&](int c) { return vt_fin_fwd_pre(f, c); },
+                            [&](int c, double s, double ss, const VtFinFwdPre& p) {
+                                float sc, sf;
+                                vt_fin_fwd_channel(f, c, s, ss, p.g, p.b, p.rm, p.rv, sc, sf, blockIdx.x == 0);
+                                s_sc[c - cg0] = sc, s_sf[c - cg0] = sf;
+                            });
+        __syncthreads();
+    } else {
+        scale += cg0, shift += cg0;
+    }
+    const int b = blockIdx.x / pp.S, slab = blockIdx.x % pp.S;
+    const int lo = slab * pp.rps, hi = min(HW, lo + pp.rps);
+    z += (long)b * HW * ldz + cg0, y += (long)b * HW * ldy + cg0;
+    const int r = t / pp.CT, tc = t % pp.CT;
+    const int W = pp.CT * EPC;
+    const float inv = 1.f / (float)HW;
+    for (int cbase = 0; cbase < pp.CPR; cbase += pp.CT) {
+        const int col = cbase + tc;
+        const bool active = (r < pp.RT) && (col < pp.CPR);
+        float s[EPC];
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) s[e] = 0.f;
+        if (active) {
+            float sc[EPC], sf[EPC];
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) {
+                if constexpr (kFin) sc[e] = s_sc[col * EPC + e], sf[e] = s_sf[col * EPC + e];
+                else sc[e] = scale[col * EPC + e], sf[e] = shift[col * EPC + e];
+            }
+            for (int hw = lo + r; hw < hi; hw += kUnroll * pp.RT) {
+                uint4 vz[kUnroll];
+                bool ok[kUnroll];
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u) {
+                    ok[u] = hw + u * pp.RT < hi;
+                    vz[u] = make_uint4(0, 0, 0, 0);
+                    if (ok[u]) vz[u] = ld16(z + (long)(hw + u * pp.RT) * ldz + col * EPC);
+                }
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u) {
+                    if (!ok[u]) continue;
+                    float v[EPC];
+                    VecIO<T>::unpack(vz[u], v);
+#pragma unroll
+                    for (int e = 0; e < EPC; ++e) v[e] = act_fwd(act, fmaf(v[e], sc[e], sf[e]));
+                    st16(y + (long)(hw + u * pp.RT) * ldy + col * EPC, VecIO<T>::pack(v));
+#pragma unroll
+                    for (int e = 0; e < EPC; ++e) s[e] += VecIO<T>::round(v[e]);  // the mean of y as stored
+                }
+            }
+        }
+        // the fold of bn_keep_bwd_reduce_kernel: row lanes of a wave in registers where CT is a power of two below 64
+        const bool inwave = pp.CT < 64 && (pp.CT & (pp.CT - 1)) == 0;
+        int rows_l = pp.RT, r_l = r;
+        if (inwave) {
+            for (int off = pp.CT; off < 64; off <<= 1) {
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) s[e] += __shfl_xor(s[e], off, 64);
+            }
+            rows_l = kThreads / 64;
+            r_l = (t & 63) < pp.CT ? (t >> 6) : -1;  // one writer per (wave, column)
+        } else if (r >= pp.RT) {
+            r_l = -1;
+        }
+        if (r_l >= 0) {
+#pragma unroll
+            for (int e = 0; e < EPC; ++e) sred[(long)r_l * W + tc * EPC + e] = s[e];
+        }
+        __syncthreads();
+        for (int lc = t; lc < W; lc += kThreads) {
+            const int c = cbase * EPC + lc;  // (within the channel group)
+            if (c < pp.Cg) {
+                float acc = 0.f;
+                for (int rr = 0; rr < rows_l; ++rr) acc += sred[(long)rr * W + lc];
+                if (pp.S == 1) pooled[(long)b * ldp + cg0 + c] = from_float<T>(acc * inv);
+                else vt_stat_add(scratch, (long)b * Ctot + cg0 + c, acc);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// pooled[b][c] = scratch[b][c] / HW (S > 1)
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+pool_finish_kernel(const float* __restrict__ scratch, T* __restrict__ pooled, int ldp, int B, int C, float inv) {
+    const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= (long)B * C) return;
+    const long long* q = (const long long*)scratch;
+    const long long hi = q[2 * i], lo = q[2 * i + 1];
+    double v = (double)hi * 4096.0 + (double)lo * (1.0 / 8589934592.0);
+    if (hi >= (kStatPoison >> 2) || hi <= -(kStatPoison >> 2)) v = __longlong_as_double(0x7ff8000000000000LL);  // poisoned
+    pooled[(i / C) * ldp + i % C] = from_float<T>((float)v * inv);
+}
+
+// the grid of a pass: as vt_bn_finalize_apply cuts it (VT_BN_FIN_APPLY_WGS workgroups over the channel groups)
+inline RowMap fin_rowmap(int Cg, int groups, int epc, long M) {
+    const int wgs = VT_KNOB("VT_BN_FIN_APPLY_WGS", 1536);
+    return RowMap::make(Cg, epc, M, wgs / groups > 0 ? wgs / groups : 1);
+}
+
+inline int check_keep(const char* who, const float* keep, int HW, long M) {
+    VT_REQUIRE(keep && HW > 0 && M > 0 && M % HW == 0 && M <= 0x7fffffffL, VT_ERR_INVALID,
+               "%s: keep is a float[M / HW] row, M=%ld a multiple of HW=%d below 2^31", who, M, HW);
+    return VT_OK;
+}
+
+// backward: keep may be NULL (factor 1) where the addend row [M / HW][C] is given
+inline int check_keep_add(const char* who, const float* keep, const void* add, int lda, int HW, long M, int C, int dtype) {
+    VT_REQUIRE((keep || add) && HW > 0 && M > 0 && M % HW == 0 && M <= 0x7fffffffL, VT_ERR_INVALID,
+               "%s: a keep row float[M / HW] or an addend [M / HW][C] (or both), M=%ld a multiple of HW=%d below 2^31", who, M, HW);
+    if (add) VT_TRY(check_mat(who, add, lda, C, dtype));
+    return VT_OK;
+}
+
+// the cut of the pool pass: channel groups of Cg channels (the finalize group where C has one; else the whole row), and as
+// many row slabs per image as bring the grid to ~1024 workgroups while every row lane keeps >= 8 rows
+inline PoolPlan pool_plan(int B, int HW, int C, int epc) {
+    PoolPlan p;
+    p.Cg = fin_group(C, epc);
+    if (!p.Cg) p.Cg = C;
+    p.groups = C / p.Cg;
+    p.CPR = p.Cg / epc;
+    p.CT = p.CPR < kThreads ? p.CPR : kThreads;
+    p.RT = kThreads / p.CT;
+    const long owners = (long)B * p.groups;
+    long S = owners >= 1024 ? 1 : (1024 + owners - 1) / owners;
+    const long smax = HW / (p.RT * 8L);
+    if (S > smax) S = smax;
+    if (S < 1) S = 1;
+    p.rps = (int)((HW + S - 1) / S);
+    p.S = (HW + p.rps - 1) / p.rps;
+    return p;
+}
+
+template <bool kFin>
+int launch_pool(const char* who, const VtFinFwd& f, const float* scale, const float* shift, const void* z, int ldz, void* y, int ldy,
+                void* pooled, int ldp, void* scratch, int B, int HW, int C, int act, int dtype, hipStream_t st) {
+    const PoolPlan pp = pool_plan(B, HW, C, vt_epc(dtype));
+    VT_REQUIRE(pp.S == 1 || (scratch && vt_aligned16(scratch)), VT_ERR_INVALID,
+               "%s: %d row slabs per image need the zeroed scratch of vt_bn_act_avgpool_scratch_bytes", who, pp.S);
+    const dim3 grid((unsigned)B * pp.S, pp.groups);
+    VT_DISPATCH_T(dtype, who,
+                  hipLaunchKernelGGL((bn_act_avgpool_kernel<T, kFin>), grid, dim3(kThreads), 0, st, f, scale, shift, (const T*)z, ldz,
+                                     (T*)y, ldy, (T*)pooled, ldp, (float*)scratch, HW, C, pp, act));
+    VT_CHECK_LAUNCH(who);
+    if (pp.S > 1) {
+        const long n = (long)B * C;
+        VT_DISPATCH_T(dtype, who,
+                      hipLaunchKernelGGL(pool_finish_kernel<T>, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                                         (const float*)scratch, (T*)pooled, ldp, B, C, 1.f / (float)HW));
+        VT_CHECK_LAUNCH(who);
+    }
+    return VT_OK;
+}
+
+inline int check_pool(const char* who, const void* z, int ldz, const void* y, int ldy, const void* pooled, int ldp, int B, int HW,
+                      int C, int act, int dtype) {
+    VT_REQUIRE(B > 0 && HW > 0 && (long)B * HW <= 0x7fffffffL && act >= 0 && act <= 6, VT_ERR_INVALID, "%s: bad argument", who);
+    VT_TRY(check_mat(who, z, ldz, C, dtype));
+    VT_TRY(check_mat(who, y, ldy, C, dtype));
+    VT_TRY(check_mat(who, pooled, ldp, C, dtype));
+    return VT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vt_bn_keep_apply(const void* z, int32_t ldz, const float* scale, const float* shift, const void* r, int32_t ldr, void* y,
+                     int32_t ldy, const float* keep, int32_t HW, int64_t M, int32_t C, int32_t act, int32_t dtype, void* stream) {
+    VT_REQUIRE(scale && shift && act >= 0 && act <= 6, VT_ERR_INVALID, "vt_bn_keep_apply: bad argument");
+    VT_TRY(check_keep("vt_bn_keep_apply", keep, HW, (long)M));
+    VT_TRY(check_mat("vt_bn_keep_apply(z)", z, ldz, C, dtype));
+    VT_TRY(check_mat("vt_bn_keep_apply(r)", r, ldr, C, dtype));
+    VT_TRY(check_mat("vt_bn_keep_apply(y)", y, ldy, C, dtype));
+    const RowMap rm = RowMap::make(C, vt_epc(dtype), M);
+    const VtFinFwd f{};
+    VT_DISPATCH_T(dtype, "vt_bn_keep_apply",
+                  hipLaunchKernelGGL((bn_keep_apply_kernel<T, false>), dim3(rm.blocks(M)), dim3(kThreads), 0, (hipStream_t)stream, f,
+                                     scale, shift, (const T*)z, ldz, (const T*)r, ldr, (T*)y, ldy, keep, (unsigned)HW, (long)M, rm, C,
+                                     act));
+    VT_CHECK_LAUNCH("vt_bn_keep_apply");
+    return VT_OK;
+}
+
+int vt_bn_keep_finalize_apply(const float* stats, int32_t C, double count, const float* gamma, const float* beta, float eps,
+                              float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked, float* scale,
+                              float* shift, float* mean, float* invstd, const void* z, int32_t ldz, const void* r, int32_t ldr,
+                              void* y, int32_t ldy, const float* keep, int32_t HW, int64_t M, int32_t act, int32_t dtype,
+                              void* stream) {
+    VT_REQUIRE(stats && scale && shift && mean && invstd && C > 0 && count > 0 && act >= 0 && act <= 6, VT_ERR_INVALID,
+               "vt_bn_keep_finalize_apply: bad argument");
+    VT_REQUIRE((running_mean == nullptr) == (running_var == nullptr), VT_ERR_INVALID,
+               "vt_bn_keep_finalize_apply: running_mean/var must both be given or both NULL");
+    VT_TRY(check_keep("vt_bn_keep_finalize_apply", keep, HW, (long)M));
+    VT_TRY(check_mat("vt_bn_keep_finalize_apply(z)", z, ldz, C, dtype));
+    VT_TRY(check_mat("vt_bn_keep_finalize_apply(r)", r, ldr, C, dtype));
+    VT_TRY(check_mat("vt_bn_keep_finalize_apply(y)", y, ldy, C, dtype));
+    const int Cg = fin_group(C, vt_epc(dtype));
+    if (!Cg || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {  // (no channel group: the two launches)
+        VT_TRY(vt_bn_finalize(stats, C, count, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, scale,
+                              shift, mean, invstd, stream));
+        return vt_bn_keep_apply(z, ldz, scale, shift, r, ldr, y, ldy, keep, HW, M, C, act, dtype, stream);
+    }
+    const int groups = C / Cg;
+    const RowMap rm = fin_rowmap(Cg, groups, vt_epc(dtype), M);
+    const VtFinFwd f{stats, gamma, beta, running_mean, running_var, num_batches_tracked, scale, shift, mean, invstd,
+                     1.0 / count, count > 1.0 ? count / (count - 1.0) : 1.0, eps, momentum, C};
+    VT_DISPATCH_T(dtype, "vt_bn_keep_finalize_apply",
+                  hipLaunchKernelGGL((bn_keep_apply_kernel<T, true>), dim3(rm.blocks(M), groups), dim3(kThreads), 0,
+                                     (hipStream_t)stream, f, (const float*)nullptr, (const float*)nullptr, (const T*)z, ldz,
+                                     (const T*)r, ldr, (T*)y, ldy, keep, (unsigned)HW, (long)M, rm, Cg, act));
+    VT_CHECK_LAUNCH("vt_bn_keep_finalize_apply");
+    return VT_OK;
+}
+
+int vt_bn_keep_bwd_reduce(const void* dy, int32_t lddy, const void* z, int32_t ldz, const float* scale, const float* shift,
+                          const float* mean, const float* invstd, const float* keep, const void* add, int32_t lda, int32_t HW,
+                          int64_t M, int32_t C, int32_t act, int32_t dtype, float* sums, void* stream) {
+    VT_REQUIRE(scale && shift && mean && invstd && sums && act >= 0 && act <= 6, VT_ERR_INVALID,
+               "vt_bn_keep_bwd_reduce: bad argument");
+    VT_TRY(check_keep_add("vt_bn_keep_bwd_reduce", keep, add, lda, HW, (long)M, C, dtype));
+    VT_TRY(check_mat("vt_bn_keep_bwd_reduce(dy)", dy, lddy, C, dtype));
+    VT_TRY(check_mat("vt_bn_keep_bwd_reduce(z)", z, ldz, C, dtype));
+    const int epc = vt_epc(dtype);
+    // the grid of vt_bn_act_bwd_reduce: few, long blocks (each ends with 2*C 64-bit atomics), channel groups of 64 on the
+    // small maps with many channels
+    const int cgroups = (M <= 65536 && C >= 256 && C % 64 == 0) ? C / 64 : 1;
+    const int Cg = C / cgroups;
+    const int blocks_knob = VT_KNOB("VT_BN_RED_BLOCKS", 1024);
+    const RowMap rm = RowMap::make(Cg, epc, M, blocks_knob / cgroups > 0 ? blocks_knob / cgroups : 1);
+    const bool inwave = rm.CT < 64 && (rm.CT & (rm.CT - 1)) == 0;  // (as in the kernel)
+    const int smem = (inwave ? kThreads / 64 : rm.RT) * 2 * rm.CT * epc * (int)sizeof(float);
+#define VT_KEEP_RED(ADD)                                                                                                        \
+    VT_DISPATCH_T(dtype, "vt_bn_keep_bwd_reduce",                                                                               \
+                  hipLaunchKernelGGL((bn_keep_bwd_reduce_kernel<T, ADD>), dim3(rm.blocks(M), cgroups), dim3(kThreads), smem,     \
+                                     (hipStream_t)stream, (const T*)dy, lddy, (const T*)z, ldz, scale, shift, mean, invstd, keep, \
+                                     (const T*)add, lda, (unsigned)HW, (long)M, Cg, rm, act, sums, C))
+    if (add) VT_KEEP_RED(true);
+    else VT_KEEP_RED(false);
+#undef VT_KEEP_RED
+    VT_CHECK_LAUNCH("vt_bn_keep_bwd_reduce");
+    return VT_OK;
+}
+
+int vt_bn_keep_bwd_apply(const void* dy, int32_t lddy, const void* z, int32_t ldz, const float* shift, const float* coef,
+                         const float* keep, const void* add, int32_t lda, int32_t HW, void* dz, int32_t lddz, int64_t M, int32_t C,
+                         int32_t act, int32_t dtype, void* stream) {
+    VT_REQUIRE(shift && coef && act >= 0 && act <= 6, VT_ERR_INVALID, "vt_bn_keep_bwd_apply: bad argument");
+    VT_TRY(check_keep_add("vt_bn_keep_bwd_apply", keep, add, lda, HW, (long)M, C, dtype));
+    VT_TRY(check_mat("vt_bn_keep_bwd_apply(dy)", dy, lddy, C, dtype));
+    VT_TRY(check_mat("vt_bn_keep_bwd_apply(z)", z, ldz, C, dtype));
+    VT_TRY(check_mat("vt_bn_keep_bwd_apply(dz)", dz, lddz, C, dtype));
+    const RowMap rm = RowMap::make(C, vt_epc(dtype), M);
+    const VtFinBwd f{};
+#define VT_KEEP_APPLY(ADD)                                                                                                        \
+    VT_DISPATCH_T(dtype, "vt_bn_keep_bwd_apply",                                                                                  \
+                  hipLaunchKernelGGL((bn_keep_bwd_apply_kernel<T, false, ADD>), dim3(rm.blocks(M)), dim3(kThreads), 0,              \
+                                     (hipStream_t)stream, f, coef, shift, (const T*)dy, lddy, (const T*)z, ldz, keep, (const T*)add, \
+                                     lda, (unsigned)HW, (T*)dz, lddz, (long)M, C, rm, C, act))
+    if (add) VT_KEEP_APPLY(true);
+    else VT_KEEP_APPLY(false);
+#undef VT_KEEP_APPLY
+    VT_CHECK_LAUNCH("vt_bn_keep_bwd_apply");
+    return VT_OK;
+}
+
+int vt_bn_keep_bwd_finalize_apply(const float* sums, int32_t C, double count, double pscale, const float* scale, const float* shift,
+                                  const float* mean, const float* invstd, int32_t train, float* dgamma, float* dbeta, float* coef,
+                                  const void* dy, int32_t lddy, const void* z, int32_t ldz, const float* keep, const void* add,
+                                  int32_t lda, int32_t HW, void* dz, int32_t lddz, int64_t M, int32_t act, int32_t dtype,
+                                  void* stream) {
+    VT_REQUIRE(sums && scale && shift && mean && invstd && coef && C > 0 && count > 0 && act >= 0 && act <= 6, VT_ERR_INVALID,
+               "vt_bn_keep_bwd_finalize_apply: bad argument");
+    VT_TRY(check_keep_add("vt_bn_keep_bwd_finalize_apply", keep, add, lda, HW, (long)M, C, dtype));
+    VT_TRY(check_mat("vt_bn_keep_bwd_finalize_apply(dy)", dy, lddy, C, dtype));
+    VT_TRY(check_mat("vt_bn_keep_bwd_finalize_apply(z)", z, ldz, C, dtype));
+    VT_TRY(check_mat("vt_bn_keep_bwd_finalize_apply(dz)", dz, lddz, C, dtype));
+    const int Cg = fin_group(C, vt_epc(dtype));
+    if (!Cg || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {  // (no channel group: the two launches)
+        VT_TRY(vt_bn_bwd_finalize(sums, C, count, pscale, scale, mean, invstd, train, dgamma, dbeta, coef, stream));
+        return vt_bn_keep_bwd_apply(dy, lddy, z, ldz, shift, coef, keep, add, lda, HW, dz, lddz, M, C, act, dtype, stream);
+    }
+    const int groups = C / Cg;
+    const RowMap rm = fin_rowmap(Cg, groups, vt_epc(dtype), M);
+    const VtFinBwd f{sums, scale, mean, invstd, dgamma, dbeta, coef, 1.0 / count, pscale, C, train};
+#define VT_KEEP_FIN_APPLY(ADD)                                                                                                        \
+    VT_DISPATCH_T(dtype, "vt_bn_keep_bwd_finalize_apply",                                                                             \
+                  hipLaunchKernelGGL((bn_keep_bwd_apply_kernel<T, true, ADD>), dim3(rm.blocks(M), groups), dim3(kThreads), 0,           \
+                                     (hipStream_t)stream, f, (const float*)nullptr, shift, (const T*)dy, lddy, (const T*)z, ldz, keep, \
+                                     (const T*)add, lda, (unsigned)HW, (T*)dz, lddz, (long)M, C, rm, Cg, act))
+    if (add) VT_KEEP_FIN_APPLY(true);
+    else VT_KEEP_FIN_APPLY(false);
+#undef VT_KEEP_FIN_APPLY
+    VT_CHECK_LAUNCH("vt_bn_keep_bwd_finalize_apply");
+    return VT_OK;
+}
+
+int64_t vt_bn_act_avgpool_scratch_bytes(int32_t B, int32_t HW, int32_t C, int32_t dtype) {
+    if (B <= 0 || HW <= 0 || C <= 0 || (dtype != VT_F32 && dtype != VT_BF16) || C % vt_epc(dtype)) return -1;
+    return pool_plan(B, HW, C, vt_epc(dtype)).S > 1 ? (int64_t)B * C * 16 : 0;
+}
+
+int vt_bn_act_avgpool_apply(const void* z, int32_t ldz, const float* scale, const float* shift, void* y, int32_t ldy, void* pooled,
+                            int32_t ldp, void* scratch, int32_t B, int32_t HW, int32_t C, int32_t act, int32_t dtype,
+                            void* stream) {
+    VT_REQUIRE(scale && shift, VT_ERR_INVALID, "vt_bn_act_avgpool_apply: bad argument");
+    VT_TRY(check_pool("vt_bn_act_avgpool_apply", z, ldz, y, ldy, pooled, ldp, B, HW, C, act, dtype));
+    const VtFinFwd f{};
+    return launch_pool<false>("vt_bn_act_avgpool_apply", f, scale, shift, z, ldz, y, ldy, pooled, ldp, scratch, B, HW, C, act, dtype,
+                              (hipStream_t)stream);
+}
+
+int vt_bn_act_avgpool_finalize_apply(const float* stats, int32_t C, double count, const float* gamma, const float* beta, float eps,
+                                     float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                     float* scale, float* shift, float* mean, float* invstd, const void* z, int32_t ldz, void* y,
+                                     int32_t ldy, void* pooled, int32_t ldp, void* scratch, int32_t B, int32_t HW, int32_t act,
+                                     int32_t dtype, void* stream) {
+    VT_REQUIRE(stats && scale && shift && mean && invstd && C > 0 && count > 0, VT_ERR_INVALID,
+               "vt_bn_act_avgpool_finalize_apply: bad argument");
+    VT_REQUIRE((running_mean == nullptr) == (running_var == nullptr), VT_ERR_INVALID,
+               "vt_bn_act_avgpool_finalize_apply: running_mean/var must both be given or both NULL");
+    VT_TRY(check_pool("vt_bn_act_avgpool_finalize_apply", z, ldz, y, ldy, pooled, ldp, B, HW, C, act, dtype));
+    if (!fin_group(C, vt_epc(dtype)) || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {  // (no channel group: the two launches)
+        VT_TRY(vt_bn_finalize(stats, C, count, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, scale,
+                              shift, mean, invstd, stream));
+        return vt_bn_act_avgpool_apply(z, ldz, scale, shift, y, ldy, pooled, ldp, scratch, B, HW, C, act, dtype, stream);
+    }
+    const VtFinFwd f{stats, gamma, beta, running_mean, running_var, num_batches_tracked, scale, shift, mean, invstd,
+                     1.0 / count, count > 1.0 ? count / (count - 1.0) : 1.0, eps, momentum, C};
+    return launch_pool<true>("vt_bn_act_avgpool_finalize_apply", f, nullptr, nullptr, z, ldz, y, ldy, pooled, ldp, scratch, B, HW, C,
+                             act, dtype, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -360,12 +360,41 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
                               I[5], I[6], I[7], I[8], I[9], I[10], st);
         case VT_OP_DWT_WGRAD_REDUCE:  // ptr: shares dw | i: B Hi Wi C k s dtype | f: shares bytes
             return vt_dwt_wgrad_reduce((const float*)P[0], (int64_t)F[0], (float*)P[1], I[0], I[1], I[2], I[3], I[4], I[5], I[6], st);
-        case VT_OP_SE_MLP_FWD:  // ptr: pooled w1 b1 w2 b2 hidden logits | i: ldp ldl B C S dtype
-            return vt_se_mlp_fwd(P[0], I[0], (const float*)P[1], (const float*)P[2], (const float*)P[3], (const float*)P[4],
-                                 (float*)P[5], P[6], I[1], I[2], I[3], I[4], I[5], st);
-        case VT_OP_SE_MLP_BWD:  // ptr: dlogits pooled w1 w2 hidden dhidden dpooled dw1 db1 dw2 db2 | i: ldg ldp lddp B C S dtype
-            return vt_se_mlp_bwd(P[0], I[0], P[1], I[1], (const float*)P[2], (const float*)P[3], (const float*)P[4], (float*)P[5],
-                                 P[6], I[2], (float*)P[7], (float*)P[8], (float*)P[9], (float*)P[10], I[3], I[4], I[5], I[6], st);
+        case VT_OP_SE_MLP_FWD:  // ptr: pooled w1 b1 w2 b2 hidden logits | i: ldp ldl B C S dtype act(0 = ReLU)
+            return vt_se_mlp_act_fwd(P[0], I[0], (const float*)P[1], (const float*)P[2], (const float*)P[3], (const float*)P[4],
+                                     (float*)P[5], P[6], I[1], I[2], I[3], I[4], I[6] ? I[6] : 1, I[5], st);
+        case VT_OP_SE_MLP_BWD:  // ptr: dlogits pooled w1 w2 hidden dhidden dpooled dw1 db1 dw2 db2 | i: ldg ldp lddp B C S dtype act(0 = ReLU)
+            return vt_se_mlp_act_bwd(P[0], I[0], P[1], I[1], (const float*)P[2], (const float*)P[3], (const float*)P[4],
+                                     (float*)P[5], P[6], I[2], (float*)P[7], (float*)P[8], (float*)P[9], (float*)P[10], I[3], I[4],
+                                     I[5], I[7] ? I[7] : 1, I[6], st);
+        case VT_OP_BN_KEEP_APPLY:  // ptr: z scale shift r y keep | i: ldz ldr ldy HW C act dtype | f: M
+            return vt_bn_keep_apply(P[0], I[0], (const float*)P[1], (const float*)P[2], P[3], I[1], P[4], I[2], (const float*)P[5],
+                                    I[3], (int64_t)F[0], I[4], I[5], I[6], st);
+        case VT_OP_BN_KEEP_FIN_APPLY:  // ptr: stats gamma beta rm rv nbt scale shift mean invstd z r y keep | i: C ldz ldr ldy HW act dtype | f: count eps momentum M
+            return vt_bn_keep_finalize_apply((const float*)P[0], I[0], F[0], (const float*)P[1], (const float*)P[2], (float)F[1],
+                                             (float)F[2], (float*)P[3], (float*)P[4], (int64_t*)P[5], (float*)P[6], (float*)P[7],
+                                             (float*)P[8], (float*)P[9], P[10], I[1], P[11], I[2], P[12], I[3], (const float*)P[13],
+                                             I[4], (int64_t)F[3], I[5], I[6], st);
+        case VT_OP_BN_KEEP_BWD_REDUCE:  // ptr: dy z scale shift mean invstd sums keep add | i: lddy ldz HW C act dtype lda | f: M
+            return vt_bn_keep_bwd_reduce(P[0], I[0], P[1], I[1], (const float*)P[2], (const float*)P[3], (const float*)P[4],
+                                         (const float*)P[5], (const float*)P[7], P[8], I[6], I[2], (int64_t)F[0], I[3], I[4], I[5],
+                                         (float*)P[6], st);
+        case VT_OP_BN_KEEP_BWD_APPLY:  // ptr: dy z shift coef dz keep add | i: lddy ldz lddz HW C act dtype lda | f: M
+            return vt_bn_keep_bwd_apply(P[0], I[0], P[1], I[1], (const float*)P[2], (const float*)P[3], (const float*)P[5], P[6], I[7],
+                                        I[3], P[4], I[2], (int64_t)F[0], I[4], I[5], I[6], st);
+        case VT_OP_BN_KEEP_BWD_FIN_APPLY:  // ptr: sums scale shift mean invstd dgamma dbeta coef dy z dz keep add | i: C train lddy ldz lddz HW act dtype lda | f: count pscale(0 = 1) M
+            return vt_bn_keep_bwd_finalize_apply((const float*)P[0], I[0], F[0], F[1] == 0.0 ? 1.0 : F[1], (const float*)P[1],
+                                                 (const float*)P[2], (const float*)P[3], (const float*)P[4], I[1], (float*)P[5],
+                                                 (float*)P[6], (float*)P[7], P[8], I[2], P[9], I[3], (const float*)P[11], P[12], I[8],
+                                                 I[5], P[10], I[4], (int64_t)F[2], I[6], I[7], st);
+        case VT_OP_BN_ACT_AVGPOOL_APPLY:  // ptr: z scale shift y pooled scratch | i: ldz ldy ldp B HW C act dtype
+            return vt_bn_act_avgpool_apply(P[0], I[0], (const float*)P[1], (const float*)P[2], P[3], I[1], P[4], I[2], P[5], I[3], I[4],
+                                           I[5], I[6], I[7], st);
+        case VT_OP_BN_ACT_AVGPOOL_FIN_APPLY:  // ptr: stats gamma beta rm rv nbt scale shift mean invstd z y pooled scratch | i: C ldz ldy ldp B HW act dtype | f: count eps momentum
+            return vt_bn_act_avgpool_finalize_apply((const float*)P[0], I[0], F[0], (const float*)P[1], (const float*)P[2],
+                                                    (float)F[1], (float)F[2], (float*)P[3], (float*)P[4], (int64_t*)P[5],
+                                                    (float*)P[6], (float*)P[7], (float*)P[8], (float*)P[9], P[10], I[1], P[11], I[2],
+                                                    P[12], I[3], P[13], I[4], I[5], I[6], I[7], st);
         case VT_OP_BN_BWD_FUSED:  // ptr: dy z scale shift mean invstd sums sync dgamma dbeta coef dz | i: lddy ldz lddz C relu dtype train | f: M count pscale(0 = 1)
             return vt_bn_act_bwd_fused(P[0], I[0], P[1], I[1], (const float*)P[2], (const float*)P[3], (const float*)P[4],
                                        (const float*)P[5], (int64_t)F[0], I[3], I[4], I[5], F[1], F[2] == 0.0 ? 1.0 : F[2], I[6],

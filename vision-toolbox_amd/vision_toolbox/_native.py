@@ -158,7 +158,14 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_DWT_FWD,
     OP_DWT_BWD,
     OP_DWT_WGRAD_REDUCE,
-) = range(1, 101)
+    OP_BN_KEEP_APPLY,
+    OP_BN_KEEP_FIN_APPLY,
+    OP_BN_KEEP_BWD_REDUCE,
+    OP_BN_KEEP_BWD_APPLY,
+    OP_BN_KEEP_BWD_FIN_APPLY,
+    OP_BN_ACT_AVGPOOL_APPLY,
+    OP_BN_ACT_AVGPOOL_FIN_APPLY,
+) = range(1, 108)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -243,6 +250,13 @@ OP_NAMES = {
     OP_DWT_FWD: "dwt_fwd",
     OP_DWT_BWD: "dwt_bwd",
     OP_DWT_WGRAD_REDUCE: "dwt_wgrad_reduce",
+    OP_BN_KEEP_APPLY: "bn_keep_apply",
+    OP_BN_KEEP_FIN_APPLY: "bn_keep_fin_apply",
+    OP_BN_KEEP_BWD_REDUCE: "bn_keep_bwd_reduce",
+    OP_BN_KEEP_BWD_APPLY: "bn_keep_bwd_apply",
+    OP_BN_KEEP_BWD_FIN_APPLY: "bn_keep_bwd_fin_apply",
+    OP_BN_ACT_AVGPOOL_APPLY: "bn_act_avgpool_apply",
+    OP_BN_ACT_AVGPOOL_FIN_APPLY: "bn_act_avgpool_fin_apply",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -425,6 +439,19 @@ SYMBOLS = {
     "vt_gconv3_wgrad": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i64] + [_i32] * 7 + [_vp]),
     "vt_se_mlp_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32] + [_i32] * 4 + [_vp]),
     "vt_se_mlp_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp] + [_i32] * 4 + [_vp]),
+    "vt_se_mlp_act_fwd": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32] + [_i32] * 5 + [_vp]),
+    "vt_se_mlp_act_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp] + [_i32] * 5 + [_vp]),
+    "vt_bn_keep_apply": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i64, _i32, _i32, _i32, _vp]),
+    "vt_bn_keep_finalize_apply": (_i32, [_vp, _i32, _f64, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp,
+                                         _i32, _vp, _i32, _vp, _i32, _i64, _i32, _i32, _vp]),
+    "vt_bn_keep_bwd_reduce": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "vt_bn_keep_bwd_apply": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i64, _i32, _i32, _i32, _vp]),
+    "vt_bn_keep_bwd_finalize_apply": (_i32, [_vp, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32,
+                                             _vp, _vp, _i32, _i32, _vp, _i32, _i64, _i32, _i32, _vp]),
+    "vt_bn_act_avgpool_scratch_bytes": (_i64, [_i32] * 4),
+    "vt_bn_act_avgpool_apply": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp] + [_i32] * 5 + [_vp]),
+    "vt_bn_act_avgpool_finalize_apply": (_i32, [_vp, _i32, _f64, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
+                                                _vp, _i32, _vp, _i32, _vp] + [_i32] * 4 + [_vp]),
     "vt_dwt_fwd": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp] + [_i32] * 7 + [_vp]),
     "vt_dwt_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i64] + [_i32] * 7 + [_vp]),
     "vt_dwt_wgrad_reduce": (_i32, [_vp, _i64, _vp] + [_i32] * 7 + [_vp]),

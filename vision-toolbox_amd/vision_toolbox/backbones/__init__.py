@@ -1,5 +1,5 @@
 """Backbones of the MI355X hot path: Darknet / CSPDarknet / DarknetYOLOv5 / VoVNet / ConvNeXt / MLP-Mixer / ViT / Swin / CaiT /
-PatchConvNet / DeiT / ResNet / RegNet / MobileNet.
+PatchConvNet / DeiT / ResNet / RegNet / MobileNet / EfficientNet.
 
 Both surfaces the reference snapshot exposes are exported: the classes with
 `from_config` (reference backbones/__init__.py:3,10, tests/test_backbones.py:25-30) and the
@@ -20,8 +20,10 @@ is not imported) runs its add-then-ReLU block ends and its 7x7 stem on the kerne
 (the next class of that file, RegNetBlock written out the same way) runs its grouped 3x3 convolutions in one launch per pass
 and its Squeeze-Excitation MLP on the kernels of vt_gconv.hip.  MobileNetExtractor (the class after it: mobilenet_v2,
 mobilenet_v3_large, mobilenet_v3_small, InvertedResidual written out the same way) runs its depthwise Conv-BN-act units on the
-tiled kernels of vt_dwtile.hip, with ReLU6 / Hardswish in the BatchNorm passes and the hardsigmoid gate of VoVNet's eSE.  The
-reference's last torchvision extractor (EfficientNet) is not part of this build.
+tiled kernels of vt_dwtile.hip, with ReLU6 / Hardswish in the BatchNorm passes and the hardsigmoid gate of VoVNet's eSE.
+EfficientNetExtractor (the last class of that file: efficientnet_b0 .. b7 and efficientnet_v2_s / m / l, MBConv / FusedMBConv
+written out the same way) adds training-mode stochastic depth -- a per-image keep factor in the BatchNorm passes that close
+a residual block -- and the Squeeze-Excitation pool inside the depthwise unit's normalise pass (vt_mbconv.hip).
 """
 from .base import BaseBackbone
 from .convnext import ConvNeXt, ConvNeXtBlock, GlobalResponseNorm
@@ -34,6 +36,7 @@ from .swin import PatchMerging, SwinBlock, SwinTransformer, WindowAttention, win
 from .resnet import BasicBlock, Bottleneck, ResNetExtractor
 from .regnet import RegNetBlock, RegNetExtractor, regnet_block_params
 from .mobilenet import InvertedResidualV2, InvertedResidualV3, MobileNetExtractor
+from .efficientnet import EfficientNetExtractor, FusedMBConv, MBConv
 from .darknet import (
     CSPDarknetStage,
     Darknet,

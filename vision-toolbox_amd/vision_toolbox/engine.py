@@ -414,6 +414,7 @@ class _ConvUnit:
     defer: bool = False  # the normalise pass is held back (_DeferredNorm)
     pre_act: bool = False  # the residual joins BEFORE the activation: y = relu(bn(conv) + residual) (vt_resnet.hip)
     stem7: bool = False  # the 7x7 stride-2 stem as a 4x4 convolution over the space-to-depth image (Builder.stem7_unit)
+    keep: Optional[tuple] = None  # row of the keep table: y = keep[b] * act(bn(conv)) + residual (vt_mbconv.hip)
 
     @property
     def padded(self) -> bool:
@@ -575,6 +576,12 @@ class Builder:
         self._dw3_scratch: dict[int, Buf] = {}  # depthwise 3x3 + GELU + pool: the per-image filter-gradient shares, per size
         self._gconv_scratch: dict[int, Buf] = {}  # grouped 3x3: the filter gradient's slabs, per size
         self._dwt_scratch: dict[int, Buf] = {}  # tiled depthwise: the filter-gradient shares of the bands, per size
+        # stochastic depth ("row" mode): float[n_sites][B] keep factors, one row per residual block in emission order.  The
+        # region is written OUTSIDE the launch lists before every forward (BackboneRunner, TrainStep), as `mix` in the HYPER
+        # buffer is, so captured graphs stay valid; the arena never reuses it, so the backward reads what the forward read.
+        self.keep_buf: Optional[Buf] = None
+        self.keep_rates: "tuple[float, ...]" = ()  # drop probability of every site
+        self.keep_B = 0
 
     # -- memory -----------------------------------------------------------------
     def alloc(self, nbytes: int, name: str = "") -> Buf:
@@ -599,6 +606,17 @@ class Builder:
 
     def f32(self, n: int, name="") -> Buf:
         return self.alloc(n * 4, name)
+
+    def keep_table(self, rates, B: int) -> list:
+        """reserve the keep table of a program -- one float[B] row per residual block with drop probability rates[i] -- and
+        return the rows' addresses, the `keep` operand of conv_unit.  Whoever runs the program fills the table before each
+        forward: bernoulli(1 - p) / (1 - p) per site and image, or the values the user set."""
+        assert self.keep_buf is None, "one keep table per program"
+        self.keep_rates, self.keep_B = tuple(float(p) for p in rates), int(B)
+        if not all(0.0 <= p < 1.0 for p in self.keep_rates):
+            raise ValueError(f"stochastic-depth rates must lie in [0, 1): {self.keep_rates}")
+        self.keep_buf = self.alloc(len(self.keep_rates) * B * 4, "keep")
+        return [self.bp(self.keep_buf, i * B * 4) for i in range(len(self.keep_rates))]
 
     def zeroed_f32(self, n: int, name="", bwd: Optional[bool] = None) -> Buf:
         """f32 scratch zeroed once per run of the list being built (stats / reduction sums)."""
@@ -863,7 +881,7 @@ class Builder:
 
     def conv_unit(self, x: TRef, conv, norm, relu, residual: Optional[TRef] = None, out: Optional[TRef] = None,
                   name: str = "", pool_out: Optional[TRef] = None, defer_norm: bool = False, residual_pre_act: bool = False,
-                  _stem7: Optional[Buf] = None) -> TRef:
+                  _stem7: Optional[Buf] = None, keep: Optional[tuple] = None) -> TRef:
         """y = [relu]([bn](conv(x))) [+ residual], written to `out` when given.  `conv`: nn.Conv2d or ConvSpec, `norm`:
         nn.BatchNorm2d, BNSpec, nn.Identity or None.  `pool_out`: MaxPool2d(3, 2, 1) of y goes there as well -- from the
         unit's own normalise pass where it has one (vt_bn_act_apply_pool), and then the unit's BatchNorm backward reads the
@@ -875,6 +893,10 @@ class Builder:
         statistics as always; the normalise pass and the BatchNorm backward are the add-then-ReLU passes of vt_resnet.hip.
         The paths that cannot honour the mode (the pointwise fold, the fused inference epilogue, a deferred normalise
         pass) are not taken: the unit runs the general kernel plus those passes.
+        `keep`: a row of the keep table (keep_table) -- stochastic depth in "row" mode, y = keep[b] * act(bn(conv(x))) +
+        residual with one factor per image: the normalise pass and the BatchNorm backward are the keep passes of vt_mbconv.hip
+        (any activation code; the residual's gradient stays d(y)).  As with residual_pre_act, the pointwise fold, the fused
+        inference epilogue and a deferred normalise pass are not taken.  keep=None emits what it always emitted.
         Validation and dispatch: grouped -> depthwise -> pointwise -> the general kernels."""
         conv, bn_spec = self._specs(conv, norm)
         relu = int(relu)  # activation code: 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 SiLU, 4 GELU, 5 ReLU6, 6 Hardswish (include/vt_amd.h)
@@ -882,6 +904,9 @@ class Builder:
         if pre_act and (residual is None or bn_spec is None or relu != 1 or conv.groups != 1 or pool_out is not None):
             raise NotImplementedError(f"{name}: residual_pre_act is relu(bn(conv(x)) + residual): it needs a residual, a "
                                       "BatchNorm, ReLU, groups = 1 and no fused pool")
+        if keep is not None and (residual is None or bn_spec is None or conv.groups != 1 or pool_out is not None or pre_act):
+            raise NotImplementedError(f"{name}: keep is keep[b] * act(bn(conv(x))) + residual: it needs a residual, a BatchNorm, "
+                                      "groups = 1, no fused pool and no residual_pre_act")
         if conv.groups != 1:
             return self._grouped_unit(x, conv, bn_spec, relu, residual, out, name, pool_out)
         dt, epc = self.dtype, _EPC[self.dtype]
@@ -897,7 +922,7 @@ class Builder:
             raise ValueError(f"{name}: a {x.H}x{x.W} map is smaller than the dilated {k}x{k} kernel")
         if bn_spec is not None:
             spec = (conv, bn_spec, relu, residual, out, name)
-            if not pre_act and self._pw_ok(x, [spec]):  # (the pointwise passes add the residual behind the ReLU)
+            if not pre_act and keep is None and self._pw_ok(x, [spec]):  # (the pointwise passes add the residual behind the ReLU)
                 y_pw = self.pw_units(x, [spec])[0]
                 if pool_out is not None:
                     self.maxpool3x3s2(y_pw, out=pool_out, name=name + ".max_pool")
@@ -913,11 +938,11 @@ class Builder:
         # the unit follows ITS BatchNorm's flag (a frozen bn.eval() inside a training model uses the
         # running statistics and leaves them untouched, like nn.BatchNorm2d)
         unit_training = bn_spec.training if has_bn else self.training
-        fused = has_bn and not unit_training and not track and not generic_act and not pre_act
+        fused = has_bn and not unit_training and not track and not generic_act and not pre_act and keep is None
         # (a training-mode BatchNorm with activation code < 2, no residual, no pool, no SyncBatchNorm, finalize-in-apply on,
         #  a tensor beyond the memory-side cache; see pw_fold_min_mb)
         defer = (defer_norm and has_bn and unit_training and not fused and not generic_act and residual is None and
-                 out is None and pool_out is None and wpack is None and not self.bn_sync and self.bn_fin_apply and
+                 out is None and pool_out is None and wpack is None and keep is None and not self.bn_sync and self.bn_fin_apply and
                  self.pointwise and not self.deterministic and dt == N.VT_BF16 and
                  x.B * Ho * Wo * Cout * _ESIZE[dt] >= self.pw_fold_min_mb * 1e6)
         if defer:  # y has no place in the arena until something reads it
@@ -925,9 +950,9 @@ class Builder:
         else:
             y = out if out is not None else self.act(x.B, Ho, Wo, Cout, name + ".y")
         u = _ConvUnit(conv, relu, x, y, residual, name, self.tag, wptr, wpack, ldw)
-        u.defer, u.pre_act, u.stem7 = defer, pre_act, _stem7 is not None
+        u.defer, u.pre_act, u.stem7, u.keep = defer, pre_act, _stem7 is not None, keep
         u.stem_fused = stem_fused = (
-            track and u.padded and has_bn and not fused and residual is None and not generic_act and
+            track and u.padded and has_bn and not fused and residual is None and not generic_act and keep is None and
             not x.needs_grad and w.requires_grad and dt == N.VT_BF16 and Cout == 32 and k == 3 and s == 1 and
             conv.dilation == 1 and pad == 1 and x.C == 8 and x.ld == 8 and x.W <= 888 and
             x.B * (x.H + 1) * (x.W + 1) < 0x7fff0000)  # (ring in LDS: halo <= 896 rows)
@@ -1008,7 +1033,7 @@ class Builder:
         fin_fwd = False
         if bn.spec.training:
             stats = self.zeroed_f32(N.stat_floats(y.C), "stats")
-            fin_fwd = self.bn_fin_apply and not self.bn_sync and relu < 2 and pool_out is None
+            fin_fwd = self.bn_fin_apply and not self.bn_sync and (relu < 2 or u.keep is not None) and pool_out is None
             self._conv(u, z, stats=stats)
             if u.defer:
                 y.buf.deferred = _DeferredNorm(self, u, stats)
@@ -1023,6 +1048,13 @@ class Builder:
             u.pool_out, u.pool_am = pool_out, self.alloc(y.B * pool_out.H * pool_out.W * y.C, "argmax")
             self._act_apply(z, bn.cp[0], bn.cp[1], res, y, relu, [pool_out.addr(), self.bp(u.pool_am)],
                             [pool_out.ld, y.B, y.H, y.W])
+        elif u.keep is not None and fin_fwd:
+            ptrs, flts = bn.finalize_operands(stats, y.M)
+            self.emit(N.OP_BN_KEEP_FIN_APPLY, ptrs + [z.addr(), res.addr(), y.addr(), u.keep],
+                      [y.C, z.ld, res.ld, y.ld, y.H * y.W, relu, self.dtype], flts + [y.M])
+        elif u.keep is not None:
+            self.emit(N.OP_BN_KEEP_APPLY, [z.addr(), bn.cp[0], bn.cp[1], res.addr(), y.addr(), u.keep],
+                      [z.ld, res.ld, y.ld, y.H * y.W, y.C, relu, self.dtype], [y.M])
         elif u.pre_act and fin_fwd:
             ptrs, flts = bn.finalize_operands(stats, y.M)
             self.emit(N.OP_BN_ADD_ACT_FIN_APPLY, ptrs + [z.addr(), res.addr(), y.addr()], [y.C, z.ld, res.ld, y.ld, self.dtype],
@@ -1084,6 +1116,8 @@ class Builder:
             return self._stem_bwd(u, dy)
         if u.pre_act:
             dz = self._bn_add_act_bwd(u, dy)
+        elif u.keep is not None:
+            dz = self._bn_keep_bwd(u, dy)
         else:
             dz = self._bn_bwd(u, dy, pool_grad) if u.bn is not None else self._act_bias_bwd(u, dy)
         # Released BEFORE the unit's data gradient, except behind the stem (see __init__): there the data gradient
@@ -1180,6 +1214,24 @@ class Builder:
                       [dy.ld, y.ld, z.ld, dz.ld, dr.ld, acc, y.C, dt], [M])
         if r.needs_grad:
             self.grad_written(r)
+        return dz
+
+    def _bn_keep_bwd(self, u: "_ConvUnit", dy: TRef) -> TRef:
+        """dz of a unit y = keep[b] * act(bn(conv)) + residual: reduce -> finalize -> apply with g = keep[b] * dy * act'(.), the
+        last two in one launch by default.  d(residual) = d(y) was registered by the caller."""
+        bn, z, y, M, dt, act = u.bn, u.z, u.y, u.y.M, self.dtype, u.relu
+        HW = y.H * y.W
+        sums, bcoef, dz = bn.bwd_buffers(y, u.name + ".dz")
+        self.emit(N.OP_BN_KEEP_BWD_REDUCE, [dy.addr(), z.addr(), *bn.cp, self.bp(sums), u.keep],
+                  [dy.ld, z.ld, HW, y.C, act, dt], [M])
+        if self.bn_fin_apply and not self.bn_sync:
+            self.emit(N.OP_BN_KEEP_BWD_FIN_APPLY,
+                      [self.bp(sums), *bn.cp, *bn.grads(), self.bp(bcoef), dy.addr(), z.addr(), dz.addr(), u.keep],
+                      [y.C, int(bn.spec.training), dy.ld, z.ld, dz.ld, HW, act, dt], [M * self.bn_world, 1.0 / self.bn_world, M])
+        else:
+            bn.bwd_finalize(sums, bcoef, M)
+            self.emit(N.OP_BN_KEEP_BWD_APPLY, [dy.addr(), z.addr(), bn.cp[1], self.bp(bcoef), dz.addr(), u.keep],
+                      [dy.ld, z.ld, dz.ld, HW, y.C, act, dt], [M])
         return dz
 
     def _act_bias_bwd(self, u: "_ConvUnit", dy: TRef) -> TRef:
@@ -1420,13 +1472,19 @@ class Builder:
         return y
 
     # -- tiled depthwise units (vt_dwtile.hip) --------------------------------------------------------------------------
-    def depthwise_unit(self, x: TRef, conv, norm, act, out: Optional[TRef] = None, name: str = "dw") -> TRef:
+    def depthwise_unit(self, x: TRef, conv, norm, act, out: Optional[TRef] = None, name: str = "dw",
+                       pool_out: Optional[TRef] = None) -> TRef:
         """y = act(bn(conv(x))) for nn.Conv2d(C, C, k, stride, (k - 1) / 2, groups=C, bias=False) with k in {3, 5} and stride in
         {1, 2} -- the depthwise unit of a MobileNet block -- on the tiled kernels: vt_dwt_fwd (+ batch statistics) -> the ordinary
         BatchNorm finalize (or eval coefficients) -> the normalise pass with any activation code; backward: the ordinary BatchNorm
         backward -> vt_dwt_bwd (d(x) and the filter-gradient shares of the bands in one launch) -> vt_dwt_wgrad_reduce, both on
         the main stream (the shares scratch is one per size).  No float atomics: it is the same program in deterministic mode.
-        ConvNormAct(groups=C) does not come here: it keeps _depthwise_unit.  A geometry the kernels do not take is refused."""
+        ConvNormAct(groups=C) does not come here: it keeps _depthwise_unit.  A geometry the kernels do not take is refused.
+        `pool_out`: a [B, 1, 1, C] row that receives the per-image mean of y from the normalise pass itself
+        (vt_bn_act_avgpool_*: the Squeeze-Excitation pool of an MBConv block without another read of the expanded map); its
+        gradient joins d(y) in f32 INSIDE the unit's BatchNorm backward (the addend of vt_bn_keep_bwd_*: adding it to the stored
+        d(y) with the average pool's backward launch would lose it wherever it is below half an ulp of the rounded d(y), and
+        costs a pass over the largest tensor of the block)."""
         conv, bn_spec = self._specs(conv, norm)
         act, dt, epc = int(act), self.dtype, _EPC[self.dtype]
         Cc, k, s = conv.in_channels, conv.k, conv.stride
@@ -1459,16 +1517,48 @@ class Builder:
         # (the unit follows ITS BatchNorm's flag, as conv_unit does)
         stats = self.zeroed_f32(N.stat_floats(Cc), "stats") if bn_spec.training else None
         self.emit(N.OP_DWT_FWD, [x.addr(), wptr, z.addr(), self.bp(stats) if stats is not None else None], [x.ld, z.ld] + geo)
-        if stats is not None:
-            bn.finalize(stats, M)
+        if pool_out is not None:
+            if (pool_out.B, pool_out.H, pool_out.W, pool_out.C) != (B, 1, 1, Cc) or pool_out.logical_c != Cc:
+                raise ValueError(f"{name}: pool_out is a [B, 1, 1, {Cc}] row per image")
+            sb = int(N.lib().vt_bn_act_avgpool_scratch_bytes(B, Ho * Wo, Cc, dt))
+            if sb < 0:
+                raise NotImplementedError(f"{name}: the fused average pool does not take B={B}, HW={Ho * Wo}, C={Cc}")
+            scratch = self.bp(self.zeroed_f32(sb // 4, "poolsums", bwd=False)) if sb else None
+            pool_ints = [z.ld, y.ld, pool_out.ld, B, Ho * Wo]
+        if pool_out is not None and stats is not None and self.bn_fin_apply and not self.bn_sync:
+            ptrs, flts = bn.finalize_operands(stats, M)
+            self.emit(N.OP_BN_ACT_AVGPOOL_FIN_APPLY, ptrs + [z.addr(), y.addr(), pool_out.addr(), scratch],
+                      [Cc, *pool_ints, act, dt], flts)
         else:
-            bn.eval_coeffs()
-        self._act_apply(z, bn.cp[0], bn.cp[1], None, y, act)
+            if stats is not None:
+                bn.finalize(stats, M)
+            else:
+                bn.eval_coeffs()
+            if pool_out is not None:
+                self.emit(N.OP_BN_ACT_AVGPOOL_APPLY, [z.addr(), bn.cp[0], bn.cp[1], y.addr(), pool_out.addr(), scratch],
+                          [*pool_ints, Cc, act, dt])
+            else:
+                self._act_apply(z, bn.cp[0], bn.cp[1], None, y, act)
         if self.need_grad:
 
             def bwd(dy):
                 sums, bcoef, dz = bn.bwd_buffers(y, name + ".dz")
-                bn.bwd_three_launches(dy, z, act, sums, bcoef, dz)
+                dp = self.grad_read(pool_out) if pool_out is not None else None
+                if dp is None:
+                    bn.bwd_three_launches(dy, z, act, sums, bcoef, dz)
+                else:  # g = (d(y) + d(pooled)[b][c] / HW) * act'(.)
+                    HW = Ho * Wo
+                    self.emit(N.OP_BN_KEEP_BWD_REDUCE, [dy.addr(), z.addr(), *bn.cp, self.bp(sums), None, dp.addr()],
+                              [dy.ld, z.ld, HW, Cc, act, dt, dp.ld], [M])
+                    if self.bn_fin_apply and not self.bn_sync:
+                        self.emit(N.OP_BN_KEEP_BWD_FIN_APPLY,
+                                  [self.bp(sums), *bn.cp, *bn.grads(), self.bp(bcoef), dy.addr(), z.addr(), dz.addr(), None, dp.addr()],
+                                  [Cc, int(bn_spec.training), dy.ld, z.ld, dz.ld, HW, act, dt, dp.ld],
+                                  [M * self.bn_world, 1.0 / self.bn_world, M])
+                    else:
+                        bn.bwd_finalize(sums, bcoef, M)
+                        self.emit(N.OP_BN_KEEP_BWD_APPLY, [dy.addr(), z.addr(), bn.cp[1], self.bp(bcoef), dz.addr(), None, dp.addr()],
+                                  [dy.ld, z.ld, dz.ld, HW, Cc, act, dt, dp.ld], [M])
                 if not (w.requires_grad or x.needs_grad):
                     return
                 # (one scratch per size: the launch that fills it and the one that reads it follow each other on one stream)
@@ -1489,11 +1579,16 @@ class Builder:
             self._node(y, bwd)
         return y
 
-    def se_mlp(self, pooled: TRef, fc1: nn.Conv2d, fc2: nn.Conv2d, name: str = "se") -> TRef:
+    def se_mlp(self, pooled: TRef, fc1: nn.Conv2d, fc2: nn.Conv2d, name: str = "se", act: int = 1) -> TRef:
         """The Squeeze-Excitation MLP on a pooled [B, 1, 1, C] row: fc2(relu(fc1(pooled))) with 1x1 biased convolutions of ANY
         squeeze width (RegNetY: round(0.25 * width_in) = 12, 26, 110 ..., no whole 16-byte chunks, which the 1x1 units need) in
         one launch (vt_se_mlp_fwd); the result is the operand `s` of se_gate.  Backward: vt_se_mlp_bwd (d(pooled) and the four
-        parameter gradients, one owner per element).  The weights are read from the f32 masters."""
+        parameter gradients, one owner per element).  The weights are read from the f32 masters.
+        `act`: the squeeze activation, 1 ReLU or 3 SiLU (EfficientNet; `hidden` then also keeps the pre-activations, which
+        silu' needs).  The code travels in an op field whose zero value means ReLU: act=1 emits the ops it always emitted."""
+        act = int(act)
+        if act not in (1, 3):
+            raise NotImplementedError(f"{name}: squeeze activation code {act} (1 ReLU, 3 SiLU)")
         Cc, S = fc1.in_channels, fc1.out_channels
         if ((pooled.H, pooled.W, pooled.C) != (1, 1, Cc) or pooled.logical_c != Cc or fc2.in_channels != S or
                 fc2.out_channels != Cc or fc1.kernel_size != (1, 1) or fc2.kernel_size != (1, 1) or fc1.bias is None or
@@ -1502,9 +1597,10 @@ class Builder:
         self.tag += 1
         B, dt = pooled.B, self.dtype
         logits = self.act(B, 1, 1, Cc, name + ".logits")
-        hidden = self.f32(B * S, name + ".hidden")
+        hidden = self.f32(B * S * (2 if act == 3 else 1), name + ".hidden")
+        code = [act] if act != 1 else []
         wts = [self.pref(fc1.weight), self.pref(fc1.bias), self.pref(fc2.weight), self.pref(fc2.bias)]
-        self.emit(N.OP_SE_MLP_FWD, [pooled.addr(), *wts, self.bp(hidden), logits.addr()], [pooled.ld, logits.ld, B, Cc, S, dt])
+        self.emit(N.OP_SE_MLP_FWD, [pooled.addr(), *wts, self.bp(hidden), logits.addr()], [pooled.ld, logits.ld, B, Cc, S, dt] + code)
         if self.need_grad:
 
             def bwd(dl):
@@ -1516,7 +1612,7 @@ class Builder:
                 self.emit(N.OP_SE_MLP_BWD,
                           [dl.addr(), pooled.addr(), wts[0], wts[2], self.bp(hidden), self.bp(dhid), _addr(gp),
                            self.pgrad(fc1.weight), self.pgrad(fc1.bias), self.pgrad(fc2.weight), self.pgrad(fc2.bias)],
-                          [dl.ld, pooled.ld, _ld(gp), B, Cc, S, dt])
+                          [dl.ld, pooled.ld, _ld(gp), B, Cc, S, dt] + code)
 
             self._node(logits, bwd)
         return logits

@@ -70,9 +70,23 @@ def resolve_dtype(x: torch.Tensor, override: Optional[torch.dtype]) -> int:
 def mode_signature(module: nn.Module, store: "E.ParamStore") -> tuple:
     """what a compiled program bakes in besides shapes: the train/eval flag of every BatchNorm (a
     frozen `bn.eval()` inside a training model must use its running statistics, as nn.BatchNorm2d
-    does) and which parameters receive gradients."""
+    does), which parameters receive gradients, and the stochastic-depth rates of a keep table (`_vt_keep_rates` of an
+    EfficientNetExtractor: empty in eval mode or at rate zero, where the program has no table)."""
     bn = tuple(m.training for m in module.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm))
-    return bn, tuple(p.requires_grad for p in store.params)
+    keep = getattr(module, "_vt_keep_rates", None)
+    return bn, tuple(p.requires_grad for p in store.params), tuple(keep()) if keep is not None else ()
+
+
+def draw_keep_factors(rates, B: int, device, override: Optional[torch.Tensor] = None, generator=None) -> torch.Tensor:
+    """the keep table float[n_sites][B] of one forward: `override` where the user set one (its shape is checked), else
+    bernoulli(1 - p_site) / (1 - p_site) per site and image, drawn on `device`"""
+    n = len(rates)
+    if override is not None:
+        if tuple(override.shape) != (n, B):
+            raise ValueError(f"keep factors of shape {tuple(override.shape)}: this program has {n} sites and {B} images")
+        return override.to(device=device, dtype=torch.float32)
+    survive = (1.0 - torch.tensor(rates, dtype=torch.float32, device=device)).unsqueeze(1).expand(n, B)
+    return torch.bernoulli(survive, generator=generator) / survive
 
 
 class Program:
@@ -277,9 +291,22 @@ class BackboneRunner:
             st.bases = prog.bases(arena.data_ptr(), PARAMS=s.pflat.data_ptr(), STATE=s.sflat.data_ptr(),
                                   MIRROR=s.mirror.data_ptr(), COUNTERS=s.nflat.data_ptr(),
                                   INPUT=x32.data_ptr())
+            self._fill_keep_table(prog, arena)
             N.run_ops(prog.fwd_ops, prog.n_fwd, st.bases, current_stream_handle())
         outs = [E.tref_to_tensor(arena, t) for t in prog.outs]
         return st, outs
+
+    def _fill_keep_table(self, prog: Program, arena: torch.Tensor) -> None:
+        """stochastic depth: the program's keep table float[n_sites][B] is written here, outside the launch list -- the values
+        the user set (module.set_keep_factors) or bernoulli(1 - p) / (1 - p) per site and image, drawn on the input's device.
+        `last_keep_table` is a copy read back from the arena (tests, reproducing a run)."""
+        b = prog.builder
+        if b.keep_buf is None:
+            return
+        n, B = len(b.keep_rates), b.keep_B
+        view = arena[b.keep_buf.offset : b.keep_buf.offset + n * B * 4].view(torch.float32).view(n, B)
+        view.copy_(draw_keep_factors(b.keep_rates, B, arena.device, getattr(self.module, "_keep_override", None)))
+        self.last_keep_table = view.clone()
 
     def _run_backward(self, st: _RunState, gouts, x_requires_grad: bool):
         prog, arena = st.prog, st.arena

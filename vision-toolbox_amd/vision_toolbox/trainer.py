@@ -40,7 +40,7 @@ from torch import nn
 from . import _native as N
 from . import engine as E
 from .distributed import GradBucketer, ShardedExchange, plan_buckets
-from .program import Program, current_stream_handle
+from .program import Program, current_stream_handle, draw_keep_factors
 
 _NORMS = (nn.modules.batchnorm._BatchNorm, nn.modules.instancenorm._InstanceNorm, nn.LayerNorm, nn.GroupNorm)
 GROUP_NORM, GROUP_BIAS, GROUP_OTHER = 0, 1, 2  # flat-buffer order: small, late-produced groups first
@@ -154,6 +154,7 @@ class TrainStep:
         betas: "tuple[float, float]" = (0.9, 0.999),
         eps: float = 1e-8,
         include_pool: bool = True,
+        drop_seed: int = 0,
     ):
         N.lib()
         if optimizer not in OPTIMIZERS:
@@ -270,6 +271,13 @@ class TrainStep:
                 raise NotImplementedError(f"exchange='sharded' with {backbone.model_name}: its depthwise filters and "
                                           "Squeeze-Excitation weights are read in f32 outside the head bucket (use "
                                           "exchange='allreduce')")
+            from .backbones.efficientnet import EfficientNetExtractor
+
+            # (... and for those of an EfficientNet)
+            if isinstance(backbone, EfficientNetExtractor):
+                raise NotImplementedError(f"exchange='sharded' with {backbone.model_name}: its depthwise filters and "
+                                          "Squeeze-Excitation weights are read in f32 outside the head bucket (use "
+                                          "exchange='allreduce')")
         # who issues the collectives: "torch" = torch.distributed calls between segments of the launch lists (any
         # backend: gloo in the CPU tests); "rccl" = the library's own RCCL communicator (vt_comm_init), the collectives are
         # OPS of the lists (VT_OP_STAT_SYNC in front of every BatchNorm finalize, FORK + VT_OP_ALLREDUCE on the
@@ -325,6 +333,14 @@ class TrainStep:
         b.build_backward()
         self.prog = Program(b, [logits], [])
         self.n_units = b.n_units
+        # stochastic depth (an EfficientNet's residual blocks): the keep table float[n_sites][B] of the training program lives
+        # in the arena and is written before every step, outside the launch lists -- drawn from a generator this object owns
+        # (seeded with drop_seed, plus the rank under data parallelism: every rank drops its own images), or the values of
+        # set_keep_factors.  validate() compiles an eval-mode program, which has no table.
+        self._keep_buf, self._keep_rates = b.keep_buf, b.keep_rates
+        self._keep_override: Optional[torch.Tensor] = None
+        self.drop_seed = int(drop_seed) + (torch.distributed.get_rank(process_group) if self.dp else 0)
+        self._keep_gen = None
         # sync points: the statistics a finalize kernel reads must be all-reduced right before it
         self._fwd_sync = self._sync_points(self.prog.fwd_ops, self.prog.n_fwd, N.OP_BN_FINALIZE) if self.sync_bn else []
         self._bwd_sync = self._sync_points(self.prog.bwd_ops, self.prog.n_bwd, N.OP_BN_BWD_FINALIZE) if self.sync_bn else []
@@ -634,6 +650,33 @@ class TrainStep:
         if self.dtype == N.VT_BF16:
             self.store.mirror.copy_(self.store.pflat)
 
+    def set_keep_factors(self, t: Optional[torch.Tensor]) -> None:
+        """the stochastic-depth keep factors of the NEXT step(s): a float[n_sites][B] tensor (one row per residual block in
+        emission order, one factor per image) used instead of drawing, or None to draw again"""
+        if t is not None:
+            if not self._keep_rates:
+                raise RuntimeError("this TrainStep's program has no keep table (no stochastic depth in the backbone)")
+            if tuple(t.shape) != (len(self._keep_rates), self.B):
+                raise ValueError(f"keep factors of shape {tuple(t.shape)}: this program has {len(self._keep_rates)} sites and "
+                                 f"{self.B} images")
+            t = t.detach().to(device=self.device, dtype=torch.float32).clone()
+        self._keep_override = t
+
+    def keep_factors(self) -> Optional[torch.Tensor]:
+        """the keep table of the last step, read back from the arena (None: the program has none)"""
+        if self._keep_buf is None:
+            return None
+        n, off = len(self._keep_rates), self._keep_buf.offset
+        return self.arena[off : off + n * self.B * 4].view(torch.float32).view(n, self.B).clone()
+
+    def _fill_keep_table(self) -> None:
+        n, off = len(self._keep_rates), self._keep_buf.offset
+        if self._keep_gen is None:
+            self._keep_gen = torch.Generator(device=self.device)
+            self._keep_gen.manual_seed(self.drop_seed)
+        view = self.arena[off : off + n * self.B * 4].view(torch.float32).view(n, self.B)
+        view.copy_(draw_keep_factors(self._keep_rates, self.B, self.device, self._keep_override, self._keep_gen))
+
     def set_lr(self, lr: float) -> None:
         self.lr = lr
         self.lr_dev[:4] = lr
@@ -687,6 +730,8 @@ class TrainStep:
                 self.labels.copy_(labels, non_blocking=True)
             s = current_stream_handle()
             p = self.prog
+            if self._keep_buf is not None:
+                self._fill_keep_table()  # (once per step, on the current stream in front of the lists or the graph)
             if self.use_graphs and not self.sync_bn and self.collectives != "rccl":
                 if self._graphs is None:
                     self._build_graphs()
