@@ -858,6 +858,30 @@ int vt_resample2x_bwd(const void* dy, int32_t lddy, void* dsrc, int32_t lds, int
                       int32_t Wd, int32_t C, int32_t mode, int32_t accumulate, int32_t dtype,
                       void* stream);
 
+/* ---- BiFPN's weighted fusion node (necks.py:197-215) ---------------------- */
+/* out = (sum_i relu(w)_i R_i(x_i)) / (sum_i relu(w)_i + eps) over n in {2, 3} inputs (x2 is ignored for n = 2).  out is
+ * [B][H][W][C]; code_i says how input i relates to that grid: 0 same size, 1 nearest x2 (x_i is [B][H/2][W/2][C], read at
+ * (i/2, j/2); H and W even), 2 nearest x0.5 (x_i is [B][2H][2W][C], read at (2i, 2j)) -- the index maps of
+ * vt_resample2x_add_fwd modes 0 and 1.  `weights` is the RAW parameter, a device float[n]: the kernels apply the ReLU and
+ * form 1 / (sum + eps) themselves.  f32 accumulation, one rounding at the store; out must not alias an input.  C is a
+ * whole number of 16-byte chunks.
+ * vt_wfuse_bwd, one launch per node, given g = d(out):
+ *   dx_i (=|+= with acc_i) relu(w)_i / (sum + eps) * R_i^T(g): code 1 sums the 2x2 block of g; code 2 writes the
+ *   even/even pixel and zeroes the other three (with acc_i nothing outside the even/even pixels is touched); a NULL dx_i
+ *   skips that input;
+ *   sums (VT_CHANNEL_SUMS_BYTES(1, n) bytes, zeroed by the caller): entry i += sum g * (R_i(x_i) - out), out recomputed in
+ *   f32 from the inputs; fixed point, integer atomics, so every run is bit-identical.
+ * vt_wfuse_finalize: dweights[i] += [w_i > 0] * sums_i / (sum + eps) -- BOTH scalar factors are applied here, in double;
+ *   an entry whose weight is not positive is left untouched (torch: relu'(0) = 0). */
+int vt_wfuse_fwd(int32_t n, const void* x0, int32_t ld0, int32_t code0, const void* x1, int32_t ld1, int32_t code1,
+                 const void* x2, int32_t ld2, int32_t code2, const float* weights, float eps, void* out, int32_t ldo, int32_t B,
+                 int32_t H, int32_t W, int32_t C, int32_t dtype, void* stream);
+int vt_wfuse_bwd(int32_t n, const void* g, int32_t ldg, const void* x0, int32_t ld0, int32_t code0, const void* x1, int32_t ld1,
+                 int32_t code1, const void* x2, int32_t ld2, int32_t code2, const float* weights, float eps, void* dx0,
+                 int32_t lddx0, int32_t acc0, void* dx1, int32_t lddx1, int32_t acc1, void* dx2, int32_t lddx2, int32_t acc2,
+                 float* sums, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype, void* stream);
+int vt_wfuse_finalize(const float* sums, const float* weights, float eps, int32_t n, float* dweights, void* stream);
+
 /* ---- ESEBlock gate (vovnet.py:20-28) ------------------------------------ */
 /* y = x * hardsigmoid(s[b][c]) [+ residual]; s is [B][C] (the biased 1x1 conv
  * of the pooled map, computed with vt_conv_igemm). */
@@ -1056,6 +1080,9 @@ enum vt_op_kind {
     VT_OP_BN_KEEP_BWD_FIN_APPLY,    /* vt_bn_keep_bwd_finalize_apply */
     VT_OP_BN_ACT_AVGPOOL_APPLY,     /* vt_bn_act_avgpool_apply */
     VT_OP_BN_ACT_AVGPOOL_FIN_APPLY, /* vt_bn_act_avgpool_finalize_apply */
+    VT_OP_WFUSE_FWD,                /* vt_wfuse_fwd */
+    VT_OP_WFUSE_BWD,                /* vt_wfuse_bwd */
+    VT_OP_WFUSE_FIN,                /* vt_wfuse_finalize */
     VT_OP_KIND_END
 };
 

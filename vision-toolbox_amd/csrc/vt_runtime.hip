@@ -231,6 +231,16 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
                                          I[3], I[4], st);
         case VT_OP_CHANNEL_SUMS:  // ptr: sums dst0 dst1 dst2 | i: rows C
             return vt_channel_sums_to_f32((const float*)P[0], I[0], I[1], (float*)P[1], (float*)P[2], (float*)P[3], st);
+        case VT_OP_WFUSE_FWD:  // ptr: x0 x1 x2 weights out | i: n ld0 ld1 ld2 code0 code1 code2 ldo B H W C dtype | f: eps
+            return vt_wfuse_fwd(I[0], P[0], I[1], I[4], P[1], I[2], I[5], P[2], I[3], I[6], (const float*)P[3], (float)F[0], P[4],
+                                I[7], I[8], I[9], I[10], I[11], I[12], st);
+        case VT_OP_WFUSE_BWD:  // ptr: g x0 x1 x2 weights dx0 dx1 dx2 sums | i: n ldg ld0 ld1 ld2 code0 code1 code2 lddx0 lddx1
+                               //      lddx2 acc0 acc1 acc2 B H W C dtype | f: eps
+            return vt_wfuse_bwd(I[0], P[0], I[1], P[1], I[2], I[5], P[2], I[3], I[6], P[3], I[4], I[7], (const float*)P[4],
+                                (float)F[0], P[5], I[8], I[11], P[6], I[9], I[12], P[7], I[10], I[13], (float*)P[8], I[14], I[15],
+                                I[16], I[17], I[18], st);
+        case VT_OP_WFUSE_FIN:  // ptr: sums weights dweights | i: n | f: eps
+            return vt_wfuse_finalize((const float*)P[0], (const float*)P[1], (float)F[0], I[0], (float*)P[2], st);
         case VT_OP_TOKEN_MIX:  // ptr: x w bias residual z a | i: ldx ldw transw ldr ldz lda act B K M C dtype
             return vt_token_mix_fwd(P[0], I[0], P[1], I[1], I[2], (const float*)P[2], P[3], I[3], P[4], I[4], P[5], I[5], I[6], I[7],
                                     I[8], I[9], I[10], I[11], st);

@@ -165,7 +165,10 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_BN_KEEP_BWD_FIN_APPLY,
     OP_BN_ACT_AVGPOOL_APPLY,
     OP_BN_ACT_AVGPOOL_FIN_APPLY,
-) = range(1, 108)
+    OP_WFUSE_FWD,
+    OP_WFUSE_BWD,
+    OP_WFUSE_FIN,
+) = range(1, 111)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -257,6 +260,9 @@ OP_NAMES = {
     OP_BN_KEEP_BWD_FIN_APPLY: "bn_keep_bwd_fin_apply",
     OP_BN_ACT_AVGPOOL_APPLY: "bn_act_avgpool_apply",
     OP_BN_ACT_AVGPOOL_FIN_APPLY: "bn_act_avgpool_fin_apply",
+    OP_WFUSE_FWD: "wfuse_fwd",
+    OP_WFUSE_BWD: "wfuse_bwd",
+    OP_WFUSE_FIN: "wfuse_fin",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -457,7 +463,11 @@ SYMBOLS = {
     "vt_dwt_wgrad_reduce": (_i32, [_vp, _i64, _vp] + [_i32] * 7 + [_vp]),
     "vt_dwt_shares_bytes": (_i64, [_i32] * 7),
     "vt_dwt_tile": (_i32, [_i32] * 6 + [C.POINTER(_i32), C.POINTER(_i32)]),
-    "vt_pack_dgrad_filter_batch": (_i32, [_vp, _i32, _vp]),
+    "vt_wfuse_fwd": (_i32, [_i32, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _f32, _vp, _i32] + [_i32] * 5 + [_vp]),
+    "vt_wfuse_bwd": (_i32, [_i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _f32, _vp, _i32, _i32, _vp, _i32,
+                            _i32, _vp, _i32, _i32, _vp] + [_i32] * 5 + [_vp]),
+    "vt_wfuse_finalize": (_i32, [_vp, _vp, _f32, _i32, _vp, _vp]),
+    "vt_pack_dgrad_filter_batch":(_i32, [_vp, _i32, _vp]),
     "vt_bn_eval_coeffs_batch": (_i32, [_vp, _i32, _vp]),
     "vt_pack_dgrad_filter": (_i32, [_vp, _i32, _i32, _vp, _i32, C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp]),
     "vt_bn_finalize": (_i32, [_vp, _i32, _f64, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

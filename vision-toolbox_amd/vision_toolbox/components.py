@@ -1,4 +1,5 @@
-"""ConvNormAct -- the fused Conv -> BatchNorm -> ReLU unit of the hot path.
+"""ConvNormAct -- the fused Conv -> BatchNorm -> ReLU unit of the hot path -- and SeparableConv2d, the depthwise + pointwise
+pair of such units that BiFPN builds on.
 
 Same constructor signature, child names (`conv`, `norm`, `act`) and therefore the same
 state_dict keys as the reference unit (vision_toolbox/components.py:13-46), and the
@@ -17,12 +18,13 @@ from __future__ import annotations
 
 import math
 import weakref
-from typing import Optional
+from functools import partial
+from typing import Callable, Optional
 
 import torch
 from torch import Tensor, nn
 
-__all__ = ["ConvNormAct", "HipModule", "Permute", "StochasticDepth", "LayerScale"]
+__all__ = ["ConvNormAct", "SeparableConv2d", "HipModule", "Permute", "StochasticDepth", "LayerScale"]
 
 _RUNNERS: "weakref.WeakKeyDictionary[nn.Module, object]" = weakref.WeakKeyDictionary()
 
@@ -141,6 +143,66 @@ class ConvNormAct(nn.Sequential, HipModule):
 
     def _eager_maps(self, x: Tensor) -> "list[Tensor]":
         return [self.act(self.norm(self.conv(x)))]
+
+    def forward(self, x: Tensor) -> Tensor:
+        return HipModule.forward(self, x)
+
+
+def _sep_act_code(a: nn.Module, name: str) -> int:
+    """activation code of the kernels for what `act_fn()` returned (include/vt_amd.h)"""
+    for cls, code in ((nn.Identity, 0), (nn.ReLU6, 5), (nn.ReLU, 1), (nn.SiLU, 3), (nn.Hardswish, 6)):
+        if isinstance(a, cls):
+            return code
+    raise NotImplementedError(f"{name}: activation {a!r} -- the MI355X path of SeparableConv2d implements Identity, ReLU, SiLU, "
+                              "ReLU6 and Hardswish")
+
+
+class _ConvBNAct(nn.Sequential):
+    """conv -> norm -> act under the child names of the reference's ConvNormAct (state_dict keys conv.weight, norm.*)"""
+
+    def __init__(self, conv: nn.Conv2d, norm: nn.BatchNorm2d, act: nn.Module):
+        super().__init__()
+        self.add_module("conv", conv)
+        self.add_module("norm", norm)
+        self.add_module("act", act)
+
+
+class SeparableConv2d(nn.Sequential, HipModule):
+    """Depthwise k x k Conv-BN-act (`dw`) then pointwise 1x1 Conv-BN-act (`pw`): the block BiFPN builds on.
+
+    The reference's class (components.py:49-72) cannot be constructed -- it hands `padding=` and `act_fn=` to ConvNormAct,
+    which takes neither -- so this implements what its ten lines evidently mean: both convolutions without bias, each
+    followed by BatchNorm2d and `act_fn()`, torch's default Conv2d initialisation (ConvNormAct re-initialises only for
+    relu / leaky_relu).  On the GPU `dw` runs on the tiled depthwise kernels (Builder.depthwise_unit: kernel_size 3 or 5,
+    stride 1 or 2, padding (k - 1) / 2, dilation 1; other geometries are refused with its message) and `pw` is a conv_unit."""
+
+    def __init__(
+        self,
+        in_channels: int,
+        out_channels: int,
+        kernel_size: int = 3,
+        stride: int = 1,
+        padding: int = 1,
+        dilation: int = 1,
+        act_fn: Callable[[], nn.Module] = partial(nn.ReLU6, inplace=True),
+    ):
+        super().__init__()
+        self.add_module("dw", _ConvBNAct(
+            nn.Conv2d(in_channels, in_channels, kernel_size, stride=stride, padding=padding, dilation=dilation,
+                      groups=in_channels, bias=False),
+            nn.BatchNorm2d(in_channels), act_fn()))
+        self.add_module("pw", _ConvBNAct(nn.Conv2d(in_channels, out_channels, 1, bias=False), nn.BatchNorm2d(out_channels),
+                                         act_fn()))
+
+    def _vt_emit(self, b, x, out=None, name: str = "sep"):
+        h = b.depthwise_unit(x, self.dw.conv, self.dw.norm, _sep_act_code(self.dw.act, name + ".dw"), name=name + ".dw")
+        return b.conv_unit(h, self.pw.conv, self.pw.norm, _sep_act_code(self.pw.act, name + ".pw"), out=out, name=name + ".pw")
+
+    def _vt_emit_maps(self, b, x):
+        return [self._vt_emit(b, x)]
+
+    def _eager_maps(self, x: Tensor) -> "list[Tensor]":
+        return [self.pw(self.dw(x))]
 
     def forward(self, x: Tensor) -> Tensor:
         return HipModule.forward(self, x)

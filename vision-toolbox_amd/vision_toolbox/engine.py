@@ -1946,6 +1946,64 @@ class Builder:
             self._node(y, bwd)
         return y
 
+    def weighted_fuse(self, xs, codes, weights: nn.Parameter, eps: float, name: str = "wfuse") -> TRef:
+        """BiFPN's fusion node (necks.py:210-215): out = (sum_i relu(w)_i R_i(x_i)) / (sum_i relu(w)_i + eps) over 2 or 3 maps
+        in ONE launch (vt_wfuse_fwd); codes[i] relates xs[i] to the output grid: 0 same size, 1 nearest x2, 2 nearest x0.5.
+        `weights` is the raw float[n] parameter, read on the device.  Backward: one launch (vt_wfuse_bwd) writes or
+        accumulates every input's gradient -- a map of a BiFPN layer has up to three consumers, so each input gets its own
+        accumulate flag -- and the fixed-point sums behind d(weights), which vt_wfuse_finalize adds to the parameter gradient."""
+        xs, n = list(xs), len(xs)
+        if n not in (2, 3) or len(codes) != n:
+            raise NotImplementedError(f"{name}: weighted_fuse takes 2 or 3 inputs with one resample code each, got {n}")
+        codes = [int(c) for c in codes]
+        if any(c not in (0, 1, 2) for c in codes):
+            raise NotImplementedError(f"{name}: resample codes {codes} (0 same size, 1 nearest x2, 2 nearest x0.5)")
+        if weights.numel() != n:
+            raise ValueError(f"{name}: {n} inputs but {weights.numel()} fusion weights")
+        dt, epc = self.dtype, _EPC[self.dtype]
+        B, Cc = xs[0].B, xs[0].C
+        if Cc % epc:
+            raise NotImplementedError(f"{name}: {Cc} channels must be a multiple of {epc} for dtype {dt} (whole 16-byte chunks)")
+        for x, c in zip(xs, codes):
+            if c == 2 and (x.H % 2 or x.W % 2):
+                raise NotImplementedError(f"{name}: x0.5 resampling of an odd-sized map")
+        sizes = [(x.H, x.W) if c == 0 else ((2 * x.H, 2 * x.W) if c == 1 else (x.H // 2, x.W // 2)) for x, c in zip(xs, codes)]
+        H, W = sizes[0]
+        if any(s != (H, W) for s in sizes) or any((x.B, x.C) != (B, Cc) for x in xs):
+            raise ValueError(f"{name}: fused maps {[(x.B, x.C, x.H, x.W) for x in xs]} with codes {codes} do not meet on one grid "
+                             "(levels must be an exact factor 2 apart)")
+        if len({(id(x.buf), x.coff) for x in xs}) != n:
+            raise ValueError(f"{name}: the same map is fused twice")
+        self.tag += 1
+        y = self.act(B, H, W, Cc, name + ".y")
+        wp = self.pref(weights)
+        x3, c3 = xs + [None] * (3 - n), codes + [0] * (3 - n)
+        self.emit(N.OP_WFUSE_FWD, [_addr(x) for x in x3] + [wp, y.addr()],
+                  [n, *[_ld(x) for x in x3], *c3, y.ld, B, H, W, Cc, dt], [eps])
+        if self.need_grad and (weights.requires_grad or any(x.needs_grad for x in xs)):
+
+            def bwd(dy):
+                sums = self.zeroed_f32(N.channel_sums_floats(1, n), "wfsums")
+                gxs, accs, flush = [], [], []
+                for x in xs:
+                    gx, acc = self.grad_accum_target(x) if x.needs_grad else (None, 0)
+                    gxs.append(gx)
+                    accs.append(acc)
+                    # (grad_target keeps ONE deferred flush; this launch has up to three destinations)
+                    if self._deferred_flush is not None:
+                        flush.append(self._deferred_flush)
+                        self._deferred_flush = None
+                g3, a3 = gxs + [None] * (3 - n), accs + [0] * (3 - n)
+                self.emit(N.OP_WFUSE_BWD, [dy.addr()] + [_addr(x) for x in x3] + [wp] + [_addr(g) for g in g3] + [self.bp(sums)],
+                          [n, dy.ld, *[_ld(x) for x in x3], *c3, *[_ld(g) for g in g3], *a3, B, H, W, Cc, dt], [eps])
+                for t in flush:
+                    self._flush_pending(t)
+                if self.pgrad(weights) is not None:
+                    self.emit(N.OP_WFUSE_FIN, [self.bp(sums), wp, self.pgrad(weights)], [n], [eps])
+
+            self._node(y, bwd)
+        return y
+
     def maxpool3x3s2(self, x: TRef, out: Optional[TRef] = None, name="maxpool") -> TRef:
         self.tag += 1
         Ho, Wo = (x.H + 2 - 3) // 2 + 1, (x.W + 2 - 3) // 2 + 1

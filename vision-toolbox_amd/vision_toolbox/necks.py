@@ -1,30 +1,37 @@
-"""FPN / PAN necks on the backbone kernels.
+"""FPN / PAN / BiFPN necks on the backbone kernels.
 
-Same constructors, child names (`lateral_convs`, `output_convs`, `top_down`, `bottom_up`) and
-therefore the same state_dict keys as the reference (vision_toolbox/necks.py:45-120); `forward`
+Same constructors, child names (`lateral_convs`, `output_convs`, `top_down`, `bottom_up`; BiFPN: `laterals`,
+`layers.{l}.td_fuses` / `out_fuses` / `last_out_fuse`, each with `.weights` and `.conv`) and
+therefore the same state_dict keys as the reference (vision_toolbox/necks.py:45-215); `forward`
 takes the list a backbone's `get_feature_maps()` returns (bottom = largest map first) and returns a
 list of the same length.  Execution: one compiled launch list per (shapes, dtype, mode) --
 biased 1x1 lateral convs and 3x3 ConvNormAct output convs on the implicit-GEMM kernels, and the
 `nn.Upsample(nearest, x2 | x0.5)` + `sum` pair as ONE resampling kernel (vt_resample2x_add_fwd);
 the whole neck is one autograd.Function, so it composes with the backbone's.
 
-Only what the reference's defaults use is implemented on the GPU: `fuse_fn="sum"`, nearest
-interpolation, `ConvNormAct` blocks.  Other settings construct (state_dict parity) and raise
-NotImplementedError when run; BiFPN (separable convs) is outside the hot path.
+FPN / PAN run `fuse_fn` "sum" / "concat", nearest / bilinear interpolation and `ConvNormAct` blocks on the GPU.  Other
+settings construct (state_dict parity) and raise NotImplementedError when run.
+
+BiFPN: biased 1x1 lateral convs, then per layer 2 (levels - 1) fusion nodes.  A node is ONE launch
+(Builder.weighted_fuse -> vt_wfuse_fwd: the ReLU of the learned weights, the normalisation by their sum and the nearest
+x2 / x0.5 resampling of its 2 or 3 inputs happen inside it, no resampled or scaled map is stored) followed by the node's
+block: `SeparableConv2d` (the default; tiled depthwise unit + 1x1 unit) or `ConvNormAct`.  `interpolation_mode="bilinear"`
+materialises the resampled map with the resampling kernel first and fuses it at equal size.
 """
 from __future__ import annotations
 
 from typing import Callable, Optional, Sequence
 
 import torch
+import torch.nn.functional as F
 from torch import Tensor, nn
 
 from . import _native as N
 from . import engine as E
-from .components import ConvNormAct
+from .components import ConvNormAct, SeparableConv2d
 from .program import Program, current_stream_handle, mode_signature, tracing_paused
 
-__all__ = ["FPN", "PAN"]
+__all__ = ["FPN", "PAN", "BiFPN"]
 
 _FUSE = ("concat", "sum", "avg", "max")
 
@@ -250,3 +257,144 @@ class PAN(_NeckBase):
 
     def _eager_list(self, xs):
         return self.bottom_up._eager_list(self.top_down._eager_list(xs))
+
+
+# https://arxiv.org/pdf/1911.09070.pdf
+_BIFPN_MODES = ("nearest", "bilinear")
+
+
+def _bifpn_fuse(b, node: "WeightedFeatureFusion", xs, codes, interpolation_mode: str, name: str):
+    """one fusion node on the launch list: the weighted fusion (one launch), then the node's block"""
+    if interpolation_mode not in _BIFPN_MODES:
+        raise NotImplementedError(f"{name}: interpolation_mode={interpolation_mode!r} -- the MI355X BiFPN implements "
+                                  "'nearest' and 'bilinear'")
+    if not isinstance(node.conv, (ConvNormAct, SeparableConv2d)):
+        raise NotImplementedError(f"{name}.conv: block {type(node.conv).__name__} -- the MI355X BiFPN runs ConvNormAct and "
+                                  "SeparableConv2d blocks")
+    ins, cs = [], []
+    for k, (x, c) in enumerate(zip(xs, codes)):
+        if c and interpolation_mode == "bilinear":  # the fusion kernel resamples nearest only: materialise, fuse at equal size
+            x, c = b.resample_add(x, None, 2 if c == 1 else 3, name=f"{name}.resample{k}"), 0
+        ins.append(x)
+        cs.append(c)
+    fused = b.weighted_fuse(ins, cs, node.weights, node.eps, name=name)
+    return node.conv._vt_emit(b, fused, name=name + ".conv")
+
+
+class WeightedFeatureFusion(_NeckBase):
+    def __init__(
+        self,
+        num_channels: int,
+        num_inputs: int = 2,
+        block: Callable[[int, int], nn.Module] = SeparableConv2d,
+        eps: float = 1e-4,
+    ):
+        super().__init__()
+        self.weights = nn.Parameter(torch.ones(num_inputs, dtype=torch.float))
+        self.conv = block(num_channels, num_channels)
+        self.eps = eps
+
+    def forward(self, x: "list[Tensor]") -> Tensor:  # (equal-sized maps, as in the reference: the caller resamples)
+        return super().forward(x)[0]
+
+    def _vt_emit_list(self, b, xs, name: str = "fuse"):
+        return [_bifpn_fuse(b, self, xs, [0] * len(xs), "nearest", name)]
+
+    def _eager(self, xs) -> Tensor:
+        weights = F.relu(self.weights)
+        out = 0
+        for i in range(weights.shape[0]):
+            out = out + xs[i] * weights[i]
+        return self.conv(out / (weights.sum() + self.eps))
+
+    def _eager_list(self, xs):
+        return [self._eager(xs)]
+
+
+class BiFPNLayer(_NeckBase):
+    def __init__(
+        self,
+        num_levels: int,
+        num_channels: int,
+        block: Callable[[int, int], nn.Module] = SeparableConv2d,
+        interpolation_mode="nearest",
+        eps: float = 1e-4,
+    ):
+        super().__init__()
+        self.num_levels = num_levels
+        self.interpolation_mode = interpolation_mode
+        self.td_fuses = nn.ModuleList(
+            [WeightedFeatureFusion(num_channels, block=block, eps=eps) for _ in range(num_levels - 1)]
+        )
+        self.out_fuses = nn.ModuleList(
+            [WeightedFeatureFusion(num_channels, num_inputs=3, block=block, eps=eps) for _ in range(num_levels - 2)]
+        )
+        self.last_out_fuse = WeightedFeatureFusion(num_channels, block=block, eps=eps)
+        self.upsample = nn.Upsample(scale_factor=2.0, mode=interpolation_mode)
+        self.downsample = nn.Upsample(scale_factor=0.5, mode=interpolation_mode)
+
+    def _check(self, xs):
+        if self.num_levels < 2 or len(xs) != self.num_levels:
+            raise ValueError(f"BiFPNLayer: {len(xs)} feature maps for {self.num_levels} levels (at least 2)")
+
+    def _vt_emit_list(self, b, xs, name: str = "bifpn_layer"):
+        self._check(xs)
+        n, mode = self.num_levels, self.interpolation_mode
+        # top-down: P6td = conv(fuse(P6in, up(P7td))) (necks.py:182-185)
+        tds = list(xs)
+        for i, node in enumerate(self.td_fuses):
+            d = n - 2 - i
+            tds[d] = _bifpn_fuse(b, node, [xs[d], tds[d + 1]], [0, 1], mode, f"{name}.td_fuses.{i}")
+        # bottom-up: P4out = conv(fuse(P4in, P4td, down(P3td))) (necks.py:187-190); the top level has two inputs (:193)
+        outs = list(tds)
+        for i, node in enumerate(self.out_fuses):
+            outs[i + 1] = _bifpn_fuse(b, node, [xs[i + 1], tds[i + 1], tds[i]], [0, 0, 2], mode, f"{name}.out_fuses.{i}")
+        outs[-1] = _bifpn_fuse(b, self.last_out_fuse, [xs[-1], tds[-2]], [0, 2], mode, f"{name}.last_out_fuse")
+        return outs
+
+    def _eager_list(self, xs):
+        self._check(xs)
+        tds = list(xs)
+        for i, node in enumerate(self.td_fuses):
+            tds[-2 - i] = node._eager([xs[-2 - i], self.upsample(tds[-1 - i])])
+        outs = list(tds)
+        for i, node in enumerate(self.out_fuses):
+            outs[i + 1] = node._eager([xs[i + 1], tds[i + 1], self.downsample(tds[i])])
+        outs[-1] = self.last_out_fuse._eager([xs[-1], self.downsample(tds[-2])])
+        return outs
+
+
+# https://github.com/google/automl/blob/master/efficientdet/efficientdet_arch.py
+class BiFPN(_NeckBase):
+    def __init__(
+        self,
+        in_channels_list: "list[int]",
+        out_channels: int = 64,
+        num_layers: int = 1,
+        block: Callable[[int, int], nn.Module] = SeparableConv2d,
+        interpolation_mode="nearest",
+        eps: float = 1e-4,
+    ):
+        super().__init__()
+        self.out_channels = out_channels
+        self.laterals = nn.ModuleList([nn.Conv2d(in_c, out_channels, kernel_size=1) for in_c in in_channels_list])
+        self.layers = nn.ModuleList(
+            [BiFPNLayer(len(in_channels_list), out_channels, block=block, interpolation_mode=interpolation_mode, eps=eps)
+             for _ in range(num_layers)]
+        )
+
+    def _vt_emit_list(self, b, xs, name: str = "bifpn"):
+        if len(xs) != len(self.laterals):
+            raise ValueError(f"BiFPN: {len(xs)} feature maps for {len(self.laterals)} lateral convs")
+        outs = [b.conv_unit(x, lat, None, False, name=f"{name}.laterals.{i}") for i, (lat, x) in enumerate(zip(self.laterals, xs))]
+        for l, layer in enumerate(self.layers):
+            outs = layer._vt_emit_list(b, outs, f"{name}.layers.{l}")
+        return outs
+
+    def _eager_list(self, xs):
+        if len(xs) != len(self.laterals):
+            raise ValueError(f"BiFPN: {len(xs)} feature maps for {len(self.laterals)} lateral convs")
+        outs = [lat(x) for lat, x in zip(self.laterals, xs)]
+        for layer in self.layers:
+            outs = layer._eager_list(outs)
+        return outs
