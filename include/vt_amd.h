@@ -882,6 +882,26 @@ int vt_wfuse_bwd(int32_t n, const void* g, int32_t ldg, const void* x0, int32_t 
                  float* sums, int32_t B, int32_t H, int32_t W, int32_t C, int32_t dtype, void* stream);
 int vt_wfuse_finalize(const float* sums, const float* weights, float eps, int32_t n, float* dweights, void* stream);
 
+/* ---- SPPBlock: cascaded stride-1 pooling (components.py:139-152) ---------- */
+/* p_1 = pool(x), p_s = pool(p_{s-1}), pool = MaxPool2d / AvgPool2d(k, 1, (k-1)/2); y = cat(p_1 .. p_repeats) over channels (x
+ * itself is not part of it).  x is [B][H][W][C] with pixel stride ldx >= C, y is [B][H][W] with ldy >= repeats*C and stage s
+ * (0-based) in channels [s*C, (s+1)*C); C is a whole number of 16-byte chunks.  Geometry (vt_spp_supported): k odd, 3 <= k <= 15
+ * (a tap is one byte), repeats in 1..4, repeats*(k-1)/2 <= 8; any H, W >= 1.  Anything else returns VT_ERR_UNSUPPORTED.
+ * vt_spp_fwd, ONE launch for all stages:
+ *   pool 0 (max): positions outside the image never win; exact in the compute dtype.  With taps != NULL it also writes
+ *     taps[repeats][B][H][W][C] (uint8, 16-byte aligned): the window tap dy*k + dx of the winner, the FIRST maximum of the
+ *     clipped window in row-major order (torch's rule, which its backward sends the whole gradient to).
+ *   pool 1 (avg): f32 sums times 1/k^2 with zeros outside the image at EVERY stage (count_include_pad); stage s+1 reads the
+ *     stored (rounded) values of stage s.  taps is ignored.
+ *   Inputs are finite by contract: what a NaN in x does is not specified.
+ * vt_spp_bwd, ONE launch, gather form, no atomics, bit-identical runs: dy is the gradient of the whole y (lddy >=
+ *   repeats*C); dx (=|+= with accumulate) the gradient of x; max needs the taps of the forward launch, avg ignores them. */
+int vt_spp_supported(int32_t k, int32_t repeats);
+int vt_spp_fwd(const void* x, int32_t ldx, void* y, int32_t ldy, uint8_t* taps, int32_t B, int32_t H, int32_t W, int32_t C,
+               int32_t k, int32_t repeats, int32_t pool, int32_t dtype, void* stream);
+int vt_spp_bwd(const void* dy, int32_t lddy, const uint8_t* taps, void* dx, int32_t lddx, int32_t accumulate, int32_t B, int32_t H,
+               int32_t W, int32_t C, int32_t k, int32_t repeats, int32_t pool, int32_t dtype, void* stream);
+
 /* ---- ESEBlock gate (vovnet.py:20-28) ------------------------------------ */
 /* y = x * hardsigmoid(s[b][c]) [+ residual]; s is [B][C] (the biased 1x1 conv
  * of the pooled map, computed with vt_conv_igemm). */
@@ -1083,6 +1103,8 @@ enum vt_op_kind {
     VT_OP_WFUSE_FWD,                /* vt_wfuse_fwd */
     VT_OP_WFUSE_BWD,                /* vt_wfuse_bwd */
     VT_OP_WFUSE_FIN,                /* vt_wfuse_finalize */
+    VT_OP_SPP_FWD,                  /* vt_spp_fwd */
+    VT_OP_SPP_BWD,                  /* vt_spp_bwd */
     VT_OP_KIND_END
 };
 

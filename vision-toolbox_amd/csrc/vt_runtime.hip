@@ -241,6 +241,11 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
                                 I[16], I[17], I[18], st);
         case VT_OP_WFUSE_FIN:  // ptr: sums weights dweights | i: n | f: eps
             return vt_wfuse_finalize((const float*)P[0], (const float*)P[1], (float)F[0], I[0], (float*)P[2], st);
+        case VT_OP_SPP_FWD:  // ptr: x y taps | i: ldx ldy B H W C k repeats pool dtype
+            return vt_spp_fwd(P[0], I[0], P[1], I[1], (uint8_t*)P[2], I[2], I[3], I[4], I[5], I[6], I[7], I[8], I[9], st);
+        case VT_OP_SPP_BWD:  // ptr: dy taps dx | i: lddy lddx accumulate B H W C k repeats pool dtype
+            return vt_spp_bwd(P[0], I[0], (const uint8_t*)P[1], P[2], I[1], I[2], I[3], I[4], I[5], I[6], I[7], I[8], I[9], I[10],
+                              st);
         case VT_OP_TOKEN_MIX:  // ptr: x w bias residual z a | i: ldx ldw transw ldr ldz lda act B K M C dtype
             return vt_token_mix_fwd(P[0], I[0], P[1], I[1], I[2], (const float*)P[2], P[3], I[3], P[4], I[4], P[5], I[5], I[6], I[7],
                                     I[8], I[9], I[10], I[11], st);

@@ -168,7 +168,9 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_WFUSE_FWD,
     OP_WFUSE_BWD,
     OP_WFUSE_FIN,
-) = range(1, 111)
+    OP_SPP_FWD,
+    OP_SPP_BWD,
+) = range(1, 113)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -263,6 +265,8 @@ OP_NAMES = {
     OP_WFUSE_FWD: "wfuse_fwd",
     OP_WFUSE_BWD: "wfuse_bwd",
     OP_WFUSE_FIN: "wfuse_fin",
+    OP_SPP_FWD: "spp_fwd",
+    OP_SPP_BWD: "spp_bwd",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -467,6 +471,9 @@ SYMBOLS = {
     "vt_wfuse_bwd": (_i32, [_i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _f32, _vp, _i32, _i32, _vp, _i32,
                             _i32, _vp, _i32, _i32, _vp] + [_i32] * 5 + [_vp]),
     "vt_wfuse_finalize": (_i32, [_vp, _vp, _f32, _i32, _vp, _vp]),
+    "vt_spp_supported": (_i32, [_i32, _i32]),
+    "vt_spp_fwd": (_i32, [_vp, _i32, _vp, _i32, _vp] + [_i32] * 8 + [_vp]),
+    "vt_spp_bwd": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32] + [_i32] * 8 + [_vp]),
     "vt_pack_dgrad_filter_batch":(_i32, [_vp, _i32, _vp]),
     "vt_bn_eval_coeffs_batch": (_i32, [_vp, _i32, _vp]),
     "vt_pack_dgrad_filter": (_i32, [_vp, _i32, _i32, _vp, _i32, C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp]),

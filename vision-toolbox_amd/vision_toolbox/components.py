@@ -1,5 +1,5 @@
 """ConvNormAct -- the fused Conv -> BatchNorm -> ReLU unit of the hot path -- and SeparableConv2d, the depthwise + pointwise
-pair of such units that BiFPN builds on.
+pair of such units that BiFPN builds on, and SPPBlock, the cascaded-pooling block of YOLOv5-style necks.
 
 Same constructor signature, child names (`conv`, `norm`, `act`) and therefore the same
 state_dict keys as the reference unit (vision_toolbox/components.py:13-46), and the
@@ -24,7 +24,7 @@ from typing import Callable, Optional
 import torch
 from torch import Tensor, nn
 
-__all__ = ["ConvNormAct", "SeparableConv2d", "HipModule", "Permute", "StochasticDepth", "LayerScale"]
+__all__ = ["ConvNormAct", "SeparableConv2d", "SPPBlock", "HipModule", "Permute", "StochasticDepth", "LayerScale"]
 
 _RUNNERS: "weakref.WeakKeyDictionary[nn.Module, object]" = weakref.WeakKeyDictionary()
 
@@ -205,6 +205,58 @@ class SeparableConv2d(nn.Sequential, HipModule):
         return [self.pw(self.dw(x))]
 
     def forward(self, x: Tensor) -> Tensor:
+        return HipModule.forward(self, x)
+
+
+class SPPBlock(HipModule):
+    """The SPPF block of YOLOv5-style necks (reference components.py:139-152): one child `pool` -- MaxPool2d or AvgPool2d
+    (kernel_size, 1, (kernel_size - 1) // 2) -- applied `repeats` times in a cascade; the output is the concat of the
+    `repeats` pooled maps over channels (the input itself is not part of it).  No parameters.
+
+    On the GPU the whole block is one forward launch that writes every stage into its channel slice of the output and one
+    backward launch (Builder.spp -> vt_spp_fwd / vt_spp_bwd): odd kernel_size in 3..15, repeats in 1..4 and
+    repeats * (kernel_size - 1) / 2 <= 8 -- (5, 3), (3, 4), (7, 2), (9, 2), (13, 1) among them; other geometries raise
+    NotImplementedError.  An even kernel_size with repeats > 1 raises on every path: the maps shrink by a pixel per stage
+    and the reference's torch.cat refuses them."""
+
+    def __init__(self, kernel_size: int = 5, repeats: int = 3, pool: str = "max"):
+        super().__init__()
+        self.pool = dict(avg=nn.AvgPool2d, max=nn.MaxPool2d)[pool](kernel_size, 1, (kernel_size - 1) // 2)
+        self.repeats = repeats
+
+    def _vt_geometry(self) -> "tuple[int, int, str]":
+        k = self.pool.kernel_size
+        if not isinstance(k, int):
+            if len(set(k)) != 1:
+                raise NotImplementedError(f"SPPBlock: kernel_size {k!r} -- the MI355X path pools over square windows")
+            k = k[0]
+        return int(k), int(self.repeats), "avg" if isinstance(self.pool, nn.AvgPool2d) else "max"
+
+    def _check_concat(self) -> None:
+        k = self.pool.kernel_size
+        if self.repeats > 1 and any(int(v) % 2 == 0 for v in ((k,) if isinstance(k, int) else k)):
+            raise RuntimeError(f"SPPBlock: an even kernel_size ({k}) shrinks the map by a pixel per stage, so the {self.repeats} "
+                               "pooled maps cannot be concatenated")
+
+    def _vt_emit(self, b, x, out=None, name: str = "spp"):
+        self._check_concat()
+        k, repeats, pool = self._vt_geometry()
+        if x.logical_c != x.C:  # (an image whose channels were padded: the concat would interleave the padding)
+            raise NotImplementedError(f"{name}: SPPBlock over {x.logical_c} channels, which are not whole 16-byte chunks")
+        return b.spp(x, k, repeats, pool, out=out, name=name)
+
+    def _vt_emit_maps(self, b, x):
+        return [self._vt_emit(b, x)]
+
+    def _eager_maps(self, x: Tensor) -> "list[Tensor]":
+        outputs = []
+        for _ in range(self.repeats):
+            x = self.pool(x)
+            outputs.append(x)
+        return [torch.cat(outputs, dim=1)]
+
+    def forward(self, x: Tensor) -> Tensor:
+        self._check_concat()
         return HipModule.forward(self, x)
 
 

@@ -2022,6 +2022,41 @@ class Builder:
             self._node(y, bwd)
         return y
 
+    def spp(self, x: TRef, k: int, repeats: int, pool: str, out: Optional[TRef] = None, name: str = "spp") -> TRef:
+        """SPPBlock (components.py:139-152): `repeats` cascaded Max/AvgPool2d(k, 1, (k-1)/2) and their concat over channels
+        in ONE launch (vt_spp_fwd) that writes every stage into its channel slice of the output.  Backward: one launch
+        (vt_spp_bwd) takes the gradient of the whole concatenated map and writes or accumulates d(x).  The winners' taps
+        (one byte per element and stage, max only) are allocated only where a gradient is needed."""
+        k, repeats = int(k), int(repeats)
+        if pool not in ("max", "avg"):
+            raise KeyError(pool)
+        if not (3 <= k <= 15 and k % 2 == 1 and 1 <= repeats <= 4 and repeats * ((k - 1) // 2) <= 8):
+            raise NotImplementedError(
+                f"{name}: SPPBlock with kernel_size k={k} and repeats={repeats}: the MI355X path runs odd k in 3..15 (a winner's "
+                "tap is one byte) with repeats in 1..4 and repeats*(k-1)/2 <= 8")
+        epc = _EPC[self.dtype]
+        if x.C % epc:
+            raise NotImplementedError(f"{name}: {x.C} channels must be a multiple of {epc} for dtype {self.dtype} (whole 16-byte "
+                                      "chunks)")
+        self.tag += 1
+        code = 0 if pool == "max" else 1
+        y = out if out is not None else self.act(x.B, x.H, x.W, repeats * x.C, name + ".y")
+        assert (y.B, y.H, y.W, y.C) == (x.B, x.H, x.W, repeats * x.C)
+        track = self.need_grad and x.needs_grad
+        taps = self.alloc(repeats * x.B * x.H * x.W * x.C, name + ".taps") if track and code == 0 else None
+        geom = [x.B, x.H, x.W, x.C, k, repeats, code, self.dtype]
+        self.emit(N.OP_SPP_FWD, [x.addr(), y.addr(), self.bp(taps) if taps is not None else None], [x.ld, y.ld, *geom])
+        if track:
+
+            def bwd(dy):
+                gx, acc = self.grad_accum_target(x)
+                self.emit(N.OP_SPP_BWD, [dy.addr(), self.bp(taps) if taps is not None else None, gx.addr()],
+                          [dy.ld, gx.ld, acc, *geom])
+                self.grad_written(x)
+
+            self._node(y, bwd)
+        return y
+
     def global_avgpool(self, x: TRef, name="avgpool") -> TRef:
         """[B,H,W,C] -> [B,1,1,C]"""
         self.tag += 1
