@@ -902,6 +902,41 @@ int vt_spp_fwd(const void* x, int32_t ldx, void* y, int32_t ldy, uint8_t* taps, 
 int vt_spp_bwd(const void* dy, int32_t lddy, const uint8_t* taps, void* dx, int32_t lddx, int32_t accumulate, int32_t B, int32_t H,
                int32_t W, int32_t C, int32_t k, int32_t repeats, int32_t pool, int32_t dtype, void* stream);
 
+/* ---- DeformableConv2d: modulated deformable convolution (components.py:77-135) ---------- */
+/* torchvision's deform_conv2d with one offset group and groups = 1, NHWC:
+ *   y[b][ho][wo][co] = bias[co] + sum_{t = i*k + j} sum_ci w[co][t][ci] * m_t * bilinear(x[b], py, px)[ci]
+ *   py = ho*stride - padding + i*dilation + offset[2t], px = wo*stride - padding + j*dilation + offset[2t + 1]
+ * bilinear over floor and floor + 1; a corner outside [0, H-1] x [0, W-1] contributes zero; at an exactly integer position the
+ * floor cell is used (d(offset) is the right-hand derivative).  m_t = mask_act(mask[t]): mask_act 0 identity, 1 sigmoid; mask
+ * NULL: m = 1.  x is [B][H][W][Cin] (pixel stride ldx), y / dy [B][Ho][Wo][Cout], Ho = (H + 2 padding - dilation (k-1) - 1) /
+ * stride + 1; offset [B][Ho][Wo] x 2k^2 (ldo >= 2k^2) and mask [B][Ho][Wo] x k^2 (ldm >= k^2) in the compute dtype: every map
+ * may be a channel slice of a wider buffer; the offset / mask maps and their gradients need element alignment only.  w is the
+ * filter image [Cout][k][k][Cin] in the compute dtype, bias f32 or NULL.  vt_deform_supported: k 1 or 3, stride 1 or 2, Cin
+ * and Cout whole 16-byte chunks; anything else returns VT_ERR_UNSUPPORTED.  Positions, bilinear weights and the sigmoid are
+ * f32 in both dtypes; bf16 products run on MFMA with the blended sample rounded once to bf16, f32 is an exact FMA chain.
+ * vt_deform_fwd: ONE launch, no column matrix in memory.
+ * vt_deform_bwd: doffset and dmask (ignored with mask NULL) are WRITTEN (their 2k^2 / k^2 channels only), each by the one wave
+ *   that owns the pixel, in a fixed order: bit-identical runs.  dx != NULL: d(x) is scattered with f32 atomics into `plane`
+ *   (f32 [B][H][W][Cin], cleared here) and a flush pass writes (accumulate 0) or adds (1) the rounded plane to dx: d(x) is the
+ *   one output that is not bit-reproducible.  dx NULL: no scatter, plane ignored.
+ * vt_deform_wgrad: dw[Cout][k][k][Cin] += dy^T col and, with dbias != NULL, dbias[Cout] += column sums of dy (f32): partial
+ *   tiles per pixel slab in `scratch` (vt_deform_wgrad_scratch_bytes), then an ordered reducer inside the same call: no float
+ *   atomics, bit-identical runs. */
+int vt_deform_supported(int32_t k, int32_t stride, int32_t Cin, int32_t Cout, int32_t dtype);
+int vt_deform_fwd(const void* x, int32_t ldx, const void* offset, int32_t ldo, const void* mask, int32_t ldm, const void* w,
+                  const float* bias, void* y, int32_t ldy, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t k,
+                  int32_t stride, int32_t padding, int32_t dilation, int32_t mask_act, int32_t dtype, void* stream);
+int vt_deform_bwd(const void* dy, int32_t lddy, const void* x, int32_t ldx, const void* offset, int32_t ldo, const void* mask,
+                  int32_t ldm, const void* w, void* doffset, int32_t lddo, void* dmask, int32_t lddm, void* dx, int32_t lddx,
+                  int32_t accumulate, float* plane, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t k,
+                  int32_t stride, int32_t padding, int32_t dilation, int32_t mask_act, int32_t dtype, void* stream);
+int64_t vt_deform_wgrad_scratch_bytes(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t k, int32_t stride,
+                                      int32_t padding, int32_t dilation);
+int vt_deform_wgrad(const void* dy, int32_t lddy, const void* x, int32_t ldx, const void* offset, int32_t ldo, const void* mask,
+                    int32_t ldm, float* dw, float* dbias, void* scratch, int64_t scratch_bytes, int32_t B, int32_t H, int32_t W,
+                    int32_t Cin, int32_t Cout, int32_t k, int32_t stride, int32_t padding, int32_t dilation, int32_t mask_act,
+                    int32_t dtype, void* stream);
+
 /* ---- ESEBlock gate (vovnet.py:20-28) ------------------------------------ */
 /* y = x * hardsigmoid(s[b][c]) [+ residual]; s is [B][C] (the biased 1x1 conv
  * of the pooled map, computed with vt_conv_igemm). */
@@ -1105,6 +1140,9 @@ enum vt_op_kind {
     VT_OP_WFUSE_FIN,                /* vt_wfuse_finalize */
     VT_OP_SPP_FWD,                  /* vt_spp_fwd */
     VT_OP_SPP_BWD,                  /* vt_spp_bwd */
+    VT_OP_DEFORM_FWD,               /* vt_deform_fwd */
+    VT_OP_DEFORM_BWD,               /* vt_deform_bwd */
+    VT_OP_DEFORM_WGRAD,             /* vt_deform_wgrad */
     VT_OP_KIND_END
 };
 

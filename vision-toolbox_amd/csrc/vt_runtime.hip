@@ -246,6 +246,15 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
         case VT_OP_SPP_BWD:  // ptr: dy taps dx | i: lddy lddx accumulate B H W C k repeats pool dtype
             return vt_spp_bwd(P[0], I[0], (const uint8_t*)P[1], P[2], I[1], I[2], I[3], I[4], I[5], I[6], I[7], I[8], I[9], I[10],
                               st);
+        case VT_OP_DEFORM_FWD:  // ptr: x offset mask w bias y | i: ldx ldo ldm ldy B H W Cin Cout k s p d mask_act dtype
+            return vt_deform_fwd(P[0], I[0], P[1], I[1], P[2], I[2], P[3], (const float*)P[4], P[5], I[3], I[4], I[5], I[6], I[7],
+                                 I[8], I[9], I[10], I[11], I[12], I[13], I[14], st);
+        case VT_OP_DEFORM_BWD:  // ptr: dy x offset mask w doffset dmask dx plane | i: lddy ldx ldo ldm lddo lddm lddx accumulate B ..
+            return vt_deform_bwd(P[0], I[0], P[1], I[1], P[2], I[2], P[3], I[3], P[4], P[5], I[4], P[6], I[5], P[7], I[6], I[7],
+                                 (float*)P[8], I[8], I[9], I[10], I[11], I[12], I[13], I[14], I[15], I[16], I[17], I[18], st);
+        case VT_OP_DEFORM_WGRAD:  // ptr: dy x offset mask dw dbias scratch | i: lddy ldx ldo ldm B .. dtype | f: scratch bytes
+            return vt_deform_wgrad(P[0], I[0], P[1], I[1], P[2], I[2], P[3], I[3], (float*)P[4], (float*)P[5], P[6], (int64_t)F[0],
+                                   I[4], I[5], I[6], I[7], I[8], I[9], I[10], I[11], I[12], I[13], I[14], st);
         case VT_OP_TOKEN_MIX:  // ptr: x w bias residual z a | i: ldx ldw transw ldr ldz lda act B K M C dtype
             return vt_token_mix_fwd(P[0], I[0], P[1], I[1], I[2], (const float*)P[2], P[3], I[3], P[4], I[4], P[5], I[5], I[6], I[7],
                                     I[8], I[9], I[10], I[11], st);

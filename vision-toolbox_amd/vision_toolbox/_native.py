@@ -170,7 +170,10 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_WFUSE_FIN,
     OP_SPP_FWD,
     OP_SPP_BWD,
-) = range(1, 113)
+    OP_DEFORM_FWD,
+    OP_DEFORM_BWD,
+    OP_DEFORM_WGRAD,
+) = range(1, 116)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -267,6 +270,9 @@ OP_NAMES = {
     OP_WFUSE_FIN: "wfuse_fin",
     OP_SPP_FWD: "spp_fwd",
     OP_SPP_BWD: "spp_bwd",
+    OP_DEFORM_FWD: "deform_fwd",
+    OP_DEFORM_BWD: "deform_bwd",
+    OP_DEFORM_WGRAD: "deform_wgrad",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -474,6 +480,12 @@ SYMBOLS = {
     "vt_spp_supported": (_i32, [_i32, _i32]),
     "vt_spp_fwd": (_i32, [_vp, _i32, _vp, _i32, _vp] + [_i32] * 8 + [_vp]),
     "vt_spp_bwd": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32] + [_i32] * 8 + [_vp]),
+    "vt_deform_supported": (_i32, [_i32] * 5),
+    "vt_deform_fwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32] + [_i32] * 11 + [_vp]),
+    "vt_deform_bwd": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp]
+                      + [_i32] * 11 + [_vp]),
+    "vt_deform_wgrad_scratch_bytes": (_i64, [_i32] * 9),
+    "vt_deform_wgrad": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64] + [_i32] * 11 + [_vp]),
     "vt_pack_dgrad_filter_batch":(_i32, [_vp, _i32, _vp]),
     "vt_bn_eval_coeffs_batch": (_i32, [_vp, _i32, _vp]),
     "vt_pack_dgrad_filter": (_i32, [_vp, _i32, _i32, _vp, _i32, C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp]),

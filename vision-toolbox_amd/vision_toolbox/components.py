@@ -1,5 +1,6 @@
 """ConvNormAct -- the fused Conv -> BatchNorm -> ReLU unit of the hot path -- and SeparableConv2d, the depthwise + pointwise
-pair of such units that BiFPN builds on, and SPPBlock, the cascaded-pooling block of YOLOv5-style necks.
+pair of such units that BiFPN builds on, SPPBlock, the cascaded-pooling block of YOLOv5-style necks, and DeformableConv2d,
+the modulated deformable convolution (defined here and importable by name; it is not listed in `__all__`).
 
 Same constructor signature, child names (`conv`, `norm`, `act`) and therefore the same
 state_dict keys as the reference unit (vision_toolbox/components.py:13-46), and the
@@ -258,6 +259,171 @@ class SPPBlock(HipModule):
     def forward(self, x: Tensor) -> Tensor:
         self._check_concat()
         return HipModule.forward(self, x)
+
+
+class DeformConv2d(nn.Module):
+    """The deformable convolution layer under torchvision's names (torchvision.ops.DeformConv2d is not a dependency of this
+    package): `weight` (out_channels, in_channels / groups, k, k) with kaiming_uniform_(a=sqrt(5)), `bias` (out_channels,)
+    with U(+-1 / sqrt(fan_in)).  forward(x, offset, mask=None) is deform_conv2d in plain torch, gather form: the CPU path of
+    DeformableConv2d (the GPU path never calls it: Builder.deform_conv)."""
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_size, stride=1, padding=0, dilation=1, groups: int = 1,
+                 bias: bool = True):
+        super().__init__()
+        if in_channels % groups or out_channels % groups:
+            raise ValueError("in_channels and out_channels must be divisible by groups")
+        pair = lambda v: (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+        self.in_channels, self.out_channels, self.groups = in_channels, out_channels, groups
+        self.kernel_size, self.stride, self.padding, self.dilation = pair(kernel_size), pair(stride), pair(padding), pair(dilation)
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels // groups, *self.kernel_size))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self) -> None:
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if self.bias is not None:
+            fan_in = self.weight.shape[1] * self.weight.shape[2] * self.weight.shape[3]
+            bound = 1 / math.sqrt(fan_in)
+            nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, x: Tensor, offset: Tensor, mask: Optional[Tensor] = None) -> Tensor:
+        return deform_conv2d(x, offset, self.weight, self.bias, self.stride, self.padding, self.dilation, mask)
+
+
+def deform_conv2d(x: Tensor, offset: Tensor, weight: Tensor, bias: Optional[Tensor] = None, stride=(1, 1), padding=(0, 0),
+                  dilation=(1, 1), mask: Optional[Tensor] = None) -> Tensor:
+    """torchvision's deform_conv2d with one offset group, in plain torch and differentiable by autograd.  Offset channel 2t is
+    dy and 2t + 1 is dx of tap t = i * kw + j; the sampling position is (ho * s - p + i * d + dy, wo * s - p + j * d + dx);
+    bilinear over floor and floor + 1, a corner outside the map contributes zero; the sample times the mask, then the weighted
+    sum over (tap, channel) plus bias.  `floor` has no gradient, so at an exactly integer position d(offset) is the right-hand
+    derivative, which is torchvision's choice."""
+    B, C_, H, W = x.shape
+    Cout, Cg, kh, kw = weight.shape
+    K2, G = kh * kw, C_ // Cg
+    Ho, Wo = offset.shape[-2:]
+    if offset.shape[1] != 2 * K2:
+        raise ValueError(f"offset has {offset.shape[1]} channels, one offset group of a {kh}x{kw} kernel has {2 * K2}")
+    dev, dt = x.device, x.dtype
+    ti = torch.arange(kh, device=dev).repeat_interleave(kw) * dilation[0]
+    tj = torch.arange(kw, device=dev).repeat(kh) * dilation[1]
+    by = (torch.arange(Ho, device=dev) * stride[0] - padding[0]).view(1, 1, Ho, 1) + ti.view(1, K2, 1, 1)
+    bx = (torch.arange(Wo, device=dev) * stride[1] - padding[1]).view(1, 1, 1, Wo) + tj.view(1, K2, 1, 1)
+    off = offset.reshape(B, K2, 2, Ho, Wo)
+    py, px = by.to(dt) + off[:, :, 0], bx.to(dt) + off[:, :, 1]
+    y0, x0 = py.detach().floor(), px.detach().floor()
+    ly, lx = py - y0, px - x0
+    flat = x.reshape(B, C_, H * W)
+
+    def corner(yy: Tensor, xx: Tensor, wgt: Tensor) -> Tensor:
+        valid = (yy >= 0) & (yy <= H - 1) & (xx >= 0) & (xx <= W - 1)
+        idx = (yy.clamp(0, H - 1) * W + xx.clamp(0, W - 1)).long().view(B, 1, K2 * Ho * Wo).expand(B, C_, K2 * Ho * Wo)
+        v = torch.gather(flat, 2, idx).view(B, C_, K2, Ho, Wo)
+        return v * (wgt * valid.to(dt)).unsqueeze(1)
+
+    col = (corner(y0, x0, (1 - ly) * (1 - lx)) + corner(y0, x0 + 1, (1 - ly) * lx) + corner(y0 + 1, x0, ly * (1 - lx)) +
+           corner(y0 + 1, x0 + 1, ly * lx))
+    if mask is not None:
+        col = col * mask.reshape(B, 1, K2, Ho, Wo)
+    y = torch.einsum("bgckhw,gock->bgohw", col.view(B, G, Cg, K2, Ho, Wo), weight.reshape(G, Cout // G, Cg, K2))
+    y = y.reshape(B, Cout, Ho, Wo)
+    return y if bias is None else y + bias.view(1, Cout, 1, 1)
+
+
+class DeformableConv2d(HipModule):
+    """Modulated deformable convolution (DCNv2; v2=False: DCNv1 without the mask) with the reference's signature and children
+    (components.py:77-135): `conv_offset = conv_fn(Cin, 2 k^2, k, stride=, padding=, dilation=)`, `conv_mask =
+    Sequential(conv_fn(Cin, k^2, ...), mask_act())` (None with v2=False) and `conv`, a DeformConv2d of our own under
+    torchvision's parameter names and initialisation -- state_dict keys conv_offset.{weight,bias}, conv_mask.0.{weight,bias},
+    conv.{weight,bias}.
+
+    The reference's default cannot be constructed: it calls `mask_act(inplace=True)` and nn.Sigmoid takes no such argument
+    (and torchvision, which its `conv` comes from, is not a dependency here).  This calls `mask_act(inplace=True)` and falls
+    back to `mask_act()` on TypeError.  `mask_init_bias` is unused in the reference; it is accepted and unused here too.
+
+    CPU tensors run plain torch in gather form (deform_conv2d above), with every argument the constructor accepts.  CUDA
+    tensors run a launch list (Builder.deform_conv -> two conv units, vt_deform_fwd / vt_deform_bwd / vt_deform_wgrad):
+    kernel_size 1 or 3, stride 1 or 2, groups = 1, in_channels and out_channels whole 16-byte chunks (8 in bf16, 4 in f32),
+    `conv_fn` children that are nn.Conv2d of the matching geometry, mask_act Sigmoid or Identity; everything else raises
+    NotImplementedError naming the argument.  d(x) leaves through float atomics, so a deterministic Builder refuses the block."""
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_size, stride: int = 1, padding: int = 0, dilation: int = 1,
+                 groups: int = 1, bias: bool = True, conv_fn: Callable[..., nn.Module] = nn.Conv2d,
+                 mask_act: Callable[..., nn.Module] = nn.Sigmoid, v2: bool = True, mask_init_bias: float = 0):
+        super().__init__()
+        num_locations = kernel_size ** 2 if isinstance(kernel_size, int) else kernel_size[0] * kernel_size[1]
+        self.conv_offset = conv_fn(in_channels, 2 * num_locations, kernel_size, stride=stride, padding=padding, dilation=dilation)
+        self.conv_mask = None
+        if v2:
+            try:
+                act = mask_act(inplace=True)
+            except TypeError:
+                act = mask_act()
+            self.conv_mask = nn.Sequential(
+                conv_fn(in_channels, num_locations, kernel_size, stride=stride, padding=padding, dilation=dilation), act)
+        self.conv = DeformConv2d(in_channels, out_channels, kernel_size, stride=stride, padding=padding, dilation=dilation,
+                                 groups=groups, bias=bias)
+
+    def _vt_reserve(self) -> "dict[int, int]":
+        """elements the slots of the offset / mask convolutions' parameters must hold in the flat store (ParamStore.ensure):
+        their 2 k^2 and k^2 output channels run as the next whole 16-byte chunk over zero rows (ConvSpec.from_conv)"""
+        out = {}
+        for conv in (self.conv_offset, self.conv_mask[0] if self.conv_mask is not None else None):
+            if isinstance(conv, nn.Conv2d) and conv.out_channels % 8:
+                rows = -(-conv.out_channels // 8) * 8
+                out[id(conv.weight)] = rows * conv.weight[0].numel()
+                if conv.bias is not None:
+                    out[id(conv.bias)] = rows
+        return out
+
+    def _vt_check(self, name: str) -> "tuple[int, int]":
+        """(kernel_size, mask_act code) of the MI355X path, or NotImplementedError naming the argument it does not cover"""
+        c = self.conv
+        no = lambda what: NotImplementedError(f"{name}: DeformableConv2d with {what} -- the MI355X path runs kernel_size 1 or 3, "
+                                              "stride 1 or 2, groups=1, conv_fn children that are nn.Conv2d and mask_act Sigmoid "
+                                              "or Identity (CPU tensors run every geometry)")
+        if c.kernel_size[0] != c.kernel_size[1] or c.kernel_size[0] not in (1, 3):
+            raise no(f"kernel_size={c.kernel_size}")
+        if c.stride[0] != c.stride[1] or c.stride[0] not in (1, 2):
+            raise no(f"stride={c.stride}")
+        if c.padding[0] != c.padding[1]:
+            raise no(f"padding={c.padding}")
+        if c.dilation[0] != c.dilation[1]:
+            raise no(f"dilation={c.dilation}")
+        if c.groups != 1:
+            raise no(f"groups={c.groups}")
+        code = 0
+        convs = [("conv_offset", self.conv_offset, 2)]
+        if self.conv_mask is not None:
+            convs.append(("conv_mask.0", self.conv_mask[0], 1))
+            act = self.conv_mask[1]
+            if isinstance(act, nn.Sigmoid):
+                code = 1
+            elif not isinstance(act, nn.Identity):
+                raise no(f"mask_act={type(act).__name__}")
+        for cname, m, mult in convs:
+            if type(m) is not nn.Conv2d:
+                raise no(f"conv_fn={type(m).__name__} ({cname})")
+            if (m.kernel_size != c.kernel_size or m.stride != c.stride or m.padding != c.padding or m.dilation != c.dilation or
+                    m.groups != 1 or m.in_channels != c.in_channels or m.out_channels != mult * c.kernel_size[0] ** 2 or
+                    m.padding_mode != "zeros"):
+                raise no(f"conv_fn: {cname} is {m} (not the geometry of conv)")
+        return c.kernel_size[0], code
+
+    def _vt_emit(self, b, x, out=None, name: str = "dcn"):
+        k, code = self._vt_check(name)
+        return b.deform_conv(x, self.conv_offset, self.conv_mask[0] if self.conv_mask is not None else None, self.conv, code,
+                             out=out, name=name)
+
+    def _vt_emit_maps(self, b, x):
+        return [self._vt_emit(b, x)]
+
+    def _eager_maps(self, x: Tensor) -> "list[Tensor]":
+        offset = self.conv_offset(x)
+        mask = self.conv_mask(x) if self.conv_mask is not None else None
+        return [self.conv(x, offset, mask)]
 
 
 # -- small modules of the reference's components.py that ConvNeXt's state_dict layout and CPU path need -----------------

@@ -167,6 +167,10 @@ class ParamStore:
         for p in params:
             if not p.is_floating_point():
                 raise TypeError("non floating point parameter")
+        for mod in self.root.modules():  # (DeformableConv2d: its offset / mask convolutions run over zero rows up to a chunk)
+            want = getattr(mod, "_vt_reserve", None)
+            if want is not None:
+                self.reserve.update(want())
         offs, slots, total = [], [], 0
         for p in params:
             offs.append(total)
@@ -248,11 +252,14 @@ class ConvSpec:
             raise NotImplementedError(f"dilation {self.dilation}: tap offsets are 8-bit")
 
     @classmethod
-    def from_conv(cls, conv: nn.Conv2d) -> "ConvSpec":
+    def from_conv(cls, conv: nn.Conv2d, out_channels: Optional[int] = None) -> "ConvSpec":
+        """(out_channels > conv.out_channels: the filter rows and bias entries beyond the parameters' own are zeros their
+        slots of the flat store reserve, as with from_linear)"""
         ks, st, dl, pd = conv.kernel_size, conv.stride, conv.dilation, conv.padding
         if ks[0] != ks[1] or st[0] != st[1] or dl[0] != dl[1] or pd[0] != pd[1]:
             raise NotImplementedError("hot path covers square convolutions (kernel, stride, dilation, padding)")
-        return cls(ks[0], st[0], pd[0], dl[0], conv.groups, conv.in_channels, conv.out_channels, conv.weight, conv.bias)
+        return cls(ks[0], st[0], pd[0], dl[0], conv.groups, conv.in_channels, out_channels or conv.out_channels, conv.weight,
+                   conv.bias)
 
     @classmethod
     def from_linear(cls, linear: nn.Linear, out_channels: Optional[int] = None) -> "ConvSpec":
@@ -576,6 +583,7 @@ class Builder:
         self._dw3_scratch: dict[int, Buf] = {}  # depthwise 3x3 + GELU + pool: the per-image filter-gradient shares, per size
         self._gconv_scratch: dict[int, Buf] = {}  # grouped 3x3: the filter gradient's slabs, per size
         self._dwt_scratch: dict[int, Buf] = {}  # tiled depthwise: the filter-gradient shares of the bands, per size
+        self._deform_scratch: dict[int, Buf] = {}  # deformable convolution: the filter gradient's slabs / the d(x) plane, per size
         # stochastic depth ("row" mode): float[n_sites][B] keep factors, one row per residual block in emission order.  The
         # region is written OUTSIDE the launch lists before every forward (BackboneRunner, TrainStep), as `mix` in the HYPER
         # buffer is, so captured graphs stay valid; the arena never reuses it, so the backward reads what the forward read.
@@ -682,7 +690,7 @@ class Builder:
             return (GRADS, off * 4)
         key = id(p)
         if key not in self.param_grad_off:
-            buf = self.zeroed_f32(p.numel(), "pgrad", bwd=True)
+            buf = self.zeroed_f32(max(p.numel(), self.store.reserve.get(key, 0)), "pgrad", bwd=True)
             self.param_grad_off[key] = buf.offset
         return (ZERO_B, self.param_grad_off[key])
 
@@ -2053,6 +2061,96 @@ class Builder:
                 self.emit(N.OP_SPP_BWD, [dy.addr(), self.bp(taps) if taps is not None else None, gx.addr()],
                           [dy.ld, gx.ld, acc, *geom])
                 self.grad_written(x)
+
+            self._node(y, bwd)
+        return y
+
+    def deform_conv(self, x: TRef, conv_offset: nn.Conv2d, conv_mask: Optional[nn.Conv2d], conv, mask_act: int,
+                    out: Optional[TRef] = None, name: str = "dcn") -> TRef:
+        """DeformableConv2d (components.py:77-135).  `conv_offset` and `conv_mask` are ordinary conv units (no norm, no
+        activation) that write the offset map and the raw mask logits in the compute dtype; their 2 k^2 and k^2 output
+        channels run as the next whole 16-byte chunk over zero filter rows (ConvSpec.from_conv(out_channels=)), so the maps
+        have logical_c < C and the deform kernels read them by leading dimension.  `conv` carries weight (Cout, Cin, k, k),
+        bias and the geometry; `mask_act`: 0 identity, 1 sigmoid, applied inside the kernels.  Forward: vt_deform_fwd.
+        Backward: vt_deform_wgrad (filter and bias, slabs + ordered reducer), then vt_deform_bwd, which writes d(offset) and
+        d(mask logit) into the two units' output gradients (their padding channels are cleared first) and scatters d(x) with
+        float atomics into an f32 plane that its flush pass writes or accumulates into d(x); the two units' data gradients
+        join d(x) when their own backward runs.  Because of those atomics a deterministic builder refuses the block."""
+        dt, epc = self.dtype, _EPC[self.dtype]
+        k, s, pad, dil = conv.kernel_size[0], conv.stride[0], conv.padding[0], conv.dilation[0]
+        Cin, Cout, K2 = conv.in_channels, conv.out_channels, conv.kernel_size[0] ** 2
+        if self.deterministic:
+            raise NotImplementedError(f"{name}: DeformableConv2d under a deterministic builder -- d(x) is scattered with float "
+                                      "atomics (a fixed-point scatter is not built)")
+        if k not in (1, 3) or conv.kernel_size[0] != conv.kernel_size[1]:
+            raise NotImplementedError(f"{name}: DeformableConv2d with kernel_size={conv.kernel_size}: the MI355X path runs 1 and 3")
+        if s not in (1, 2):
+            raise NotImplementedError(f"{name}: DeformableConv2d with stride={s}: the MI355X path runs 1 and 2")
+        if conv.groups != 1:
+            raise NotImplementedError(f"{name}: DeformableConv2d with groups={conv.groups}: the MI355X path runs groups=1")
+        if x.logical_c != Cin:
+            raise ValueError(f"{name}: conv expects {Cin} input channels, got {x.logical_c}")
+        if Cin % epc or x.C != Cin:
+            raise NotImplementedError(f"{name}: DeformableConv2d with in_channels={Cin}: must be a multiple of {epc} for dtype {dt} "
+                                      "(whole 16-byte chunks)")
+        if Cout % epc:
+            raise NotImplementedError(f"{name}: DeformableConv2d with out_channels={Cout}: must be a multiple of {epc} for dtype {dt} "
+                                      "(whole 16-byte chunks)")
+        padded = lambda c: ConvSpec.from_conv(c, out_channels=_round_up(c.out_channels, epc))
+        off = self.conv_unit(x, padded(conv_offset), None, 0, name=name + ".conv_offset")
+        off.logical_C = 2 * K2
+        msk = None
+        if conv_mask is not None:
+            msk = self.conv_unit(x, padded(conv_mask), None, 0, name=name + ".conv_mask")
+            msk.logical_C = K2
+        self.tag += 1
+        Ho, Wo = off.H, off.W
+        y = out if out is not None else self.act(x.B, Ho, Wo, Cout, name + ".y")
+        assert (y.B, y.H, y.W, y.C) == (x.B, Ho, Wo, Cout), "out geometry mismatch"
+        w, bias = conv.weight, conv.bias
+        wptr = self.pref(w, mirror=dt != N.VT_F32)
+        geom = [x.B, x.H, x.W, Cin, Cout, k, s, pad, dil, int(mask_act), dt]
+        self.emit(N.OP_DEFORM_FWD, [x.addr(), off.addr(), _addr(msk), wptr, self.pref(bias), y.addr()],
+                  [x.ld, off.ld, _ld(msk), y.ld, *geom])
+        if self.need_grad:
+
+            def scratch(nbytes: int, what: str) -> Buf:
+                # (one scratch per size: the launches that use it run on the main stream, in order)
+                buf = self._deform_scratch.get(nbytes)
+                if buf is None:
+                    buf = self._deform_scratch[nbytes] = self.alloc(nbytes, what)
+                return buf
+
+            def bwd(dy):
+                if w.requires_grad:
+                    nbytes = int(N.lib().vt_deform_wgrad_scratch_bytes(x.B, x.H, x.W, Cin, Cout, k, s, pad, dil))
+                    self.emit(N.OP_DEFORM_WGRAD,
+                              [dy.addr(), x.addr(), off.addr(), _addr(msk), self.pgrad(w), self.pgrad(bias),
+                               self.bp(scratch(nbytes, "deform_slabs"))], [dy.ld, x.ld, off.ld, _ld(msk), *geom], [nbytes])
+                elif bias is not None and bias.requires_grad:
+                    self.emit(N.OP_COLSUM, [dy.addr(), self.pgrad(bias)], [dy.ld, dy.C, dt], [y.M])
+                grads = []
+                for t in (off, msk):  # written whole: the logical channels by the kernel, the padding channels stay zero
+                    if t is None:
+                        grads.append(None)
+                        continue
+                    g, res = self.grad_target(t)
+                    assert res is None, "the offset / mask maps have one consumer"
+                    if t.logical_c != t.C:
+                        self.emit(N.OP_MEMSET, [g.addr()], [0], [t.M * t.C * t.esize])
+                    grads.append(g)
+                gx, acc, plane = None, 0, None
+                if x.needs_grad:
+                    gx, acc = self.grad_accum_target(x)
+                    plane = self.bp(scratch(x.M * Cin * 4, "deform_plane"))
+                self.emit(N.OP_DEFORM_BWD,
+                          [dy.addr(), x.addr(), off.addr(), _addr(msk), wptr, grads[0].addr(), _addr(grads[1]), _addr(gx), plane],
+                          [dy.ld, x.ld, off.ld, _ld(msk), grads[0].ld, _ld(grads[1]), _ld(gx), acc, *geom])
+                if x.needs_grad:
+                    self.grad_written(x)
+                for t in (off, msk):
+                    if t is not None:
+                        self.grad_written(t)
 
             self._node(y, bwd)
         return y
