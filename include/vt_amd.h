@@ -937,6 +937,36 @@ int vt_deform_wgrad(const void* dy, int32_t lddy, const void* x, int32_t ldx, co
                     int32_t Cin, int32_t Cout, int32_t k, int32_t stride, int32_t padding, int32_t dilation, int32_t mask_act,
                     int32_t dtype, void* stream);
 
+/* ---- Input pipeline: crop-resize-flip-erase from uint8 (reference data.py) ---------- */
+/* ONE launch turns a ragged batch of decoded uint8 HWC images into out[B][3][S_h][S_w] (f32, NCHW, the trainer's input batch).
+ * Every pointer is a device pointer; the geometry is read from the tables by the kernel, the grid depends on (B, S_h, S_w) only.
+ *   raw     all images packed, each [H][W][3] uint8
+ *   table   int64 [B][3] = (byte offset of the image in raw, H, W); trusted: it says where the images are.  H, W <= 2^20.
+ *           A row with H < 1, W < 1 or a negative offset names no image: nothing is read for it and its output is all zeros.
+ *   params  int32 [B][16] = top, left, h, w, OH, OW, oy, ox, flip, ei, ej, eh, ew, erase mode, seed, constant (f32 bits)
+ * Per image: the crop box (top, left, h, w) is resized to a virtual (OH, OW) image and the (S_h, S_w) window at (oy, ox) of it is
+ * produced (training: OH, OW = S_h, S_w and oy = ox = 0; validation: the whole image to the Resize size, the window is the
+ * centre crop).  The filter is torch's F.interpolate(mode="bilinear", antialias = antialias != 0, align_corners=False): along an
+ * axis of n source and `out` virtual pixels, with s = n / out, support = max(s, 1) (antialias) or 1, c = s (i + 0.5), the taps
+ * of output i are j in [max(int(c - support + 0.5), 0), min(int(c + support + 0.5), n)) with weight max(0, 1 - |j + 0.5 - c| /
+ * support) over the sum of the weights; separable, never leaving the crop box, no rounding to 8 bits in between.  Then: flip
+ * != 0 mirrors the columns of the window; the value is multiplied by 1/255; with mean_std != NULL (f32 [6] = mean[3], std[3])
+ * it becomes (v - mean[c]) / std[c]; last, with erase mode 1 or 2 and eh > 0, the box rows [ei, ei + eh) x columns [ej, ej + ew)
+ * of the OUTPUT is overwritten with the constant (mode 1) or with standard-normal values (mode 2) of the counter-based generator
+ *   mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16            (uint32)
+ *   k = mix(seed + 0x9e3779b9); k = mix(k + b); k = mix(k + c); k = mix(k + y); k = mix(k + x)     (output coordinates)
+ *   h1 = mix(k ^ 0x68bc21eb), h2 = mix(k ^ 0x02e5be93); u1 = ((h1 >> 8) + 1) / 2^24, u2 = (h2 >> 8) / 2^24
+ *   z = sqrtf(-2 logf(u1)) * cosf(6.2831855f * u2)                                                  (accurate f32 functions)
+ * which is part of the interface: the same (seed, b) gives the same values in every run.
+ * Whatever params holds is clamped into its image before it forms an address (a bad box cannot read outside its image); what
+ * such a box produces is not specified.  No atomics, a fixed summation order: repeated launches are bit-identical.
+ * lds_bytes caps the LDS plan (tables + the plane of horizontally filtered source rows); 0: the default (64 KiB); values above
+ * 160 KiB mean 160 KiB.  A band that needs more source rows than the plane holds runs in chunks, with the same bits.
+ * VT_ERR_INVALID: a null raw / table / params / out, B, S_h or S_w <= 0, a misaligned table, lds_bytes < 0 or too small for the
+ * tables and one source row. */
+int vt_augment_batch(const uint8_t* raw, const int64_t* table, const int32_t* params, float* out, int32_t B, int32_t S_h,
+                     int32_t S_w, int32_t antialias, const float* mean_std, int32_t lds_bytes, void* stream);
+
 /* ---- ESEBlock gate (vovnet.py:20-28) ------------------------------------ */
 /* y = x * hardsigmoid(s[b][c]) [+ residual]; s is [B][C] (the biased 1x1 conv
  * of the pooled map, computed with vt_conv_igemm). */

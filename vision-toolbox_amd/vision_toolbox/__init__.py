@@ -5,6 +5,7 @@ so `from vision_toolbox import backbones` keeps working; the arithmetic runs in
 libvt_amd.so (hand-written HIP for gfx950) and only on the GPU.
 """
 from . import backbones, checkpoint, components, necks
+from . import data
 from .components import ConvNormAct
 from .necks import FPN, PAN
 
