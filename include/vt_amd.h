@@ -967,6 +967,51 @@ int vt_deform_wgrad(const void* dy, int32_t lddy, const void* x, int32_t ldx, co
 int vt_augment_batch(const uint8_t* raw, const int64_t* table, const int32_t* params, float* out, int32_t B, int32_t S_h,
                      int32_t S_w, int32_t antialias, const float* mean_std, int32_t lds_bytes, void* stream);
 
+/* ---- Input pipeline: TrivialAugmentWide on 8-bit levels (reference data.py:44-52, its third stage) ---------- */
+/* With TrivialAugmentWide the image between resize / flip and ToTensor is 8-bit, as in the reference.  Two calls:
+ *
+ * vt_augment_batch_u8: the arguments of vt_augment_batch without mean_std, the SAME kernel body with another epilogue.  The
+ *   filtered value of vt_augment_batch on the 0 .. 255 scale, before the 1/255, is rounded half up (floorf(v + 0.5f), the
+ *   product rounded before the sum) and clamped to 0 .. 255: out is uint8 [B][S_h][S_w][3], the LEVELS.  No mean / std, no
+ *   erase (the erase fields of params are ignored).  A table row that names no image gives zeros.  out needs no alignment.
+ *
+ * vt_trivial_augment: u8 = those levels, ta = f64 [B][8] = (op, m0..m5, arg) per image, params = the table of
+ *   vt_augment_batch (only its erase fields ei, ej, eh, ew, mode, seed, constant are read), out f32 [B][3][S_h][S_w],
+ *   workspace u32 [B][4][256] (the three channel histograms and the gray histogram; cleared inside the call).  Per image the
+ *   op is applied to the levels, then out = float32(level) * (1.0f / 255.0f), then mean / std and the erase exactly as in
+ *   vt_augment_batch (same fields, same generator).  The ops, torchvision's TrivialAugmentWide order, with `a` the levels of
+ *   an image, H = S_h, W = S_w, and every result the level PIL 12 computes on an 8-bit RGB image:
+ *     0 Identity.
+ *     1 ShearX, 2 ShearY, 3 TranslateX, 4 TranslateY, 5 Rotate: PIL's Image.transform(AFFINE, (m0..m5), BILINEAR), fill 0.
+ *       For output pixel (x, y), in f64 with every product and sum rounded on its own (no FMA), left to right:
+ *         xin = m0 (x + .5) + m1 (y + .5) + m2,  yin = m3 (x + .5) + m4 (y + .5) + m5;
+ *         0 unless 0 <= xin < W and 0 <= yin < H;  xin -= .5, yin -= .5;  x0 = floor(xin), dx = xin - x0 (likewise y);
+ *         the neighbours (y0, x0), (y0, x0 + 1), (y0 + 1, x0), (y0 + 1, x0 + 1) with their indices clamped into the image;
+ *         v1 = p00 + (p01 - p00) dx, v2 = p10 + (p11 - p10) dx, v = v1 + (v2 - v1) dy, truncated.
+ *       The matrix (output -> input) is the host's: torchvision's inverse affine matrix, or PIL's Image.rotate matrix.
+ *     6 Brightness, 7 Color, 8 Contrast, 9 Sharpness: blend(deg, a, f) with f = float32(arg):
+ *         t = f32(deg) + f * (f32(a) - f32(deg)) (a product, then a sum);  0 if t <= 0, 255 if t >= 255, else t truncated.
+ *       gray g = (19595 R + 38470 G + 7471 B + 32768) >> 16.  Brightness: deg = 0.  Color: deg = g on all three channels.
+ *       Contrast: deg = int(mean of g over the image (f64: the integer sum over H W) + 0.5).  Sharpness: deg = PIL's SMOOTH,
+ *       floor((sum of the 3 x 3 + 4 centre) / 13 + 0.5) inside, the first and last row and column copied.
+ *     10 Posterize: a & (256 - (1 << (8 - k))), k = arg.      11 Solarize: a if a < arg (f64) else 255 - a.
+ *     12 AutoContrast, per channel: lo, hi = the lowest and highest level present; identity if hi <= lo; else in f64
+ *         scale = 255 / (hi - lo), offset = -lo scale, lut[i] = clamp(int(i scale + offset), 0, 255).
+ *     13 Equalize, per channel with histogram h: identity if at most one bin is non-zero; step = (H W - h[highest non-zero
+ *         bin]) / 255 (integer); identity if 0; n = step / 2; for i in 0 .. 255: lut[i] = min(n / step, 255), n += h[i].
+ *   The histograms are built with integer atomics only (no float atomics anywhere): repeated launches are bit-identical.
+ *   The op differs per image inside one launch; any S_h x S_w with S_h S_w < 2^31 runs (no image has to fit in LDS).
+ *   ta ON THE DEVICE IS NOT VALIDATED: an op that is not a number in [0, 14) is Identity (NaN included), a fractional op is
+ *   truncated; Posterize's k is truncated and clamped into 1 .. 8 (NaN: 1); a matrix with NaNs or huge coefficients fills
+ *   with 0 wherever the coordinate tests fail; a factor or threshold that is not a number gives unspecified levels.  No
+ *   value of ta or params forms an address outside u8, workspace or out.
+ *   VT_ERR_INVALID: a null u8 / ta / params / out / workspace, B, S_h or S_w <= 0, S_h S_w >= 2^31, a misaligned ta (8),
+ *   params, out, workspace or mean_std (4). */
+int vt_augment_batch_u8(const uint8_t* raw, const int64_t* table, const int32_t* params, uint8_t* out, int32_t B, int32_t S_h,
+                        int32_t S_w, int32_t antialias, int32_t lds_bytes, void* stream);
+int vt_trivial_augment(const uint8_t* u8, const double* ta, const int32_t* params, float* out, uint32_t* workspace, int32_t B,
+                       int32_t S_h, int32_t S_w, const float* mean_std, void* stream);
+
 /* ---- ESEBlock gate (vovnet.py:20-28) ------------------------------------ */
 /* y = x * hardsigmoid(s[b][c]) [+ residual]; s is [B][C] (the biased 1x1 conv
  * of the pooled map, computed with vt_conv_igemm). */

@@ -37,7 +37,14 @@
 // x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (32-bit).  k = mix(seed + 0x9e3779b9); k = mix(k + b); k = mix(k + c);
 // k = mix(k + y); k = mix(k + x) with (b, c, y, x) the OUTPUT coordinates; h1 = mix(k ^ 0x68bc21eb), h2 = mix(k ^
 // 0x02e5be93); u1 = ((h1 >> 8) + 1) 2^-24 in (0, 1], u2 = (h2 >> 8) 2^-24 in [0, 1);
-// z = sqrtf(-2 logf(u1)) * cosf(6.2831855f * u2) with the accurate f32 functions.
+// z = sqrtf(-2 logf(u1)) * cosf(6.2831855f * u2) with the accurate f32 functions.  (vt_augment_erase.h, shared with
+// vt_trivial_augment.hip.)
+//
+// THE 8-BIT ENTRY.  vt_augment_batch_u8 is the same kernel body with another epilogue (template parameter U8): the levels
+// that TrivialAugmentWide works on, uint8 [B][S_h][S_w][3].
+#include <type_traits>
+
+#include "vt_augment_erase.h"
 #include "vt_common.h"
 
 namespace {
@@ -89,29 +96,12 @@ __device__ AxisTap axis_tap(int i, int n, int out, int sup) {
     return t;
 }
 
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-__device__ float erase_normal(uint32_t seed, uint32_t b, uint32_t c, uint32_t y, uint32_t x) {
-    uint32_t k = mix32(seed + 0x9e3779b9u);
-    k = mix32(k + b);
-    k = mix32(k + c);
-    k = mix32(k + y);
-    k = mix32(k + x);
-    const uint32_t h1 = mix32(k ^ 0x68bc21ebu), h2 = mix32(k ^ 0x02e5be93u);
-    const float u1 = (float)((h1 >> 8) + 1u) * 5.9604644775390625e-8f;  // 2^-24, exact
-    const float u2 = (float)(h2 >> 8) * 5.9604644775390625e-8f;
-    return sqrtf(-2.0f * logf(u1)) * cosf(6.2831855f * u2);
-}
-
+// U8 = false: the float32 NCHW batch (vt_augment_batch).  U8 = true: the EPILOGUE alone changes -- the filtered value on the
+// 0 .. 255 scale is rounded half up to a level and stored as uint8 [B][S_h][S_w][3], without 1/255, mean / std or erase
+// (vt_augment_batch_u8, the input of vt_trivial_augment).
+template <bool U8>
 __global__ __launch_bounds__(kT) void augment_kernel(const uint8_t* __restrict__ raw, const long long* __restrict__ table,
-                                                     const int* __restrict__ params, float* __restrict__ out,
+                                                     const int* __restrict__ params, std::conditional_t<U8, uint8_t, float>* __restrict__ out,
                                                      const float* __restrict__ mean_std, AugGeo g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     AxisTap* colt = (AxisTap*)smem;                  // [CW]
@@ -128,14 +118,19 @@ __global__ __launch_bounds__(kT) void augment_kernel(const uint8_t* __restrict__
     const int Rb = min(g.R, g.Sh - Y0), Cb = min(g.CW, g.Sw - X0);
     const int x = t % g.CW, tr = t / g.CW;
     const bool active = tr < g.trows && x < Cb;
-    float* outb = out + (long long)b * 3 * g.Sh * g.Sw;
+    auto* outb = out + (long long)b * 3 * g.Sh * g.Sw;
 
     const long long off = table[3 * b], Hl = table[3 * b + 1], Wl = table[3 * b + 2];
     if (Hl < 1 || Wl < 1 || off < 0) {  // no image: zeros (uniform over the workgroup, in front of every barrier)
         for (int m = 0; m < kRowsPerThread; ++m) {
             const int r = tr + g.trows * m;
             if (active && r < Rb)
-                for (int c = 0; c < 3; ++c) outb[((long long)c * g.Sh + (Y0 + r)) * g.Sw + X0 + x] = 0.0f;
+                for (int c = 0; c < 3; ++c) {
+                    if constexpr (U8)
+                        outb[((long long)(Y0 + r) * g.Sw + X0 + x) * 3 + c] = 0;
+                    else
+                        outb[((long long)c * g.Sh + (Y0 + r)) * g.Sw + X0 + x] = 0.0f;
+                }
         }
         return;
     }
@@ -209,6 +204,22 @@ __global__ __launch_bounds__(kT) void augment_kernel(const uint8_t* __restrict__
     }
 
     if (!active) return;
+    if constexpr (U8) {
+        const int X = X0 + x;
+#pragma unroll
+        for (int m = 0; m < kRowsPerThread; ++m) {
+            const int r = tr + g.trows * m;
+            if (r < Rb) {
+#pragma clang fp contract(off)  // (the product is rounded before the half is added, as on the host)
+                const float inv = rowt[r].inv;
+                uint8_t* d = outb + ((long long)(Y0 + r) * g.Sw + X) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c)  // half up; fminf / fmaxf also turn a NaN (there is none) into a level
+                    d[c] = (uint8_t)fminf(fmaxf(floorf(acc[c][m] * inv + 0.5f), 0.0f), 255.0f);
+            }
+        }
+        return;
+    }
     const long long ei = p[9], ej = p[10], eh = p[11], ew = p[12];
     const int mode = p[13];
     const uint32_t seed = (uint32_t)p[14];
@@ -233,17 +244,14 @@ __global__ __launch_bounds__(kT) void augment_kernel(const uint8_t* __restrict__
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int vt_augment_batch(const uint8_t* raw, const int64_t* table, const int32_t* params, float* out, int32_t B, int32_t S_h,
-                     int32_t S_w, int32_t antialias, const float* mean_std, int32_t lds_bytes, void* stream) {
-    const char* who = "vt_augment_batch";
+template <bool U8>
+int augment_launch(const char* who, const uint8_t* raw, const int64_t* table, const int32_t* params,
+                   std::conditional_t<U8, uint8_t, float>* out, int32_t B, int32_t S_h, int32_t S_w, int32_t antialias,
+                   const float* mean_std, int32_t lds_bytes, void* stream) {
     VT_REQUIRE(raw && table && params && out, VT_ERR_INVALID, "%s: null pointer (raw %p, table %p, params %p, out %p)", who,
                (const void*)raw, (const void*)table, (const void*)params, (const void*)out);
     VT_REQUIRE(B > 0 && S_h > 0 && S_w > 0, VT_ERR_INVALID, "%s: non-positive size (B %d, S_h %d, S_w %d)", who, B, S_h, S_w);
-    VT_REQUIRE((((uintptr_t)table) & 7) == 0 && (((uintptr_t)params) & 3) == 0 && (((uintptr_t)out) & 3) == 0 &&
+    VT_REQUIRE((((uintptr_t)table) & 7) == 0 && (((uintptr_t)params) & 3) == 0 && (U8 || (((uintptr_t)out) & 3) == 0) &&
                    (((uintptr_t)mean_std) & 3) == 0,
                VT_ERR_INVALID, "%s: misaligned table (8), params, out or mean_std (4)", who);
     VT_REQUIRE(lds_bytes >= 0, VT_ERR_INVALID, "%s: lds_bytes %d is negative", who, lds_bytes);
@@ -262,13 +270,27 @@ int vt_augment_batch(const uint8_t* raw, const int64_t* table, const int32_t* pa
     const long blocks = (long)B * g.bandsY * g.tilesX;
     VT_REQUIRE(blocks < (1L << 31), VT_ERR_INVALID, "%s: %ld workgroups", who, blocks);
     if (smem > 64 * 1024) {
-        const int rc = vt_raise_dynamic_lds((const void*)augment_kernel, smem, who);
+        const int rc = vt_raise_dynamic_lds((const void*)augment_kernel<U8>, smem, who);
         if (rc != VT_OK) return rc;
     }
-    hipLaunchKernelGGL(augment_kernel, dim3((unsigned)blocks), dim3(kT), smem, (hipStream_t)stream, raw, (const long long*)table,
-                       (const int*)params, out, mean_std, g);
+    hipLaunchKernelGGL(augment_kernel<U8>, dim3((unsigned)blocks), dim3(kT), smem, (hipStream_t)stream, raw,
+                       (const long long*)table, (const int*)params, out, mean_std, g);
     VT_CHECK_LAUNCH(who);
     return VT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vt_augment_batch(const uint8_t* raw, const int64_t* table, const int32_t* params, float* out, int32_t B, int32_t S_h,
+                     int32_t S_w, int32_t antialias, const float* mean_std, int32_t lds_bytes, void* stream) {
+    return augment_launch<false>("vt_augment_batch", raw, table, params, out, B, S_h, S_w, antialias, mean_std, lds_bytes, stream);
+}
+
+int vt_augment_batch_u8(const uint8_t* raw, const int64_t* table, const int32_t* params, uint8_t* out, int32_t B, int32_t S_h,
+                        int32_t S_w, int32_t antialias, int32_t lds_bytes, void* stream) {
+    return augment_launch<true>("vt_augment_batch_u8", raw, table, params, out, B, S_h, S_w, antialias, nullptr, lds_bytes, stream);
 }
 
 }  // extern "C"
