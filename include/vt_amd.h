@@ -62,7 +62,17 @@ extern "C" {
  * int64[VT_STAT_REPLICAS][2][C][2], VT_STAT_BYTES(C) bytes, zeroed by the caller and passed as float*: fixed point,
  * value = hi*2^12 + lo/2^33, accumulated with integer atomics.  Integer addition is associative, so the statistics --
  * and with them every activation, loss and data gradient -- are bit-identical from run to run;
- * vt_bn_finalize / vt_bn_bwd_finalize sum the replicas exactly.  SyncBatchNorm all-reduces the buffer as int64. */
+ * vt_bn_finalize / vt_bn_bwd_finalize sum the replicas exactly.  SyncBatchNorm all-reduces the buffer as int64.
+ *
+ * The marker.  A legitimate sum has |sum| < 2^50 (1.1e15), i.e. |hi| < 2^38.  A contribution that is NaN, +-Inf or has
+ * |v| >= 2^50 is not accumulated: it adds 2^40 to the hi limb instead, and EVERY decoder of the format -- vt_bn_finalize,
+ * vt_bn_finalize_apply, vt_bn_bwd_finalize, vt_bn_bwd_finalize_apply and the passes that finalize for themselves,
+ * vt_fixed_to_f32, vt_channel_sums_to_f32, vt_wfuse_finalize, vt_stem_bn_bwd_s2 / _combine / _combine_y -- returns NaN
+ * for an entry whose hi limb, summed over the replicas, has |hi| >= 2^38 (the marker carries no sign: -Inf gives NaN too).
+ * Legitimate contributions that together leave the range decode as NaN as well, never as a wrapped finite value.  The
+ * replicas are summed as integers, so vt_stat_fold and the int64 all-reduce preserve the marker of any replica or rank;
+ * other entries of the buffer are not affected.  A diverged activation thus shows up as NaN statistics, coefficients and
+ * parameter gradients, as it would with float sums. */
 #define VT_STAT_BYTES(C) ((int64_t)VT_STAT_REPLICAS * 2 * (C) * 16)
 
 /*
@@ -415,7 +425,8 @@ int vt_conv_wgrad_slabs(const vt_conv_desc* d, const void* x, const void* dz, fl
 int vt_conv_wgrad_group(const vt_conv_desc* d, int32_t n, const void* const* x, const void* const* dz,
                         float* const* dw, int32_t ldgw, void* stream);
 
-/* dst[i] (+)= hi[i]*2^12 + lo[i]/2^33 for a fixed-point buffer q = int64[n][2] (vt_colsum_fixed). */
+/* dst[i] (+)= hi[i]*2^12 + lo[i]/2^33 for a fixed-point buffer q = int64[n][2] (vt_colsum_fixed); a marked entry
+ * (|hi| >= 2^38, see VT_STAT_REPLICAS: a non-finite or out-of-range contribution) yields NaN. */
 int vt_fixed_to_f32(const void* q, float* dst, int64_t n, int32_t accumulate, void* stream);
 
 /* Re-pack a [Cout][ntaps][Cin] filter (f32 master or dtype mirror) into the
@@ -444,7 +455,8 @@ int vt_bn_finalize(const float* stats, int32_t C, double count, const float* gam
                    float* running_var, int64_t* num_batches_tracked, float* scale,
                    float* shift, float* mean, float* invstd, void* stream);
 /* Fold the VT_STAT_REPLICAS replicas of a statistics / sums buffer into replica 0 (exact integer adds) and zero the
- * others: SyncBatchNorm then all-reduces 32*C bytes per layer instead of the whole buffer. */
+ * others: SyncBatchNorm then all-reduces 32*C bytes per layer instead of the whole buffer.  The marker of a non-finite
+ * contribution (see VT_STAT_REPLICAS) is part of the hi limb and is folded with it. */
 int vt_stat_fold(float* stats, int32_t C, void* stream);
 /* eval: coefficients from the running statistics. */
 int vt_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean,
@@ -829,7 +841,9 @@ int vt_maxpool3x3s2_bwd(const void* dy, int32_t lddy, const uint8_t* argmax, voi
                         int32_t lddx, int32_t B, int32_t H, int32_t W, int32_t C,
                         int32_t accumulate, int32_t dtype, void* stream);
 /* nn.AdaptiveAvgPool2d((1,1)) of the classifier head (classifier.py:61) and of
- * ESEBlock (vovnet.py:23). y is [B][C] with row stride ldy. */
+ * ESEBlock (vovnet.py:23). y is [B][C] with row stride ldy.  The sum over the pixels is 2^-32 fixed point (bit-identical
+ * from run to run); a cell (b, c) whose pixels hold a NaN, an Inf or partial sums of 2^22 and more yields NaN, other cells
+ * are not affected. */
 int vt_global_avgpool_fwd(const void* x, int32_t ldx, void* y, int32_t ldy, int32_t B,
                           int32_t HW, int32_t C, int32_t dtype, void* stream);
 int vt_global_avgpool_bwd(const void* dy, int32_t lddy, void* dx, int32_t lddx, int32_t B,
@@ -1018,7 +1032,8 @@ int vt_trivial_augment(const uint8_t* u8, const double* ta, const int32_t* param
 int vt_ese_gate_fwd(const void* x, int32_t ldx, const void* s, int32_t lds,
                     const void* residual, int32_t ldr, void* y, int32_t ldy, int32_t B,
                     int32_t HW, int32_t C, int32_t dtype, void* stream);
-/* dx (=|+=) dy*hsig(s);  ds[b][c] = hsig'(s) * sum_hw dy*x  (f32 [B][C]) */
+/* dx (=|+=) dy*hsig(s);  ds[b][c] = hsig'(s) * sum_hw dy*x  (f32 [B][C]; the sum as in vt_global_avgpool_fwd: NaN for a
+ * cell with a non-finite or out-of-range (2^22) partial sum) */
 int vt_ese_gate_bwd(const void* dy, int32_t lddy, const void* x, int32_t ldx, const void* s,
                     int32_t lds, void* dx, int32_t lddx, float* ds, int32_t B, int32_t HW,
                     int32_t C, int32_t accumulate, int32_t dtype, void* stream);

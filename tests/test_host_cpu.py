@@ -347,6 +347,20 @@ def test_statistics_buffer_fixed_point_roundtrip():
     assert got[0][3].item() == 3.25 - 0.03125 and got[0][5].item() == 4096.0 - 8192.5  # dyadic values: exact
     hi = buf[3, 0, :, 0]
     assert hi.tolist() == [0, 0, 0, 0, 0, 1, 3013]  # trunc(v / 4096): the hi limb stays zero below 4096
+    # the marker of a non-finite / out-of-range contribution (vt_common.h: 2^40 added to the hi limb, here by the LAST
+    # replica): that entry decodes to NaN as every kernel decodes it, whatever the other replicas hold; its neighbours,
+    # the other row and a sum just inside the legitimate range (|hi| < 2^38) are untouched
+    before = got.clone()
+    buf[N.VT_STAT_REPLICAS - 1, 0, 6, 0] += N.STAT_MARKER
+    buf[2, 1, 1, 0] -= N.STAT_MARKER  # two markers of replicas that also hold values; negative limbs count too
+    buf[5, 1, 1, 0] -= N.STAT_MARKER
+    buf[4, 1, 3, 0] += (1 << 38) - 1  # (entry [1][3] holds -0.03125: hi limb 0 so far)
+    got = N.stats_decode(buf)
+    bad = torch.zeros(2, C_, dtype=torch.bool)
+    bad[0, 6] = bad[1, 1] = True
+    assert torch.equal(torch.isnan(got), bad)
+    before[1, 3] += float(((1 << 38) - 1) * 4096)
+    assert torch.equal(got[~bad], before[~bad])
 
 
 def test_padded_stem_filter_is_read_from_the_bf16_mirror():

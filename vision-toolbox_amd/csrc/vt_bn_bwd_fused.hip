@@ -202,11 +202,7 @@ __global__ void __launch_bounds__(kT) bn_bwd_fused_kernel(const FArgs a) {
                 }
             }
             if (rp == 0) {
-                auto nat = [](long long h, long long l) -> double {
-                    if (h >= (kStatPoison >> 2) || h <= -(kStatPoison >> 2)) return __longlong_as_double(0x7ff8000000000000LL);
-                    return (double)h * 4096.0 + (double)l * (1.0 / 8589934592.0);
-                };
-                const double S1 = nat(hi[0], lo[0]), S2 = nat(hi[1], lo[1]);
+                const double S1 = vt_stat_decode(hi[0], lo[0]), S2 = vt_stat_decode(hi[1], lo[1]);
                 const float av = a.scale[c], mv = a.mean[c], istd = a.invstd[c];
                 if (a.dgamma) a.dgamma[c] += (float)(S2 * a.pscale);
                 if (a.dbeta) a.dbeta[c] += (float)(S1 * a.pscale);

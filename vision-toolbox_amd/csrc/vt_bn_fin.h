@@ -113,8 +113,7 @@ __device__ __forceinline__ double vt_replica_sum(const float* stats, long entry,
     long long hi = 0, lo = 0;
 #pragma unroll
     for (int r = 0; r < kStatReplicas; ++r) hi += (long long)h[r], lo += (long long)l[r];
-    if (hi >= (kStatPoison >> 2) || hi <= -(kStatPoison >> 2)) return __longlong_as_double(0x7ff8000000000000LL);  // poisoned
-    return (double)hi * 4096.0 + (double)lo * (1.0 / 8589934592.0);
+    return vt_stat_decode(hi, lo);
 }
 
 // Thread t owns entry (w = t & 1, c = c_begin + t / 2); the lane pair swaps its sums and f(c, s0, s1, pre) runs in the w = 0

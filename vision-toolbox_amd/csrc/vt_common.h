@@ -39,13 +39,26 @@ int vt_device_cus(void);
 // (VT_STAT_BYTES(C) bytes, zeroed by the caller); the kernels take it as float* and index the limbs themselves.
 constexpr int kStatReplicas = VT_STAT_REPLICAS;
 #ifdef __HIPCC__
-// A non-finite (or absurdly large) contribution cannot be represented: it adds the marker 2^40 to the hi limb instead
-// (no legitimate sum of a layer comes near 2^38 * 4096 = 1e15), and vt_stat_sum turns a marked sum into NaN -- a
-// diverged activation shows up in the batch / running statistics as it did with float atomics, instead of as a
-// finite garbage value.  (2^20 marked contributions per replica before the limb could wrap.)
+// THE MARKER.  A legitimate sum is |sum| < 2^50 = 2^38 * 4096 = 1.1e15 (no sum of a layer comes near it), i.e. a hi limb
+// of |hi| < 2^38.  A contribution that is non-finite or has |v| >= 2^50 (kStatLimit) is not accumulated: it adds the
+// marker 2^40 to the hi limb instead, and every decoder (vt_stat_decode: vt_stat_sum, vt_replica_sum, vt_fixed_to_f32,
+// the stem combine kernels, N.stats_decode on the host) returns NaN for an entry whose summed hi limb has |hi| >= 2^38 --
+// a diverged activation shows up in the batch / running statistics, the bias and filter gradients as it did with float
+// atomics, instead of as a finite garbage value.  The arithmetic of the limb:
+//   * an accumulated contribution has |hi| < 2^38, so legitimate contributions that together leave the range (two of
+//     2^49.5) decode as NaN as well, never as a wrapped finite value; 2^24 contributions of the largest size fit an int64;
+//   * a marked entry stays marked unless the accumulated contributions of the same entry total below -3 * 2^38 * 4096
+//     (-3.4e15: three times the legitimate range, and themselves a marked sum); 2^22 markers fit an int64;
+//   * the replicas are summed as integers (vt_stat_fold, the int64 all-reduce of the data-parallel step), so the marker
+//     of any replica or rank survives into the sum that is decoded.
 constexpr long long kStatPoison = 1LL << 40;
+constexpr float kStatLimit = 1125899906842624.0f;  // 2^50
+__device__ __forceinline__ double vt_stat_decode(long long hi, long long lo) {
+    if (hi >= (kStatPoison >> 2) || hi <= -(kStatPoison >> 2)) return __longlong_as_double(0x7ff8000000000000LL);  // marked
+    return (double)hi * 4096.0 + (double)lo * (1.0 / 8589934592.0);
+}
 __device__ __forceinline__ void vt_stat_add(float* stats, long idx, float v) {
-    if (!(fabsf(v) < 1.0e30f)) {
+    if (!(fabsf(v) < kStatLimit)) {
         atomicAdd((unsigned long long*)stats + 2 * idx, (unsigned long long)kStatPoison);
         return;
     }
@@ -55,17 +68,18 @@ __device__ __forceinline__ void vt_stat_add(float* stats, long idx, float v) {
     atomicAdd(q + 1, (unsigned long long)__float2ll_rn(rem * 8589934592.0f));  // 2^33
     if (hf != 0.0f) atomicAdd(q, (unsigned long long)(long long)hf);
 }
-// exact integer sums over the replicas of entry `idx` (stride = entries per replica), as a double in natural units
+// exact integer sums over the R replicas of entry `idx` (stride = entries per replica), as a double in natural units;
+// NaN if the entry is marked
+template <int R = kStatReplicas>
 __device__ __forceinline__ double vt_stat_sum(const float* stats, long idx, long stride) {
     const long long* q = (const long long*)stats;
     long long hi = 0, lo = 0;
 #pragma unroll
-    for (int r = 0; r < kStatReplicas; ++r) {
+    for (int r = 0; r < R; ++r) {
         hi += q[2 * (idx + r * stride)];
         lo += q[2 * (idx + r * stride) + 1];
     }
-    if (hi >= (kStatPoison >> 2) || hi <= -(kStatPoison >> 2)) return __longlong_as_double(0x7ff8000000000000LL);  // poisoned
-    return (double)hi * 4096.0 + (double)lo * (1.0 / 8589934592.0);
+    return vt_stat_decode(hi, lo);
 }
 #endif
 

@@ -19,12 +19,24 @@ namespace {
 
 // LDS sums over the row lanes of a block as 64-bit fixed point (2^-32): integer atomics, order-free (a float LDS
 // atomic made the pooled features, and with them logits and loss, differ in the last bit from run to run)
-__device__ __forceinline__ void lds_fix_add(unsigned long long* s, int i, float v) {
+// A partial sum that is non-finite or has |v| >= 2^22 is not accumulated: it sets the entry's word of `bad` (n words
+// behind the n sums, zeroed with them) with an integer atomic OR, and lds_fix_get returns NaN for such an entry -- a
+// diverged feature map gives NaN pooled features, logits and loss, as the float sum did, never a finite garbage value.
+// (At most 2^8 row lanes of |v| * 2^32 < 2^54 each: the 64-bit word cannot wrap.)
+constexpr float kLdsFixLimit = 4194304.0f;  // 2^22
+static_assert(kThreads <= 256, "lds_fix_add: 2^8 row lanes of 2^54 fit an int64");
+__device__ __forceinline__ void lds_fix_add(unsigned long long* s, unsigned* bad, int i, float v) {
+    if (!(fabsf(v) < kLdsFixLimit)) {
+        atomicOr(&bad[i], 1u);
+        return;
+    }
     atomicAdd(&s[i], (unsigned long long)__float2ll_rn(v * 4294967296.0f));
 }
-__device__ __forceinline__ float lds_fix_get(const unsigned long long* s, int i) {
+__device__ __forceinline__ float lds_fix_get(const unsigned long long* s, const unsigned* bad, int i) {
+    if (bad[i]) return __builtin_nanf("");
     return (float)((double)(long long)s[i] * (1.0 / 4294967296.0));
 }
+constexpr int kLdsFixBytes = sizeof(unsigned long long) + sizeof(unsigned);  // LDS per entry: the sum and its `bad` word
 
 // ---------------------------------------------------------------------------------
 // BatchNorm finalize (training): stats -> mean / invstd / scale / shift + running stats
@@ -853,13 +865,14 @@ avgpool_fwd_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy,
     constexpr int EPC = VecIO<T>::EPC;
     extern __shared__ unsigned long long sfix[];  // [CT*EPC] fixed point
     unsigned long long* sred = sfix;
+    unsigned* sbad = (unsigned*)(sfix + CT * EPC);  // [CT*EPC] (lds_fix_add)
     const int t = threadIdx.x;
     const int RT = kThreads / CT;
     const int b = blockIdx.x;
     const int col = blockIdx.y * CT + t % CT;
     const int r = t / CT;
     const int CPR = C / EPC;
-    for (int i = t; i < CT * EPC; i += kThreads) sred[i] = 0ull;
+    for (int i = t; i < CT * EPC; i += kThreads) sred[i] = 0ull, sbad[i] = 0u;
     __syncthreads();
     if (r < RT && col < CPR) {
         float s[EPC];
@@ -872,14 +885,14 @@ avgpool_fwd_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy,
             for (int e = 0; e < EPC; ++e) s[e] += v[e];
         }
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) lds_fix_add(sred, (t % CT) * EPC + e, s[e]);
+        for (int e = 0; e < EPC; ++e) lds_fix_add(sred, sbad, (t % CT) * EPC + e, s[e]);
     }
     __syncthreads();
     if (r == 0 && col < CPR) {
         float v[EPC];
         const float inv = 1.f / (float)HW;
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) v[e] = lds_fix_get(sred, (t % CT) * EPC + e) * inv;
+        for (int e = 0; e < EPC; ++e) v[e] = lds_fix_get(sred, sbad, (t % CT) * EPC + e) * inv;
         st16(y + (long)b * ldy + col * EPC, VecIO<T>::pack(v));
     }
 }
@@ -1087,13 +1100,14 @@ ese_bwd_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ x, int 
     constexpr int EPC = VecIO<T>::EPC;
     extern __shared__ unsigned long long sfix[];  // [CT*EPC] fixed point
     unsigned long long* sred = sfix;
+    unsigned* sbad = (unsigned*)(sfix + CT * EPC);  // [CT*EPC] (lds_fix_add)
     const int t = threadIdx.x;
     const int RT = kThreads / CT;
     const int b = blockIdx.x;
     const int col = blockIdx.y * CT + t % CT;
     const int r = t / CT;
     const int CPR = C / EPC;
-    for (int i = t; i < CT * EPC; i += kThreads) sred[i] = 0ull;
+    for (int i = t; i < CT * EPC; i += kThreads) sred[i] = 0ull, sbad[i] = 0u;
     __syncthreads();
     float sv[EPC];
     if (r < RT && col < CPR) {
@@ -1120,14 +1134,14 @@ ese_bwd_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ x, int 
             st16(dx + row * lddx + col * EPC, VecIO<T>::pack(o));
         }
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) lds_fix_add(sred, (t % CT) * EPC + e, acc[e]);
+        for (int e = 0; e < EPC; ++e) lds_fix_add(sred, sbad, (t % CT) * EPC + e, acc[e]);
     }
     __syncthreads();
     if (r == 0 && col < CPR) {
 #pragma unroll
         for (int e = 0; e < EPC; ++e) {
             const float d = (sv[e] > -3.f && sv[e] < 3.f) ? (1.f / 6.f) : 0.f;
-            ds[(long)b * C + col * EPC + e] = lds_fix_get(sred, (t % CT) * EPC + e) * d;
+            ds[(long)b * C + col * EPC + e] = lds_fix_get(sred, sbad, (t % CT) * EPC + e) * d;
         }
     }
 }
@@ -1578,7 +1592,7 @@ inline int vt_bn_order() {
 __global__ void __launch_bounds__(kThreads)
 fixed_to_f32_kernel(const long long* __restrict__ q, float* __restrict__ dst, long n, int accumulate) {
     for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads) {
-        const double v = (double)q[2 * i] * 4096.0 + (double)q[2 * i + 1] * (1.0 / 8589934592.0);
+        const double v = vt_stat_decode(q[2 * i], q[2 * i + 1]);  // NaN for a marked entry
         dst[i] = accumulate ? dst[i] + (float)v : (float)v;
     }
 }
@@ -1957,7 +1971,7 @@ int vt_global_avgpool_fwd(const void* x, int32_t ldx, void* y, int32_t ldy, int3
     const int CT = pool_ct(C, epc);
     const dim3 grid(B, (C / epc + CT - 1) / CT);
     VT_DISPATCH_T(dtype, "vt_global_avgpool_fwd",
-                  hipLaunchKernelGGL(avgpool_fwd_kernel<T>, grid, dim3(kThreads), CT * epc * sizeof(unsigned long long),
+                  hipLaunchKernelGGL(avgpool_fwd_kernel<T>, grid, dim3(kThreads), CT * epc * kLdsFixBytes,
                                      (hipStream_t)stream, (const T*)x, ldx, (T*)y, ldy, HW, C, CT));
     VT_CHECK_LAUNCH("vt_global_avgpool_fwd");
     return VT_OK;
@@ -2045,7 +2059,7 @@ int vt_ese_gate_bwd(const void* dy, int32_t lddy, const void* x, int32_t ldx, co
     const int CT = pool_ct(C, epc);
     const dim3 grid(B, (C / epc + CT - 1) / CT);
     VT_DISPATCH_T(dtype, "vt_ese_gate_bwd",
-                  hipLaunchKernelGGL(ese_bwd_kernel<T>, grid, dim3(kThreads), CT * epc * sizeof(unsigned long long),
+                  hipLaunchKernelGGL(ese_bwd_kernel<T>, grid, dim3(kThreads), CT * epc * kLdsFixBytes,
                                      (hipStream_t)stream, (const T*)dy, lddy, (const T*)x, ldx, (const T*)s,
                                      lds, (T*)dx, lddx, ds, HW, C, CT, accumulate));
     VT_CHECK_LAUNCH("vt_ese_gate_bwd");

@@ -408,9 +408,7 @@ pool_finish_kernel(const float* __restrict__ scratch, T* __restrict__ pooled, in
     const long i = (long)blockIdx.x * kThreads + threadIdx.x;
     if (i >= (long)B * C) return;
     const long long* q = (const long long*)scratch;
-    const long long hi = q[2 * i], lo = q[2 * i + 1];
-    double v = (double)hi * 4096.0 + (double)lo * (1.0 / 8589934592.0);
-    if (hi >= (kStatPoison >> 2) || hi <= -(kStatPoison >> 2)) v = __longlong_as_double(0x7ff8000000000000LL);  // poisoned
+    const double v = vt_stat_decode(q[2 * i], q[2 * i + 1]);
     pooled[(i / C) * ldp + i % C] = from_float<T>((float)v * inv);
 }
 

@@ -22,7 +22,8 @@
 //     of the 4-pixel group starting at tap (e, 0) (the 4th pixel is computed and dropped: 96 columns for 72);
 //   * waves 0/1 take positions 0..31 of the step, waves 2/3 positions 32..63; even waves filter-row fragments 0..2,
 //     odd waves 3..5.  HBM-bound: 9.2 KB per step against 15-27 MFMAs per wave.
-// Partial results leave as f32 atomics into `gzx` [8 replicas][2C+16][96] and `sums` [32 replicas][2][C].
+// Partial results leave as f32 atomics into `gzx` [8 replicas][2C+16][96] and `sums` [VT_STAT_REPLICAS][2][C]
+// (fixed point, vt_common.h; `gzx` in the same fixed point when `fixed` is set).
 #include <stdlib.h>
 #include <string.h>
 
@@ -353,6 +354,16 @@ __global__ void __launch_bounds__(256, 2) stem_bwd_kernel(const SbArgs p) {
     }
 }
 
+// entry (row, col) of `gzx` summed over its replicas, in natural units: the exact integer sum of the fixed-point limbs (NaN
+// if the entry carries the marker of vt_common.h), or the f32 partial sums added in double
+__device__ __forceinline__ double gzx_entry(const float* __restrict__ gzx, int row, int col, int rows, int fixed) {
+    const long e = (long)row * kCols + col;
+    if (fixed) return vt_stat_sum<kGzxReplicas>(gzx, e, (long)rows * kCols);
+    double v = 0.0;
+    for (int r = 0; r < kGzxReplicas; ++r) v += (double)gzx[(long)r * rows * kCols + e];
+    return v;
+}
+
 // dW[n][t][c] += a_n*G - b_n*Z + d_n*X  (coef = [a | b | d] of bn_bwd_finalize), c < cin of the 8 staged channels
 __global__ void stem_bwd_combine_kernel(const float* __restrict__ gzx, const float* __restrict__ coef, int C, int cin,
                                         float* __restrict__ dw, int fixed) {
@@ -361,26 +372,8 @@ __global__ void stem_bwd_combine_kernel(const float* __restrict__ gzx, const flo
     const int c = idx % cin, t = (idx / cin) % 9, n = idx / (9 * cin);
     const int col = (t / 3) * 32 + (t % 3) * 8 + c;
     const int rows = 2 * C + 16;
-    double G = 0.0, Z = 0.0, X = 0.0;
-    if (fixed) {
-        const long long* q = (const long long*)gzx;
-        long long h[3] = {0, 0, 0}, l[3] = {0, 0, 0};
-        for (int r = 0; r < kGzxReplicas; ++r) {
-            const long base = (long)r * rows * kCols;
-            const long e[3] = {base + (long)n * kCols + col, base + (long)(C + n) * kCols + col,
-                               base + (long)(2 * C) * kCols + col};
-            for (int k = 0; k < 3; ++k) h[k] += q[2 * e[k]], l[k] += q[2 * e[k] + 1];
-        }
-        G = (double)h[0] * 4096.0 + (double)l[0] * (1.0 / 8589934592.0);
-        Z = (double)h[1] * 4096.0 + (double)l[1] * (1.0 / 8589934592.0);
-        X = (double)h[2] * 4096.0 + (double)l[2] * (1.0 / 8589934592.0);
-    } else
-    for (int r = 0; r < kGzxReplicas; ++r) {
-        const float* o = gzx + (long)r * rows * kCols;
-        G += (double)o[(long)n * kCols + col];
-        Z += (double)o[(long)(C + n) * kCols + col];
-        X += (double)o[(long)(2 * C) * kCols + col];
-    }
+    const double G = gzx_entry(gzx, n, col, rows, fixed), Z = gzx_entry(gzx, C + n, col, rows, fixed),
+                 X = gzx_entry(gzx, 2 * C, col, rows, fixed);
     const double v = (double)coef[n] * G - (double)coef[C + n] * Z + (double)coef[2 * C + n] * X;
     dw[idx] += (float)v;
 }
@@ -394,21 +387,7 @@ __global__ void stem_bwd_combine_y_kernel(const float* __restrict__ gzx, const f
     const int c = idx % cin, t = (idx / cin) % 9, n = idx / (9 * cin);
     const int col = (t / 3) * 32 + (t % 3) * 8 + c;
     const int rows = 2 * C + 16;
-    auto entry = [&](int row) -> double {
-        double v = 0.0;
-        if (fixed) {
-            const long long* q = (const long long*)gzx;
-            long long h = 0, l = 0;
-            for (int r = 0; r < kGzxReplicas; ++r) {
-                const long e = (long)r * rows * kCols + (long)row * kCols + col;
-                h += q[2 * e], l += q[2 * e + 1];
-            }
-            v = (double)h * 4096.0 + (double)l * (1.0 / 8589934592.0);
-        } else {
-            for (int r = 0; r < kGzxReplicas; ++r) v += (double)gzx[(long)r * rows * kCols + (long)row * kCols + col];
-        }
-        return v;
-    };
+    auto entry = [&](int row) -> double { return gzx_entry(gzx, row, col, rows, fixed); };
     const double G = entry(n), X = entry(2 * C);
     double Z = 0.0;
     for (int i = 0; i < 27; ++i) Z += (double)(float)w[(long)n * 72 + (i / 3) * 8 + (i % 3)] * entry(C + i);
@@ -426,25 +405,13 @@ __global__ void stem_bwd_s2_kernel(const float* __restrict__ gzx, const bf16_t* 
     for (int i = 0; i < 27; ++i) {
         const int t = i / 3, c = i - 3 * t;
         const int col = (t / 3) * 32 + (t % 3) * 8 + c;
-        double v = 0.0;
-        if (fixed) {
-            const long long* q = (const long long*)gzx;
-            long long h = 0, l = 0;
-            for (int r = 0; r < kGzxReplicas; ++r) {
-                const long e = (long)r * rows * kCols + (long)n * kCols + col;
-                h += q[2 * e], l += q[2 * e + 1];
-            }
-            v = (double)h * 4096.0 + (double)l * (1.0 / 8589934592.0);
-        } else {
-            for (int r = 0; r < kGzxReplicas; ++r) v += (double)gzx[(long)r * rows * kCols + (long)n * kCols + col];
-        }
-        dot += (double)(float)w[(long)n * 72 + t * 8 + c] * v;
+        dot += (double)(float)w[(long)n * 72 + t * 8 + c] * gzx_entry(gzx, n, col, rows, fixed);
     }
     const double s1 = vt_stat_sum(sums, n, 2L * C);
     const double s2 = (double)invstd[n] * (dot - (double)mean[n] * s1);
     // (the entry is still zero: the reduction left sum g * xhat to this kernel.  Two limbs as vt_stat_add, from a double.)
     long long* q = (long long*)sums + 2 * ((long)C + n);
-    if (!(fabs(s2) < 1.0e30)) {  // non-finite (a poisoned sum g, a diverged G): poison this entry too (vt_common.h)
+    if (!(fabs(s2) < (double)kStatLimit)) {  // NaN (a marked sum g, a marked G) or out of range: mark this entry too (vt_common.h)
         q[0] = kStatPoison, q[1] = 0;
         return;
     }

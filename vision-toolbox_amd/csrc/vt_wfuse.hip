@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(kT) wfuse_fwd_kernel(FuseIn in, const float* _
 // the fixed-point add of vt_common.h (vt_stat_add) for a double: the split is exact, so the hand-over loses nothing
 __device__ __forceinline__ void stat_add_f64(float* stats, long idx, double v) {
     unsigned long long* q = (unsigned long long*)stats + 2 * idx;
-    if (!(fabs(v) < 1.0e15)) {  // non-finite or beyond what the limbs hold: the marker vt_stat_sum turns into NaN
+    if (!(fabs(v) < (double)kStatLimit)) {  // non-finite or beyond the legitimate range: the marker vt_stat_sum turns into NaN
         atomicAdd(q, (unsigned long long)kStatPoison);
         return;
     }

@@ -20,6 +20,7 @@ VT_MAX_TAPS = 36
 VT_CONV_RELU, VT_CONV_STATS, VT_CONV_RESIDUAL, VT_CONV_AFFINE, VT_CONV_D2S, VT_CONV_NOSTORE = 1, 2, 4, 8, 16, 32
 VT_STAT_REPLICAS = 16
 # a statistics buffer is int64[VT_STAT_REPLICAS][2][C][2]: value = hi * 2^12 + lo / 2^33 (vt_amd.h)
+STAT_MARKER = 1 << 40  # what a non-finite or |v| >= 2^50 contribution adds to the hi limb instead of its value
 
 
 def stat_floats(C_: int) -> int:
@@ -40,9 +41,12 @@ def stats_buffer(C_: int, device="cuda"):
 
 
 def stats_decode(buf):
-    """statistics buffer as the kernels fill it -> float64 [2][C] (exact sum over the replicas)"""
+    """statistics buffer as the kernels fill it -> float64 [2][C] (exact sum over the replicas); NaN for an entry that
+    carries the marker of a non-finite / out-of-range contribution (|summed hi limb| >= 2^38, vt_amd.h), as the kernels decode it"""
     q = buf.sum(0)
-    return q[..., 0].double() * 4096.0 + q[..., 1].double() / float(1 << 33)
+    v = q[..., 0].double() * 4096.0 + q[..., 1].double() / float(1 << 33)
+    v[q[..., 0].abs() >= STAT_MARKER >> 2] = float("nan")
+    return v
 
 
 def stats_encode(buf, which: int, values, replica: int = 0):

@@ -560,9 +560,10 @@ class TrainStep:
         return self.arena[start : start + nbytes // N.VT_STAT_REPLICAS].view(torch.int64)
 
     def _sync_stats(self, base, off, nbytes, stream):
-        """SyncBatchNorm exchange of one layer's sums: the 32 replicas the kernels spread their atomics
-        over are folded into replica 0 on the device first (vt_stat_fold), so the collective carries 32 C bytes --
-        the algorithmic payload -- instead of the raw 1 KiB x C buffer"""
+        """SyncBatchNorm exchange of one layer's sums: the VT_STAT_REPLICAS (16) replicas the kernels spread
+        their atomics over are folded into replica 0 on the device first (vt_stat_fold), so the collective carries 32 C
+        bytes -- the algorithmic payload -- instead of the raw 512 B x C buffer.  Fold and all-reduce add the limbs as
+        integers: the marker of a non-finite contribution (vt_amd.h) on any replica or rank survives into every rank's sum"""
         start = {E.ZERO_F: self.prog.zf_off, E.ZERO_B: self.prog.zb_off}[base] + off
         C_ = nbytes // (N.VT_STAT_REPLICAS * 32)
         N.check(N.lib().vt_stat_fold(ctypes.c_void_p(self.arena.data_ptr() + start), C_, ctypes.c_void_p(stream)))
