@@ -1026,6 +1026,66 @@ int vt_augment_batch_u8(const uint8_t* raw, const int64_t* table, const int32_t*
 int vt_trivial_augment(const uint8_t* u8, const double* ta, const int32_t* params, float* out, uint32_t* workspace, int32_t B,
                        int32_t S_h, int32_t S_w, const float* mean_std, void* stream);
 
+/* ---- Input pipeline: baseline JPEG decoding (reference classifier.py:22-25, image_loader) ---------- */
+/* Two launches turn the compressed files of a batch into the packed uint8 HWC images (`raw` of vt_augment_batch):
+ *   vt_jpeg_entropy   Huffman-decodes every entropy segment into the coefficient scratch, one wave per segment;
+ *   vt_jpeg_idct_rgb  dequantises, runs libjpeg's accurate integer IDCT, the "fancy" chroma upsampling and the 16-bit
+ *                     fixed-point YCbCr -> RGB conversion, and writes the pixels.
+ * The result is the level libjpeg's default decode gives (PIL's Image.open(...).convert("RGB")), integer arithmetic throughout.
+ * As in libjpeg, a chroma plane is filtered only if it is more than two samples wide (ceil(W / 2) > 2) and replicated otherwise.
+ * The IDCT forms its sums and products modulo 2^32: jidctint on the coefficients of any real image, and a defined function (no
+ * signed overflow) of whatever a damaged stream leaves in the scratch.
+ * Scope: baseline sequential DCT (SOF0, SOF1 with 8-bit tables), 8-bit samples, Huffman coding, ONE interleaved scan of 1 or 3
+ * components, sampling 4:4:4, 4:2:2 (2x1) or 4:2:0 (2x2) with the chroma components at 1x1; any W, H >= 1; restart intervals
+ * of any length.  The HOST parses the markers, refuses everything else and builds the tables; every pointer below is a device
+ * pointer, and all geometry is read from the tables by the kernels.
+ *
+ *   data      the bytes of all files, packed.
+ *   images    int64 [B][VT_JPEG_IMG_FIELDS]:
+ *               0 H   1 W   2 components (1 or 3)   3 h_max (1 or 2)   4 v_max (1 or 2)   5 MCUs per row   6 MCU rows
+ *               7, 8, 9     quantisation table index of component 0, 1, 2
+ *               10 .. 15    Huffman table index: DC0, AC0, DC1, AC1, DC2, AC2
+ *               16 first block of the image in the coefficient scratch   17 byte offset of the image in raw
+ *               18 first row of the image in `segments`   19 its segment count   20 restart interval in MCUs (0: none)
+ *               21 .. 23    unused (0)
+ *             A gray image uses the entries of component 0 only; its MCU is one block.  An MCU of a colour image is h_max x
+ *             v_max luma blocks (rows of blocks, left to right) followed by one Cb and one Cr block.
+ *   segments  int64 [S][VT_JPEG_SEG_FIELDS] = image, first byte in data, one past the last byte, first MCU, MCU count, 0.
+ *             A segment is the entropy-coded data between two markers of the scan; the markers themselves are outside it.
+ *   qtabs     uint8 [NQ][64]: quantisation tables in NATURAL (row-major) order, de-duplicated over the batch.
+ *   hufftabs  uint8 [NH][VT_JPEG_HUFF_BYTES]: T.81's BITS (16 bytes) then HUFFVAL (256 bytes, zero padded), de-duplicated.
+ *   coef      int16 [blocks][64], 16-byte aligned: per image, component after component (Y, Cb, Cr), each a raster of
+ *             (MCUs per row x h_c) x (MCU rows x v_c) blocks; a block is 64 coefficients in natural order, the DC prediction
+ *             resolved.  vt_jpeg_scratch_bytes(blocks) is its size.  EVERY coefficient of every block that a segment names
+ *             is written (zeros included), so the scratch needs no clearing.
+ *   status    int32 [S], one entry per SEGMENT, always written: 0 clean, 1 a bit pattern that is no code of its table (or a
+ *             DC size above 15), 2 a zero run that passes coefficient 63, 3 the blocks needed bits past the end of the segment
+ *             (or past a marker inside it; such reads yield zero bits, as libjpeg pads), 4 a row of `segments` / `images`
+ *             that is out of range (nothing but the status is written for such a segment) or a Huffman table that
+ *             over-subscribes its code space (all blocks of the segment are written as zeros), 5 all blocks decoded but 8 or
+ *             more bits of the segment were left over.  On 1, 2 and 3 the block in which it happened and all later blocks of
+ *             the segment are written as zeros.  An image's status is the largest of its segments'.
+ *   raw       uint8, the output: image b is [H][W][3] at its byte offset; no alignment is needed.
+ * UNTRUSTED BYTES.  `data` may hold anything.  A byte is read only inside its segment's [begin, end), itself checked against
+ * data_bytes; the number of symbols a wave decodes is at most 64 per block and its blocks are MCU count x blocks per MCU, both
+ * known before the loop starts; block indices are re-checked against coef_blocks and pixel addresses against raw_bytes on
+ * entry, and a row that fails writes nothing.  `images` / `segments` come from the host and are checked all the same.
+ * No atomics; repeated launches are bit-identical.  The result does not depend on band_mcu_rows.
+ *   band_mcu_rows  MCU rows a workgroup of vt_jpeg_idct_rgb owns: 0 (the default, 4) or 1 .. 4.
+ *   max_mcus_x/y   the largest fields 5 / 6 of the batch (they size the grid; an image with more is cut off there).
+ * VT_ERR_INVALID: a null pointer, B / S / NQ / NH / blocks / bytes <= 0, a misaligned table (8), status (4) or coef (16),
+ * band_mcu_rows outside 0 .. 4, max_mcus_x / max_mcus_y < 1 or a grid beyond 2^31 workgroups (B > 65535). */
+#define VT_JPEG_IMG_FIELDS 24
+#define VT_JPEG_SEG_FIELDS 6
+#define VT_JPEG_HUFF_BYTES 272
+int64_t vt_jpeg_scratch_bytes(int64_t blocks);
+int vt_jpeg_entropy(const uint8_t* data, int64_t data_bytes, const int64_t* images, int32_t B, const int64_t* segments,
+                    int32_t S, const uint8_t* hufftabs, int32_t NH, int16_t* coef, int64_t coef_blocks, int32_t* status,
+                    void* stream);
+int vt_jpeg_idct_rgb(const int16_t* coef, int64_t coef_blocks, const int64_t* images, int32_t B, const uint8_t* qtabs,
+                     int32_t NQ, uint8_t* raw, int64_t raw_bytes, int32_t max_mcus_x, int32_t max_mcus_y,
+                     int32_t band_mcu_rows, void* stream);
+
 /* ---- ESEBlock gate (vovnet.py:20-28) ------------------------------------ */
 /* y = x * hardsigmoid(s[b][c]) [+ residual]; s is [B][C] (the biased 1x1 conv
  * of the pooled map, computed with vt_conv_igemm). */

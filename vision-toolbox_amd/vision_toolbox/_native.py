@@ -493,6 +493,9 @@ SYMBOLS = {
     "vt_augment_batch": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "vt_augment_batch_u8": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_trivial_augment": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "vt_jpeg_scratch_bytes": (_i64, [_i64]),
+    "vt_jpeg_entropy": (_i32, [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp]),
+    "vt_jpeg_idct_rgb": (_i32, [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _vp]),
     "vt_pack_dgrad_filter_batch":(_i32, [_vp, _i32, _vp]),
     "vt_bn_eval_coeffs_batch": (_i32, [_vp, _i32, _vp]),
     "vt_pack_dgrad_filter": (_i32, [_vp, _i32, _i32, _vp, _i32, C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp]),

@@ -13,7 +13,8 @@ float32 [B, 3, S_h, S_w] batch that TrainStep.images holds:
 
 The filter is torch's F.interpolate(mode="bilinear", antialias=True, align_corners=False) of the float crop, with no
 rounding to 8 bits in between (PIL rounds after each pass and differs by at most one 8-bit level).  MixUp / CutMix stay
-in the program's input op (trainer.py).  Not here: JPEG decoding, WebDataset / ImageFolder loaders.
+in the program's input op (trainer.py).  JPEG decoding is the last part of this file (decode_jpeg_batch: compressed bytes ->
+RaggedBatch on the device).  Not here: WebDataset / ImageFolder loaders.
 
 TrivialAugmentWide (the reference's third stage) is the optional table `ta` (sample_trivial_augment): with it the filtered
 value is rounded half up to an 8-bit level (vt_augment_batch_u8), one of the 14 ops (TA_OPS) is applied to the levels of
@@ -37,6 +38,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import sys
 from typing import Optional, Sequence, Union
 
 import torch
@@ -64,6 +66,8 @@ def f32_bits(v: float) -> int:
 class RaggedBatch:
     """Decoded images of different sizes in one uint8 buffer: `raw` (all images packed HWC), `table` int64 [B, 3] =
     (byte offset, H, W) and `sizes` = [(H, W), ...] on the host."""
+
+    status = None  # int32 [B] beside a batch that decode_jpeg_batch made (0 = a clean image), otherwise None
 
     def __init__(self, raw: torch.Tensor, table: torch.Tensor, sizes: "list[tuple[int, int]]"):
         self.raw, self.table, self.sizes = raw, table, list(sizes)
@@ -101,7 +105,10 @@ class RaggedBatch:
         """non_blocking applies to copies TO a GPU only (from the pinned buffer, ordered on the current stream); a copy to
         the host is always complete when this returns, since the host reads it without a stream to order it"""
         nb = non_blocking and torch.device(device).type == "cuda"
-        return RaggedBatch(self.raw.to(device, non_blocking=nb), self.table.to(device, non_blocking=nb), self.sizes)
+        out = RaggedBatch(self.raw.to(device, non_blocking=nb), self.table.to(device, non_blocking=nb), self.sizes)
+        if self.status is not None:
+            out.status = self.status.to(device, non_blocking=nb)
+        return out
 
 
 # ---- the sampling rules --------------------------------------------------------------------------------------------
@@ -682,3 +689,698 @@ class GPUBatchTransform:
                     v[:, ei : ei + eh, ej : ej + ew] = erase_normal(seed, b, Sh, Sw)[:, ei : ei + eh, ej : ej + ew]
             out[b].copy_(v)
         return out
+
+
+# ---- baseline JPEG decoding ---------------------------------------------------------------------------------------------
+# The reference's image_loader (classifier.py:22-25) is torchvision.io.decode_jpeg(read_file(path), device=device).  Here:
+#
+#     batch = decode_jpeg_batch(files, device="cuda")      # list of JPEG byte strings -> RaggedBatch on the device
+#     aug(batch, sample_train_params(batch.sizes, 176), out=ts.images); ts.step()
+#
+# The host reads the markers (jpeg_info), refuses what is out of scope (jpeg_check) and packs the streams and the tables of
+# vt_amd.h (JpegBatch); two launches (vt_jpeg_entropy, vt_jpeg_idct_rgb, csrc/vt_jpeg.hip) decode them.  The DEFINITION of the
+# result is jpeg_decode_levels below: libjpeg's default decode restated in integer torch (Huffman decode, the accurate integer
+# IDCT, "fancy" triangle chroma upsampling, 16-bit fixed-point YCbCr -> RGB), which the CPU tests compare with PIL level for
+# level and the GPU tests compare the kernels with.  libjpeg's source was not at hand: it is restated from its documentation
+# and from memory, and PIL arbitrates.
+JPEG_NATURAL = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21,
+                28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54,
+                47, 55, 62, 63)  # zigzag position -> natural (row-major) index
+JPEG_IMG_FIELDS, JPEG_SEG_FIELDS, JPEG_HUFF_BYTES = 24, 6, 272
+(JI_H, JI_W, JI_NC, JI_HMAX, JI_VMAX, JI_MCUS_X, JI_MCUS_Y, JI_Q0, JI_Q1, JI_Q2, JI_DC0, JI_AC0, JI_DC1, JI_AC1, JI_DC2, JI_AC2,
+ JI_COEF, JI_OUT, JI_SEG0, JI_NSEG, JI_RESTART) = range(21)
+JPEG_OK, JPEG_ERR_CODE, JPEG_ERR_RUN, JPEG_ERR_TRUNCATED, JPEG_ERR_TABLE, JPEG_ERR_TRAILING = range(6)
+JPEG_SAMPLINGS = {((1, 1),): "gray", ((1, 1), (1, 1), (1, 1)): "4:4:4", ((2, 1), (1, 1), (1, 1)): "4:2:2",
+                  ((2, 2), (1, 1), (1, 1)): "4:2:0"}
+_SOF_NAMES = {0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "differential sequential (SOF5)",
+              0xC6: "differential progressive (SOF6)", 0xC7: "differential lossless (SOF7)", 0xC9: "arithmetic coding (SOF9)",
+              0xCA: "arithmetic coding (SOF10)", 0xCB: "arithmetic coding (SOF11)", 0xCD: "arithmetic coding (SOF13)",
+              0xCE: "arithmetic coding (SOF14)", 0xCF: "arithmetic coding (SOF15)"}
+
+
+class JpegInfo:
+    """What the markers of a JPEG file say (jpeg_info).  width, height, precision, sof (the marker byte, 0xC0 ..), components =
+    [(id, h, v, quantisation table id)] (the factors of a single-component frame are given as 1 x 1, which is what they mean), qtabs = {id: (precision 8 | 16, [64 values in NATURAL order])}, huff = {(class 0 DC | 1
+    AC, id): (BITS bytes[16], HUFFVAL bytes)}, restart_interval (MCUs, 0: none), scans = number of SOS markers, scan_components
+    = [(component index, DC table id, AC table id)] and spectral = (Ss, Se, Ah, Al) of the FIRST scan, scan_offset = its first
+    entropy-coded byte, scan_end = the first byte after its entropy-coded data (the FF of the marker that ends it)."""
+
+    __slots__ = ("width", "height", "precision", "sof", "components", "qtabs", "huff", "restart_interval", "scans",
+                 "scan_components", "spectral", "scan_offset", "scan_end", "segments")
+
+    @property
+    def sampling(self) -> "Optional[str]":
+        return JPEG_SAMPLINGS.get(tuple((h, v) for _, h, v, _ in self.components))
+
+    @property
+    def mcu_geometry(self) -> "tuple[int, int, int, int]":
+        """(h_max, v_max, MCUs per row, MCU rows)"""
+        hm, vm = max(c[1] for c in self.components), max(c[2] for c in self.components)
+        return hm, vm, -(-self.width // (8 * hm)), -(-self.height // (8 * vm))
+
+
+def _jpeg_markers(data: bytes, begin: int, limit: int) -> "list[tuple[int, int]]":
+    """(index of the first FF of the marker, marker code) of every marker in data[begin:limit]: an FF followed by a byte that is
+    neither 00 (a stuffed data byte) nor FF (a fill byte; the run of FFs belongs to the marker that ends it)"""
+    a = torch.frombuffer(bytearray(data[begin:limit]), dtype=torch.uint8) if limit > begin else torch.empty(0, dtype=torch.uint8)
+    if a.numel() < 2:
+        return []
+    hit = ((a[:-1] == 0xFF) & (a[1:] != 0) & (a[1:] != 0xFF)).nonzero().flatten().tolist()
+    out = []
+    for p in hit:
+        q = p + begin
+        code = data[q + 1]
+        while q > begin and data[q - 1] == 0xFF:
+            q -= 1
+        out.append((q, code))
+    return out
+
+
+def jpeg_info(data: bytes) -> JpegInfo:
+    """Read the markers of a JPEG file; nothing is decoded.  ValueError for a file that is not a JPEG or whose header is
+    truncated or inconsistent.  What this package can decode is jpeg_check's business, not this function's."""
+    data = bytes(data)
+    n = len(data)
+    if n < 4 or data[0] != 0xFF or data[1] != 0xD8:
+        raise ValueError("not a JPEG file: no SOI marker")
+    info = JpegInfo()
+    info.qtabs, info.huff, info.restart_interval, info.scans = {}, {}, 0, 0
+    info.width = info.height = info.precision = info.sof = None
+    info.components, info.scan_components, info.segments = [], [], None
+    pos = 2
+
+    def need(k, what):
+        if pos + k > n:
+            raise ValueError(f"truncated header: the file ends inside {what}")
+
+    while True:
+        need(2, "a marker")
+        if data[pos] != 0xFF:
+            raise ValueError(f"byte {pos}: expected a marker, found {data[pos]:#04x}")
+        while pos < n and data[pos] == 0xFF:  # fill bytes
+            pos += 1
+        need(1, "a marker")
+        m = data[pos]
+        pos += 1
+        if m == 0xD9:
+            raise ValueError("truncated header: EOI before any scan")
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        need(2, f"the length of segment {m:#04x}")
+        L = (data[pos] << 8) | data[pos + 1]
+        if L < 2:
+            raise ValueError(f"segment {m:#04x} at byte {pos}: length {L}")
+        need(L, f"segment {m:#04x}")
+        seg = data[pos + 2 : pos + L]
+        if m == 0xDB:
+            i = 0
+            while i < len(seg):
+                pq, tq = seg[i] >> 4, seg[i] & 15
+                size = 128 if pq else 64
+                if pq > 1 or i + 1 + size > len(seg):
+                    raise ValueError(f"DQT at byte {pos}: malformed table")
+                vals = [(seg[i + 1 + 2 * k] << 8) | seg[i + 2 + 2 * k] for k in range(64)] if pq else list(seg[i + 1 : i + 65])
+                nat = [0] * 64
+                for k in range(64):
+                    nat[JPEG_NATURAL[k]] = vals[k]
+                info.qtabs[tq] = (16 if pq else 8, nat)
+                i += 1 + size
+        elif m == 0xC4:
+            i = 0
+            while i < len(seg):
+                if i + 17 > len(seg):
+                    raise ValueError(f"DHT at byte {pos}: malformed table")
+                tc, th = seg[i] >> 4, seg[i] & 15
+                bits = bytes(seg[i + 1 : i + 17])
+                cnt = sum(bits)
+                if tc > 1 or cnt > 256 or i + 17 + cnt > len(seg):
+                    raise ValueError(f"DHT at byte {pos}: malformed table")
+                info.huff[(tc, th)] = (bits, bytes(seg[i + 17 : i + 17 + cnt]))
+                i += 17 + cnt
+        elif m == 0xDD:
+            if len(seg) < 2:
+                raise ValueError("DRI: malformed segment")
+            info.restart_interval = (seg[0] << 8) | seg[1]
+        elif 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            if info.sof is not None:
+                raise ValueError("two frame headers")
+            if len(seg) < 6 or len(seg) < 6 + 3 * seg[5]:
+                raise ValueError("SOF: malformed segment")
+            info.sof, info.precision = m, seg[0]
+            info.height, info.width = (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4]
+            info.components = [(seg[6 + 3 * k], seg[7 + 3 * k] >> 4, seg[7 + 3 * k] & 15, seg[8 + 3 * k]) for k in range(seg[5])]
+            if len(info.components) == 1:  # a single component is never sub-sampled: its factors only scale an MCU that is one block
+                info.components = [(info.components[0][0], 1, 1, info.components[0][3])]
+        elif m == 0xDA:
+            if info.sof is None:
+                raise ValueError("SOS before the frame header")
+            ns = seg[0] if seg else 0
+            if len(seg) < 1 + 2 * ns + 3:
+                raise ValueError("SOS: malformed segment")
+            ids = [c[0] for c in info.components]
+            for k in range(ns):
+                cid = seg[1 + 2 * k]
+                if cid not in ids:
+                    raise ValueError(f"SOS: component id {cid} is not in the frame")
+                info.scan_components.append((ids.index(cid), seg[2 + 2 * k] >> 4, seg[2 + 2 * k] & 15))
+            info.spectral = (seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns] >> 4, seg[3 + 2 * ns] & 15)
+            info.scans = 1
+            info.scan_offset = pos + L
+            break
+        pos += L
+    # the entropy-coded data of the first scan: up to the first marker that is not RSTn; what follows decides `scans`
+    marks = _jpeg_markers(data, info.scan_offset, n)
+    segs, begin, info.scan_end = [], info.scan_offset, n
+    for q, code in marks:
+        if 0xD0 <= code <= 0xD7:
+            segs.append((begin, q))
+            begin = data.index(bytes([code]), q) + 1
+            continue
+        info.scan_end = q
+        for _, c in marks:  # further scans of THIS image: up to its EOI (what follows EOI -- a trailer, a second image -- is not ours)
+            if c == 0xD9:
+                break
+            info.scans += c == 0xDA
+        break
+    segs.append((begin, info.scan_end))
+    info.segments = segs
+    return info
+
+
+def jpeg_check(info: JpegInfo, index: Optional[int] = None) -> None:
+    """Raise for a file outside the scope of the decoder, naming the image and the property: NotImplementedError for a kind of
+    JPEG that exists but is not built here, ValueError for a file that is inconsistent."""
+    who = "image" if index is None else f"image {index}"
+
+    def no(what):
+        raise NotImplementedError(f"{who}: {what} is not supported (baseline Huffman JPEG, 8 bit, one interleaved scan, gray / "
+                                  f"4:4:4 / 4:2:2 / 4:2:0)")
+
+    if info.sof in _SOF_NAMES:
+        no(_SOF_NAMES[info.sof])
+    if info.precision != 8:
+        no(f"{info.precision}-bit precision")
+    if info.width < 1 or info.height < 1:
+        raise ValueError(f"{who}: size {info.width} x {info.height}")
+    if len(info.components) == 4:
+        no("4 components (CMYK / YCCK)")
+    if len(info.components) not in (1, 3):
+        no(f"{len(info.components)} components")
+    if info.sampling is None:
+        no("sampling " + ", ".join(f"{h}x{v}" for _, h, v, _ in info.components))
+    if info.scans != 1:
+        no(f"{info.scans} scans (multiple scans)")
+    if [c for c, _, _ in info.scan_components] != list(range(len(info.components))):
+        no(f"a non-interleaved scan (components {[c for c, _, _ in info.scan_components]} of {len(info.components)})")
+    if info.spectral != (0, 63, 0, 0):
+        no(f"spectral selection / successive approximation {info.spectral}")
+    for _, _, _, tq in info.components:
+        if tq not in info.qtabs:
+            raise ValueError(f"{who}: missing quantisation table {tq}")
+        if info.qtabs[tq][0] != 8:
+            no(f"16-bit quantisation table {tq}")
+    for _, td, ta in info.scan_components:
+        for key in ((0, td), (1, ta)):
+            if key not in info.huff:
+                raise ValueError(f"{who}: missing Huffman table {'DC' if key[0] == 0 else 'AC'} {key[1]}")
+
+
+def jpeg_segment_table(info: JpegInfo) -> "list[tuple[int, int, int, int]]":
+    """(first byte, one past the last byte, first MCU, MCU count) of every entropy segment of the scan.  Without DRI: one segment.
+    With an interval of Ri MCUs: ceil(MCUs / Ri) segments; if the file has fewer (damaged), the last one found takes all the
+    MCUs that are left, and further segments of the file are not used."""
+    _, _, mx, my = info.mcu_geometry
+    total, Ri = mx * my, info.restart_interval
+    if Ri <= 0:
+        return [(info.segments[0][0], info.segments[0][1], 0, total)]
+    wanted = -(-total // Ri)
+    found = info.segments[:wanted]
+    out = []
+    for k, (b, e) in enumerate(found):
+        first = k * Ri
+        out.append((b, e, first, total - first if k == len(found) - 1 else Ri))
+    return out
+
+
+def _huff_lut(bits: bytes, huffval: bytes) -> "Optional[list[int]]":
+    """16-bit lookahead -> (length << 8) | value, 0 for a pattern that is no code; None for a table that is not a prefix code
+    (the rule of vt_jpeg_huff_build)"""
+    key = (bits, huffval)
+    if key not in _HUFF_LUTS:
+        lut, code, k, valid = [0] * 65536, 0, 0, True
+        for l in range(1, 17):
+            nl = bits[l - 1]
+            if code + nl > (1 << l):
+                valid = False
+                break
+            for _ in range(nl):
+                v = huffval[k] if k < len(huffval) else 0
+                lut[code << (16 - l) : (code + 1) << (16 - l)] = [(l << 8) | v] * (1 << (16 - l))
+                code, k = code + 1, k + 1
+            code <<= 1
+        _HUFF_LUTS[key] = lut if valid and sum(bits) <= 256 else None
+    return _HUFF_LUTS[key]
+
+
+_HUFF_LUTS: dict = {}
+
+
+def _unstuff(seg: bytes) -> bytes:
+    """the data bytes of a segment: FF 00 -> FF; an FF followed by anything else (or by nothing) ends the data"""
+    out, i, n = bytearray(), 0, len(seg)
+    while True:
+        j = seg.find(b"\xff", i)
+        if j < 0:
+            out += seg[i:]
+            break
+        if j + 1 < n and seg[j + 1] == 0:
+            out += seg[i : j + 1]
+            i = j + 2
+        else:
+            out += seg[i:j]
+            break
+    return bytes(out)
+
+
+def jpeg_decode_coefficients(data: bytes, info: Optional[JpegInfo] = None, segments=None, huff=None):
+    """The entropy stage on the host, the definition vt_jpeg_entropy is held to: (coef int16 [blocks, 64], status [segments]).
+    Blocks are component after component, each a raster of (MCUs per row x h_c) x (MCU rows x v_c) blocks, coefficients in
+    natural order, DC prediction resolved.  Statuses as in vt_amd.h; from the block in which an error happens on, a segment's
+    blocks are zeros.  `segments` / `huff` replace the file's own segment table / Huffman tables (the tests damage them)."""
+    data = bytes(data)
+    if info is None:
+        info = jpeg_info(data)
+        jpeg_check(info)
+    hm, vm, mx, my = info.mcu_geometry
+    nc = len(info.components)
+    segments = jpeg_segment_table(info) if segments is None else segments
+    huff = info.huff if huff is None else huff
+    nY = mx * hm * my * vm
+    coef = torch.zeros((nY + (2 * mx * my if nc == 3 else 0), 64), dtype=torch.int16)
+    luts = []
+    for _, td, ta in info.scan_components:
+        luts.append((_huff_lut(*huff[(0, td)]), _huff_lut(*huff[(1, ta)])))
+    table_ok = all(d is not None and a is not None for d, a in luts)
+    statuses = []
+    for begin, end, m0, mc in segments:
+        if not (0 <= begin <= end <= len(data) and 0 <= m0 and 0 <= mc and m0 + mc <= mx * my):
+            statuses.append(JPEG_ERR_TABLE)
+            continue
+        if not table_ok:
+            statuses.append(JPEG_ERR_TABLE)
+            continue
+        buf = _unstuff(data[begin:end])
+        real = 8 * len(buf)
+        buf += b"\0" * 260  # zero bits past the end, as the kernel's reader supplies them (a block reads < 2048 bits)
+        bp, st, pred = 0, JPEG_OK, [0] * nc
+        rows = []
+        for mcu in range(m0, m0 + mc):
+            mcx, mcy = mcu % mx, mcu // mx
+            for c in range(nc):
+                dcl, acl = luts[c]
+                for v in range(vm if c == 0 else 1):
+                    for h in range(hm if c == 0 else 1):
+                        blk = (mcy * vm + v) * mx * hm + mcx * hm + h if c == 0 else nY + (c - 1) * mx * my + mcy * mx + mcx
+                        if st != JPEG_OK:
+                            continue
+                        vals = [0] * 64
+                        while True:  # one block
+                            e = dcl[(int.from_bytes(buf[bp >> 3 : (bp >> 3) + 3], "big") >> (8 - (bp & 7))) & 0xFFFF]
+                            if e == 0 or (e & 255) > 15:
+                                st = JPEG_ERR_CODE
+                                break
+                            bp += e >> 8
+                            s = e & 255
+                            if s:
+                                x = (int.from_bytes(buf[bp >> 3 : (bp >> 3) + 3], "big") >> (24 - (bp & 7) - s)) & ((1 << s) - 1)
+                                bp += s
+                                d = x - (1 << s) + 1 if x < (1 << (s - 1)) else x
+                                pred[c] = ((pred[c] + d + 32768) & 0xFFFF) - 32768
+                            vals[0] = pred[c]
+                            k = 1
+                            while k < 64:
+                                e = acl[(int.from_bytes(buf[bp >> 3 : (bp >> 3) + 3], "big") >> (8 - (bp & 7))) & 0xFFFF]
+                                if e == 0:
+                                    st = JPEG_ERR_CODE
+                                    break
+                                bp += e >> 8
+                                run, s = (e & 255) >> 4, e & 15
+                                if s == 0:
+                                    if run != 15:
+                                        break
+                                    if k + 15 > 63:
+                                        st = JPEG_ERR_RUN
+                                        break
+                                    k += 16
+                                    continue
+                                k += run
+                                if k > 63:
+                                    st = JPEG_ERR_RUN
+                                    break
+                                x = (int.from_bytes(buf[bp >> 3 : (bp >> 3) + 3], "big") >> (24 - (bp & 7) - s)) & ((1 << s) - 1)
+                                bp += s
+                                vals[JPEG_NATURAL[k]] = x - (1 << s) + 1 if x < (1 << (s - 1)) else x
+                                k += 1
+                            break
+                        if st == JPEG_OK and bp > real:
+                            st = JPEG_ERR_TRUNCATED
+                        if st == JPEG_OK:
+                            rows.append((blk, vals))
+        if rows:
+            coef[torch.tensor([b for b, _ in rows])] = torch.tensor([v for _, v in rows], dtype=torch.int16)
+        if st == JPEG_OK and real - bp >= 8:
+            st = JPEG_ERR_TRAILING
+        statuses.append(st)
+    return coef, statuses
+
+
+_IDCT_C = (2446, 3196, 4433, 6270, 7373, 9633, 12299, 15137, 16069, 16819, 20995, 25172)
+
+
+def _idct_1d(d, shift: int):
+    """one pass of libjpeg's accurate integer IDCT (jidctint) on eight int64 tensors"""
+    c0298, c0390, c0541, c0765, c0899, c1175, c1501, c1847, c1961, c2053, c2562, c3072 = _IDCT_C
+    z2, z3 = d[2], d[6]
+    z1 = (z2 + z3) * c0541
+    tmp2, tmp3 = z1 - z3 * c1847, z1 + z2 * c0765
+    z2, z3 = d[0], d[4]
+    tmp0, tmp1 = (z2 + z3) << 13, (z2 - z3) << 13
+    tmp10, tmp13, tmp11, tmp12 = tmp0 + tmp3, tmp0 - tmp3, tmp1 + tmp2, tmp1 - tmp2
+    tmp0, tmp1, tmp2, tmp3 = d[7], d[5], d[3], d[1]
+    z1, z2, z3, z4 = tmp0 + tmp3, tmp1 + tmp2, tmp0 + tmp2, tmp1 + tmp3
+    z5 = (z3 + z4) * c1175
+    tmp0, tmp1, tmp2, tmp3 = tmp0 * c0298, tmp1 * c2053, tmp2 * c3072, tmp3 * c1501
+    z1, z2, z3, z4 = -z1 * c0899, -z2 * c2562, -z3 * c1961 + z5, -z4 * c0390 + z5
+    tmp0, tmp1, tmp2, tmp3 = tmp0 + z1 + z3, tmp1 + z2 + z4, tmp2 + z2 + z3, tmp3 + z1 + z4
+    r = 1 << (shift - 1)
+
+    def descale(v):  # the sum as a signed 32-bit value (nothing wraps for a real image; see jpeg_idct_blocks), then the shift
+        return ((((v + r) + 2147483648) & 0xFFFFFFFF) - 2147483648) >> shift
+
+    return [descale(tmp10 + tmp3), descale(tmp11 + tmp2), descale(tmp12 + tmp1), descale(tmp13 + tmp0),
+            descale(tmp13 - tmp0), descale(tmp12 - tmp1), descale(tmp11 - tmp2), descale(tmp10 - tmp3)]
+
+
+def jpeg_idct_blocks(coef: torch.Tensor, q: "Sequence[int]") -> torch.Tensor:
+    """int16 [N, 64] coefficients (natural order) and a quantisation table (natural order) -> int64 [N, 8, 8] samples 0 .. 255:
+    dequantise, columns (CONST_BITS 13, PASS1_BITS 2), rows (descale by 18), + 128, clamp.  The sums of a pass are exact in
+    int64 and are reduced to signed 32 bits before the pass's shift: for the coefficients of a real image nothing changes (libjpeg's
+    32-bit arithmetic never overflows on them), and for the garbage of a damaged stream (any int16 times a table entry) the result
+    is what the kernel's modulo-2^32 arithmetic gives, bit for bit, instead of an overflow."""
+    d = coef.to(torch.int64).view(-1, 8, 8) * torch.tensor(list(q), dtype=torch.int64).view(1, 8, 8)
+    ws = torch.stack(_idct_1d([d[:, k, :] for k in range(8)], 11), dim=1)
+    out = torch.stack(_idct_1d([ws[:, :, k] for k in range(8)], 18), dim=2)
+    return (out + 128).clamp_(0, 255)
+
+
+def _jpeg_plane(samples: torch.Tensor, bh: int, bw: int) -> torch.Tensor:
+    return samples.view(bh, bw, 8, 8).permute(0, 2, 1, 3).reshape(bh * 8, bw * 8)
+
+
+def _near_far(n_out: int, n_in: int) -> "tuple[torch.Tensor, torch.Tensor, torch.Tensor]":
+    """for outputs 0 .. n_out - 1 of a 2x triangle filter over n_in samples: near index, far index (clamped: edge
+    replication), and whether the output is the odd one of its pair"""
+    o = torch.arange(n_out, dtype=torch.int64)
+    near = o >> 1
+    odd = (o & 1).bool()
+    far = (near + torch.where(odd, 1, -1)).clamp_(0, n_in - 1)
+    return near, far, odd
+
+
+def jpeg_pixels(coef: torch.Tensor, info: JpegInfo) -> torch.Tensor:
+    """coefficients (jpeg_decode_coefficients' layout) -> uint8 [H, W, 3]: IDCT, fancy upsampling, colour conversion"""
+    hm, vm, mx, my = info.mcu_geometry
+    H, W, nc = info.height, info.width, len(info.components)
+    nY = mx * hm * my * vm
+    y = _jpeg_plane(jpeg_idct_blocks(coef[:nY], info.qtabs[info.components[0][3]][1]), my * vm, mx * hm)[:H, :W]
+    if nc == 1:
+        return y.to(torch.uint8)[..., None].expand(H, W, 3).contiguous()
+    ch, cw = -(-H // vm), -(-W // hm)
+    cc = []
+    for c in (1, 2):
+        blocks = coef[nY + (c - 1) * mx * my : nY + c * mx * my]
+        p = _jpeg_plane(jpeg_idct_blocks(blocks, info.qtabs[info.components[c][3]][1]), my, mx)[:ch, :cw]
+        if hm == 2 and cw <= 2:
+            # libjpeg takes the triangle ("fancy") upsamplers only for a component MORE than two samples wide
+            # (downsampled_width > 2); a chroma plane of one or two columns is replicated, in both directions
+            p = p[(torch.arange(H) // vm)][:, torch.arange(W) // 2]
+        elif hm == 2:
+            xn, xf, xodd = _near_far(W, cw)
+            if vm == 2:  # h2v2: 9-3-3-1, + 8 on the even and + 7 on the odd output column
+                yn, yf, _ = _near_far(H, ch)
+                a = 3 * p[yn] + p[yf]
+                p = (3 * a[:, xn] + a[:, xf] + torch.where(xodd, 7, 8)[None, :]) >> 4
+            else:        # h2v1: 3 near + far, + 1 on the even and + 2 on the odd output column
+                p = (3 * p[:, xn] + p[:, xf] + torch.where(xodd, 2, 1)[None, :]) >> 2
+        cc.append(p - 128)
+    cb, cr = cc
+    r = y + ((91881 * cr + 32768) >> 16)
+    g = y + ((-22554 * cb - 46802 * cr + 32768) >> 16)
+    b = y + ((116130 * cb + 32768) >> 16)
+    return torch.stack([r, g, b], dim=2).clamp_(0, 255).to(torch.uint8)
+
+
+def jpeg_decode_levels(data: bytes, return_status: bool = False):
+    """The host stage: a baseline JPEG file -> uint8 [H, W, 3], libjpeg's default decode in integer torch (the definition the
+    kernels are held to; PIL's Image.open(...).convert("RGB") level for level).  Out-of-scope files raise as jpeg_check says.
+    return_status: also the image's status (the largest of its segments' statuses, 0 = clean)."""
+    info = jpeg_info(data)
+    jpeg_check(info)
+    coef, st = jpeg_decode_coefficients(data, info)
+    px = jpeg_pixels(coef, info)
+    return (px, max(st)) if return_status else px
+
+
+class JpegBatch:
+    """The compressed streams of a batch packed for the device, with the tables of vt_amd.h (all on the host, pinned where there
+    is a GPU): data uint8, images int64 [B, 24], segments int64 [S, 6], qtabs uint8 [NQ, 64], hufftabs uint8 [NH, 272]
+    (de-duplicated over the batch), and on the host sizes = [(H, W)], infos, blocks (of the coefficient scratch), raw_bytes,
+    max_mcus_x, max_mcus_y.  Built by from_bytes, which refuses out-of-scope files by image index before anything is launched."""
+
+    @classmethod
+    def from_bytes(cls, files: "Sequence[bytes]", out_offsets: "Optional[Sequence[int]]" = None,
+                   indices: "Optional[Sequence[int]]" = None, infos: "Optional[Sequence[JpegInfo]]" = None,
+                   alloc=None) -> "JpegBatch":
+        """alloc(name, shape, dtype) -> an uninitialised host tensor for `data`, `images`, `segments`, `qtabs`, `hufftabs`
+        (GPUJpegDecoder hands out views of the pinned staging buffers it keeps); None: fresh tensors, pinned where there is a GPU"""
+        if len(files) == 0:
+            raise ValueError("JpegBatch.from_bytes: no files")
+        self = cls()
+        self.infos, self.sizes = [], []
+        qkeys, hkeys, img_rows, seg_rows, starts = {}, {}, [], [], []
+        total, blocks, out = 0, 0, 0
+        for i, f in enumerate(files):
+            idx = i if indices is None else indices[i]
+            if infos is not None:
+                info = infos[i]
+            else:
+                try:
+                    info = jpeg_info(f)
+                except ValueError as e:
+                    raise ValueError(f"image {idx}: {e}") from None
+                jpeg_check(info, idx)
+            hm, vm, mx, my = info.mcu_geometry
+            nc = len(info.components)
+            row = [0] * JPEG_IMG_FIELDS
+            row[JI_H], row[JI_W], row[JI_NC], row[JI_HMAX], row[JI_VMAX], row[JI_MCUS_X], row[JI_MCUS_Y] = (
+                info.height, info.width, nc, hm, vm, mx, my)
+            for c, (_, _, _, tq) in enumerate(info.components):
+                row[JI_Q0 + c] = qkeys.setdefault(bytes(info.qtabs[tq][1]), len(qkeys))
+            for c, (_, td, ta) in enumerate(info.scan_components):
+                for k, key in enumerate(((0, td), (1, ta))):
+                    bits, vals = info.huff[key]
+                    row[JI_DC0 + 2 * c + k] = hkeys.setdefault(bits + vals + b"\0" * (256 - len(vals)), len(hkeys))
+            row[JI_COEF] = blocks
+            row[JI_OUT] = out if out_offsets is None else int(out_offsets[i])
+            segs = jpeg_segment_table(info)
+            row[JI_SEG0], row[JI_NSEG], row[JI_RESTART] = len(seg_rows), len(segs), info.restart_interval
+            for b, e, m0, mc in segs:
+                seg_rows.append([i, total + b, total + e, m0, mc, 0])
+            img_rows.append(row)
+            starts.append(total)
+            self.infos.append(info)
+            self.sizes.append((info.height, info.width))
+            blocks += mx * my * (hm * vm + (2 if nc == 3 else 0))
+            out += info.height * info.width * 3
+            total += (len(f) + 3) & ~3
+        if alloc is None:
+            pin = torch.cuda.is_available()
+
+            def alloc(name, shape, dtype):
+                return torch.empty(shape, dtype=dtype, pin_memory=pin)
+
+        self.data = alloc("data", (total,), torch.uint8)  # (the up to 3 bytes between two files belong to no segment: never read)
+        for f, s in zip(files, starts):
+            self.data[s : s + len(f)] = torch.frombuffer(bytearray(f), dtype=torch.uint8)
+        for name, rows, dtype in (("images", img_rows, torch.int64), ("segments", seg_rows, torch.int64),
+                                  ("qtabs", [list(k) for k in qkeys], torch.uint8), ("hufftabs", [list(k) for k in hkeys], torch.uint8)):
+            t = torch.tensor(rows, dtype=dtype)
+            setattr(self, name, alloc(name, tuple(t.shape), dtype).copy_(t))
+        self.starts, self.blocks, self.raw_bytes = starts, blocks, out
+        self.max_mcus_x = max(r[JI_MCUS_X] for r in img_rows)
+        self.max_mcus_y = max(r[JI_MCUS_Y] for r in img_rows)
+        return self
+
+    def __len__(self) -> int:
+        return len(self.sizes)
+
+
+class GPUJpegDecoder:
+    """files -> RaggedBatch.  decoder(files, device="cuda", on_unsupported="raise"): on a CUDA device the two launches of
+    csrc/vt_jpeg.hip; on the CPU the host stage (jpeg_decode_levels), image by image.  There is no fallback on the GPU: a file
+    the kernels cannot decode raises (by image index and property) before anything is launched, or with
+    on_unsupported="host" is decoded by PIL, if PIL is importable, and packed beside the others.  The batch carries `status`,
+    int32 [B] on the batch's device: 0 for a clean image, otherwise the largest status of its entropy segments (vt_amd.h).
+    band_mcu_rows is passed on to vt_jpeg_idct_rgb (0: its default).
+
+    The object OWNS its buffers and reuses them from call to call, growing them when a batch needs more: the coefficient scratch,
+    one per (device, stream) -- two streams never share one, and on a stream the next call's kernels are ordered behind the last
+    call's -- and per device the pinned host staging buffers of everything that is uploaded (the packed streams, the four tables,
+    the batch's (offset, H, W) table).  The uploads are asynchronous, so before the staging buffers are written again the object
+    waits on an event recorded behind the previous call's uploads.  The host side keeps no lock: use one decoder per thread
+    (decode_jpeg_batch shares ONE instance, for one thread)."""
+
+    def __init__(self, band_mcu_rows: int = 0):
+        self.band_mcu_rows = int(band_mcu_rows)
+        self._scratch = {}
+        self._staging = {}  # device -> {name: pinned tensor}
+        self._uploaded = {}  # device -> event behind the last call's uploads
+
+    def _stage(self, device, name, shape, dtype) -> torch.Tensor:
+        """an uninitialised view of the device's pinned staging buffer `name`, grown (by at least half) when too small"""
+        numel = 1
+        for n in shape:
+            numel *= int(n)
+        pool = self._staging.setdefault(str(device), {})
+        buf = pool.get(name)
+        if buf is None or buf.dtype != dtype or buf.numel() < numel:
+            grown = max(numel, 0 if buf is None or buf.dtype != dtype else buf.numel() * 3 // 2, 1)
+            buf = pool[name] = torch.empty(grown, dtype=dtype, pin_memory=True)
+        return buf[:numel].view(shape)
+
+    def _scratch_on(self, device, blocks: int) -> torch.Tensor:
+        key = (str(device), int(torch.cuda.current_stream(device).cuda_stream))
+        need = int(N.lib().vt_jpeg_scratch_bytes(blocks))
+        if key not in self._scratch or self._scratch[key].numel() * 2 < need:
+            self._scratch[key] = torch.empty(need // 2, dtype=torch.int16, device=device)
+        return self._scratch[key]
+
+    @staticmethod
+    def _split(files, on_unsupported):
+        """(infos or None per file, PIL-decoded uint8 HWC tensor or None per file)"""
+        if on_unsupported not in ("raise", "host"):
+            raise ValueError(f"on_unsupported={on_unsupported!r}: 'raise' or 'host'")
+        if len(files) == 0:
+            raise ValueError("decode_jpeg_batch: no files")
+        infos, hosted = [], []
+        for i, f in enumerate(files):
+            try:
+                try:
+                    info = jpeg_info(f)
+                except ValueError as e:
+                    raise ValueError(f"image {i}: {e}") from None
+                jpeg_check(info, i)
+                infos.append(info)
+                hosted.append(None)
+            except (ValueError, NotImplementedError):
+                if on_unsupported == "raise":
+                    raise
+                refusal = sys.exc_info()[1]
+                try:
+                    import io
+
+                    import numpy as np
+                    from PIL import Image
+                except ImportError:
+                    raise refusal from None  # no PIL to hand the file to: the refusal itself, which names image and property
+                infos.append(None)
+                hosted.append(torch.from_numpy(np.array(Image.open(io.BytesIO(bytes(f))).convert("RGB"))))
+        return infos, hosted
+
+    def __call__(self, files: "Sequence[bytes]", device="cuda", on_unsupported: str = "raise") -> RaggedBatch:
+        dev = torch.device(device)
+        infos, hosted = self._split(files, on_unsupported)
+        B = len(files)
+        if dev.type != "cuda":
+            images, status = [], []
+            for f, info, h in zip(files, infos, hosted):
+                if h is not None:
+                    images.append(h)
+                    status.append(0)
+                else:
+                    coef, st = jpeg_decode_coefficients(f, info)
+                    images.append(jpeg_pixels(coef, info))
+                    status.append(max(st))
+            batch = RaggedBatch.from_images(images)
+            batch.status = torch.tensor(status, dtype=torch.int32)
+            return batch
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        sizes = [(i.height, i.width) if i is not None else (int(h.shape[0]), int(h.shape[1])) for i, h in zip(infos, hosted)]
+        offsets, total = [], 0
+        for H, W in sizes:
+            offsets.append(total)
+            total += H * W * 3
+        if str(dev) in self._uploaded:  # the staging buffers may still be the source of the last call's uploads
+            self._uploaded.pop(str(dev)).synchronize()
+
+        def stage(name, shape, dtype):
+            return self._stage(dev, name, shape, dtype)
+
+        table = stage("table", (B, 3), torch.int64).copy_(torch.tensor([[o, H, W] for o, (H, W) in zip(offsets, sizes)], dtype=torch.int64))
+        raw = torch.empty(total, dtype=torch.uint8, device=dev)
+        status = torch.zeros(B, dtype=torch.int32, device=dev)
+        on_dev = [i for i in range(B) if infos[i] is not None]
+        with torch.cuda.device(dev):
+            if on_dev:
+                jb = JpegBatch.from_bytes([files[i] for i in on_dev], [offsets[i] for i in on_dev], on_dev, [infos[i] for i in on_dev],
+                                          alloc=stage)
+                seg_status = self.run(jb, raw, dev)
+                which = stage("which", (len(on_dev),), torch.int64).copy_(torch.tensor(on_dev, dtype=torch.int64))
+                seg_img = which.to(dev, non_blocking=True)[jb.segments[:, 0].to(dev, non_blocking=True)]
+                status.scatter_reduce_(0, seg_img, seg_status, "amax", include_self=True)
+            for i, h in enumerate(hosted):
+                if h is not None:
+                    raw[offsets[i] : offsets[i] + h.numel()].copy_(h.reshape(-1))
+            batch = RaggedBatch(raw, table.to(dev, non_blocking=True), sizes)
+            self._uploaded[str(dev)] = torch.cuda.Event()
+            self._uploaded[str(dev)].record()
+        batch.status = status
+        return batch
+
+    def run(self, jb: JpegBatch, raw: torch.Tensor, dev, coef: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the two launches for a packed batch into `raw` (uint8 on dev, jb's output offsets); returns the per-SEGMENT status,
+        int32 [S] on dev.  `coef`: a scratch of the caller's (int16, at least jb.blocks * 64 elements) instead of the object's."""
+        stream = int(torch.cuda.current_stream().cuda_stream)
+        data, images, segments, qtabs, hufftabs = (t.to(dev, non_blocking=True)
+                                                   for t in (jb.data, jb.images, jb.segments, jb.qtabs, jb.hufftabs))
+        if coef is None:
+            coef = self._scratch_on(dev, jb.blocks)
+        seg_status = torch.empty(segments.shape[0], dtype=torch.int32, device=dev)
+        lib = N.lib()
+        N.check(lib.vt_jpeg_entropy(C.c_void_p(data.data_ptr()), data.numel(), C.c_void_p(images.data_ptr()), len(jb),
+                                    C.c_void_p(segments.data_ptr()), segments.shape[0], C.c_void_p(hufftabs.data_ptr()),
+                                    hufftabs.shape[0], C.c_void_p(coef.data_ptr()), jb.blocks, C.c_void_p(seg_status.data_ptr()),
+                                    C.c_void_p(stream)))
+        N.check(lib.vt_jpeg_idct_rgb(C.c_void_p(coef.data_ptr()), jb.blocks, C.c_void_p(images.data_ptr()), len(jb),
+                                     C.c_void_p(qtabs.data_ptr()), qtabs.shape[0], C.c_void_p(raw.data_ptr()), raw.numel(),
+                                     jb.max_mcus_x, jb.max_mcus_y, self.band_mcu_rows, C.c_void_p(stream)))
+        return seg_status
+
+
+_DEFAULT_JPEG_DECODER = GPUJpegDecoder()
+
+
+def decode_jpeg_batch(files: "Sequence[bytes]", device="cpu", on_unsupported: str = "raise") -> RaggedBatch:
+    """A list of JPEG byte strings -> RaggedBatch on `device` (raw, table, sizes as RaggedBatch.from_images of the decoded
+    images gives them, plus status int32 [B]).  GPUJpegDecoder says what runs where; this is a shared instance of it."""
+    return _DEFAULT_JPEG_DECODER(files, device, on_unsupported)
+
+
+def image_loader(path, device="cpu") -> torch.Tensor:
+    """the reference's image_loader (classifier.py:22-25): a JPEG file -> uint8 [3, H, W] on `device`"""
+    with open(path, "rb") as f:
+        data = f.read()
+    batch = decode_jpeg_batch([data], device)
+    H, W = batch.sizes[0]
+    return batch.raw.view(H, W, 3).permute(2, 0, 1).contiguous()
