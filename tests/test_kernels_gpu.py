@@ -214,12 +214,15 @@ def test_conv_filter_gradient(dtype, case):
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=DNAME.get)
-@pytest.mark.parametrize("shape", [(2, 24, 5, 7), (3, 160, 4, 4), (2, 8, 16, 16), (6, 256, 7, 7), (5, 512, 5, 3), (3, 320, 9, 9)],
+@pytest.mark.parametrize("shape", [(2, 24, 5, 7), (3, 160, 4, 4), (2, 8, 16, 16), (6, 256, 7, 7), (5, 512, 5, 3), (3, 320, 9, 9),
+                                   (2, 1032, 5, 5)],
                          ids=str)
 def test_batchnorm_relu_forward_backward_chain(dtype, shape):
     """stats -> finalize -> apply -> bwd reduce -> bwd finalize -> bwd apply vs autograd of
     F.batch_norm + relu (+ residual), incl. running statistics (components.py:36-44).  (256 / 512 / 320 channels on small
-    maps: the backward reduction splits the channels over blockIdx.y there, round 4.)"""
+    maps: the backward reduction splits the channels over blockIdx.y there, round 4.  1032 channels: 258 chunks per row in
+    f32, more than a block has threads -- the column loop of the reduction takes a second pass with two live columns; 129
+    threads along the row in bf16.)"""
     B, Cc, H, W = shape
     M = B * H * W
     z0 = rounded(filler.tensor(f"z{shape}", shape) * 1.5 + 0.3, dtype)
@@ -683,7 +686,8 @@ def test_filter_repack_batch_equals_the_single_launches():
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=DNAME.get)
-@pytest.mark.parametrize("shape", [(2, 16, 12, 10), (3, 24, 7, 9), (1, 64, 56, 56), (2, 8, 2, 2), (2, 40, 15, 16)],
+@pytest.mark.parametrize("shape", [(2, 16, 12, 10), (3, 24, 7, 9), (1, 64, 56, 56), (2, 8, 2, 2), (2, 40, 15, 16),
+                                   (1, 256, 4, 4)],  # (256 channels in f32: 64 threads along the row, no in-wave fold)
                          ids=lambda s: "x".join(map(str, s)))
 @pytest.mark.parametrize("with_res", [False, True], ids=["plain", "residual"])
 def test_bn_apply_fused_with_the_max_pool_and_its_backward(dtype, shape, with_res):

@@ -144,4 +144,28 @@ __device__ __forceinline__ VtFinBwdPre vt_fin_bwd_pre(const VtFinBwd& f, int c) 
     if (f.dbeta) p.db = f.dbeta[c];
     return p;
 }
+
+// ---- the prologue of a pass that finalizes for itself ----------------------------------------------------------------------
+// The workgroup finalizes the Cg (<= blockDim.x / 2) channels from cg0 on into its LDS coefficient rows (indexed c - cg0); the
+// workgroups of row block 0 (blockIdx.x == 0) also store them, with the running statistics / d(gamma), d(beta), for the
+// later passes.  Every thread of the block calls it; the rows are readable when it returns (barrier inside).
+__device__ __forceinline__ void vt_fin_fwd_to_lds(const VtFinFwd& f, int cg0, int Cg, float* s_sc, float* s_sf) {
+    vt_pair_sums<false>(f.stats, f.C, cg0, cg0 + Cg, [&](int c) { return vt_fin_fwd_pre(f, c); },
+                        [&](int c, double s, double ss, const VtFinFwdPre& p) {
+                            float sc, sf;
+                            vt_fin_fwd_channel(f, c, s, ss, p.g, p.b, p.rm, p.rv, sc, sf, blockIdx.x == 0);
+                            s_sc[c - cg0] = sc, s_sf[c - cg0] = sf;
+                        });
+    __syncthreads();
+}
+// (s_a, s_b, s_d: the coefficients of dz = a*g - b*z + d)
+__device__ __forceinline__ void vt_fin_bwd_to_lds(const VtFinBwd& f, int cg0, int Cg, float* s_a, float* s_b, float* s_d) {
+    vt_pair_sums<false>(f.sums, f.C, cg0, cg0 + Cg, [&](int c) { return vt_fin_bwd_pre(f, c); },
+                        [&](int c, double s1, double s2, const VtFinBwdPre& p) {
+                            float b, d;
+                            vt_fin_bwd_channel(f, c, s1, s2, p.a, p.mu, p.istd, p.dg, p.db, b, d, blockIdx.x == 0);
+                            s_a[c - cg0] = p.a, s_b[c - cg0] = b, s_d[c - cg0] = d;
+                        });
+    __syncthreads();
+}
 #endif

@@ -98,30 +98,58 @@ __global__ void __launch_bounds__(256) bn_eval_coeffs_batch_kernel(const BnEvalB
     if (it.invstd) it.invstd[c] = istd;
 }
 
-// (the activation codes of the `relu` argument, act_fwd / act_grad: vt_act.h)
-// y = [relu](z*scale + shift) [+ residual]
 // ---------------------------------------------------------------------------------
-template <typename T, bool kRes, bool GEN = false>
+// Finalize INSIDE the consuming launch (round 6).  The 134 single-workgroup finalize launches of a CSPDarknet-53 step sit on
+// the critical path between a producer of statistics and the streaming pass that needs the coefficients: skipping them
+// (diagnostic build) shortens the 19.8 ms step by 1.17 ms, 9 - 13 us each.  Any hand-off INSIDE a launch -- first workgroups
+// finalize and publish, the others poll (the first form of these kernels: +2.3 ms per step); the producer's last workgroup
+// finalizes behind a ticket (NOTEBOOK R6.10: +-0, removed) -- costs the dependent memory-side round trips it is made of, as much as
+// the launch boundary it replaces.  Here nothing is handed over: the sums are complete when the streaming launch starts, so
+// EVERY workgroup finalizes the (at most 128) channels of its own channel group for itself -- a thread per (channel, sum),
+// its 16 replicas x 2 limbs in one round of plain loads (64 KB per workgroup, L2 hits after the first workgroup of an XCD),
+// the arithmetic of bn_finalize_kernel / bn_bwd_finalize_kernel bit for bit (vt_fin_fwd_to_lds / vt_fin_bwd_to_lds,
+// vt_bn_fin.h) -- and keeps the coefficients in LDS; the workgroups of row block 0 also store them (and the running
+// statistics, d(gamma), d(beta)) for the later passes.  The grid is cut for ~1536 workgroups instead of 4096, so that the
+// redundant reads stay small beside the tensor traffic (step: 1024 -> 19.50, 1536 -> 19.47, 3072 -> 19.59, 4096 -> 19.81 ms).
+// These are the kFin instantiations of bn_act_apply_kernel and bn_bwd_apply_kernel: grid (row blocks, channel groups of Cg
+// channels; kFinCg, fin_group: vt_rowmap.h), the coefficients come from the workgroup's LDS rows instead of global memory.
+// ---------------------------------------------------------------------------------
+// (the activation codes of the `relu` argument, act_fwd / act_grad: vt_act.h)
+// y = [relu](z*scale + shift) [+ residual]; !kFin: scale / shift may be NULL (1 / 0) and `f` is unused
+// ---------------------------------------------------------------------------------
+template <typename T, bool kRes, bool GEN = false, bool kFin = false>
 __global__ void __launch_bounds__(kThreads)
-bn_act_apply_kernel(const T* __restrict__ z, int ldz, const float* __restrict__ scale,
+bn_act_apply_kernel(const VtFinFwd f, const T* __restrict__ z, int ldz, const float* __restrict__ scale,
                     const float* __restrict__ shift, const T* __restrict__ res, int ldr, T* __restrict__ y,
-                    int ldy, long M, RowMap rm, int relu) {
+                    int ldy, long M, RowMap rm, int relu, int Cg) {
     constexpr int EPC = VecIO<T>::EPC;
+    __shared__ float s_sc[kFinCg], s_sf[kFinCg];
     const int t = threadIdx.x;
+    if constexpr (kFin) {
+        const int cg0 = blockIdx.y * Cg;
+        vt_fin_fwd_to_lds(f, cg0, Cg, s_sc, s_sf);
+        z += cg0, y += cg0;
+        if (kRes) res += cg0;
+    }
     const int r = t / rm.CT;
     if (r >= rm.RT) return;
     const long row0 = (long)(rm.rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * rm.RT * rm.iters + r;
     for (int col = t % rm.CT; col < rm.CPR; col += rm.CT) {
         float sc[EPC], sf[EPC];
+        if constexpr (kFin) {
 #pragma unroll
-        for (int e = 0; e < EPC; ++e) sc[e] = 1.f, sf[e] = 0.f;
-        if (scale) {
+            for (int e = 0; e < EPC; ++e) sc[e] = s_sc[col * EPC + e], sf[e] = s_sf[col * EPC + e];
+        } else {
 #pragma unroll
-            for (int e = 0; e < EPC; ++e) sc[e] = scale[col * EPC + e];
-        }
-        if (shift) {
+            for (int e = 0; e < EPC; ++e) sc[e] = 1.f, sf[e] = 0.f;
+            if (scale) {
 #pragma unroll
-            for (int e = 0; e < EPC; ++e) sf[e] = shift[col * EPC + e];
+                for (int e = 0; e < EPC; ++e) sc[e] = scale[col * EPC + e];
+            }
+            if (shift) {
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) sf[e] = shift[col * EPC + e];
+            }
         }
         const T* pz = z + row0 * ldz + col * EPC;
         const T* pr = kRes ? res + row0 * ldr + col * EPC : nullptr;
@@ -178,7 +206,7 @@ bn_act_apply_kernel(const T* __restrict__ z, int ldz, const float* __restrict__ 
 // da <= a, db <= b -- four pooled gradients + arg-max words serve four pixels (a per-pixel gather loads four per pixel and
 // measured SLOWER than the separate pool backward: bn_bwd_reduce 1.69 -> 2.19 ms, bn_bwd_apply 2.43 -> 3.09 ms on
 // VoVNet-39).  d(y) of a pixel = sum of the windows whose arg-max tap it is, rounded where the unfused pool backward
-// stores it.  APPLY: dz = a*g - b*z + d; else the reduction sum g, sum g*(z - mean) (folded as in bn_bwd_reduce_kernel).
+// stores it.  APPLY: dz = a*g - b*z + d; else the reduction sum g, sum g*(z - mean) (row lanes: rowlane_fold, vt_rowmap.h).
 template <typename T, bool APPLY>
 __global__ void __launch_bounds__(kThreads)
 bn_bwd_pool_kernel(const T* __restrict__ dp, int lddp, const uint8_t* __restrict__ amax, const T* __restrict__ z, int ldz,
@@ -186,17 +214,17 @@ bn_bwd_pool_kernel(const T* __restrict__ dp, int lddp, const uint8_t* __restrict
                    const float* __restrict__ invstd, T* __restrict__ dz, int lddz, int H, int W, int Ho, int Wo, int C, long Mo,
                    RowMap rm, int relu, float* __restrict__ sums) {
     constexpr int EPC = VecIO<T>::EPC;
-    extern __shared__ __attribute__((aligned(16))) float sred[];
+    extern __shared__ __attribute__((aligned(16))) float sred[];  // (!APPLY) rowlane_fold_bytes(2, CT, RT, EPC)
     const int t = threadIdx.x;
     const int r = t / rm.CT;
     const int tc = t % rm.CT;
-    const int Wc = rm.CT * EPC;
     const long row0 = (long)blockIdx.x * rm.RT * rm.iters + r;
     const int rep = blockIdx.x % kStatReplicas;
     for (int cbase = 0; cbase < rm.CPR; cbase += rm.CT) {
         const int col = cbase + tc;
         const bool active = (r < rm.RT) && (col < rm.CPR);
-        float s1[EPC], s2[EPC];
+        float s[2][EPC];
+        float(&s1)[EPC] = s[0], (&s2)[EPC] = s[1];
 #pragma unroll
         for (int e = 0; e < EPC; ++e) s1[e] = s2[e] = 0.f;
         if (active) {
@@ -281,43 +309,12 @@ bn_bwd_pool_kernel(const T* __restrict__ dp, int lddp, const uint8_t* __restrict
             }
         }
         if constexpr (!APPLY) {
-            // fold of the row lanes: as bn_bwd_reduce_kernel (in-wave shuffles where CT is a power of two below 64)
-            const bool inwave = rm.CT < 64 && (rm.CT & (rm.CT - 1)) == 0;
-            int rows_l = rm.RT, r_l = r;
-            if (inwave) {
-                for (int off = rm.CT; off < 64; off <<= 1) {
-#pragma unroll
-                    for (int e = 0; e < EPC; ++e) {
-                        s1[e] += __shfl_xor(s1[e], off, 64);
-                        s2[e] += __shfl_xor(s2[e], off, 64);
-                    }
-                }
-                rows_l = kThreads / 64;
-                r_l = (t & 63) < rm.CT ? (t >> 6) : -1;
-            } else if (r >= rm.RT) {
-                r_l = -1;
-            }
-            if (r_l >= 0) {
-                float4* d1 = (float4*)(sred + ((long)(r_l * 2 + 0) * Wc + tc * EPC));
-                float4* d2 = (float4*)(sred + ((long)(r_l * 2 + 1) * Wc + tc * EPC));
-#pragma unroll
-                for (int q = 0; q < EPC / 4; ++q) {
-                    d1[q] = make_float4(s1[4 * q], s1[4 * q + 1], s1[4 * q + 2], s1[4 * q + 3]);
-                    d2[q] = make_float4(s2[4 * q], s2[4 * q + 1], s2[4 * q + 2], s2[4 * q + 3]);
-                }
-            }
-            __syncthreads();
-            for (int i = t; i < 2 * Wc; i += kThreads) {
-                const int which = i / Wc, lc = i % Wc;
+            rowlane_fold(sred, s, rm.CT, rm.RT, [&](int which, int lc, float acc) {
                 const int c = cbase * EPC + lc;
-                if (c < C) {
-                    float acc = 0.f;
-                    for (int rr = 0; rr < rows_l; ++rr) acc += sred[(long)(rr * 2 + which) * Wc + lc];
-                    if (which) acc *= invstd[c];
-                    vt_stat_add(sums, ((long)rep * 2 + which) * C + c, acc);
-                }
-            }
-            __syncthreads();
+                if (c >= C) return;
+                if (which) acc *= invstd[c];
+                vt_stat_add(sums, ((long)rep * 2 + which) * C + c, acc);
+            });
         }
     }
 }
@@ -407,144 +404,6 @@ bn_act_apply_pool_kernel(const T* __restrict__ z, int ldz, const float* __restri
 }
 
 // ---------------------------------------------------------------------------------
-// Finalize INSIDE the consuming launch (round 6).  The 134 single-workgroup finalize launches of a CSPDarknet-53 step sit on
-// the critical path between a producer of statistics and the streaming pass that needs the coefficients: skipping them
-// (diagnostic build) shortens the 19.8 ms step by 1.17 ms, 9 - 13 us each.  Any hand-off INSIDE a launch -- first workgroups
-// finalize and publish, the others poll (the first form of these kernels: +2.3 ms per step); the producer's last workgroup
-// finalizes behind a ticket (NOTEBOOK R6.10: +-0, removed) -- costs the dependent memory-side round trips it is made of, as much as
-// the launch boundary it replaces.  Here nothing is handed over: the sums are complete when the streaming launch starts, so
-// EVERY workgroup finalizes the (at most 128) channels of its own channel group for itself -- a thread per (channel, sum),
-// its 16 replicas x 2 limbs in one round of plain loads (64 KB per workgroup, L2 hits after the first workgroup of an XCD),
-// the arithmetic of bn_finalize_kernel / bn_bwd_finalize_kernel bit for bit (vt_fin_fwd_channel / vt_fin_bwd_channel) --
-// and keeps the coefficients in LDS; the workgroups of row block 0 also store them (and the running statistics, d(gamma),
-// d(beta)) for the later passes.  The grid is cut for ~1536 workgroups instead of 4096, so that the redundant reads stay
-// small beside the tensor traffic (step: 1024 -> 19.50, 1536 -> 19.47, 3072 -> 19.59, 4096 -> 19.81 ms).
-// ---------------------------------------------------------------------------------
-// (kFinCg channels per channel group, fin_group: vt_rowmap.h)
-// y = [relu](z*scale + shift) [+ residual]; grid (row blocks, channel groups of Cg channels)
-template <typename T, bool kRes>
-__global__ void __launch_bounds__(kThreads)
-bn_fin_apply_kernel(const VtFinFwd f, const T* __restrict__ z, int ldz, const T* __restrict__ res, int ldr, T* __restrict__ y,
-                    int ldy, long M, RowMap rm, int relu, int Cg) {
-    constexpr int EPC = VecIO<T>::EPC;
-    __shared__ float s_sc[kFinCg], s_sf[kFinCg];
-    const int t = threadIdx.x;
-    const int cg0 = blockIdx.y * Cg;
-    vt_pair_sums<false>(f.stats, f.C, cg0, cg0 + Cg, [&](int c) { return vt_fin_fwd_pre(f, c); },
-                        [&](int c, double s, double ss, const VtFinFwdPre& p) {
-                            float sc, sf;
-                            vt_fin_fwd_channel(f, c, s, ss, p.g, p.b, p.rm, p.rv, sc, sf, blockIdx.x == 0);
-                            s_sc[c - cg0] = sc, s_sf[c - cg0] = sf;
-                        });
-    __syncthreads();
-    z += cg0, y += cg0;
-    if (kRes) res += cg0;
-    const int r = t / rm.CT;
-    if (r >= rm.RT) return;
-    const long row0 = (long)(rm.rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * rm.RT * rm.iters + r;
-    for (int col = t % rm.CT; col < rm.CPR; col += rm.CT) {
-        float sc[EPC], sf[EPC];
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) sc[e] = s_sc[col * EPC + e], sf[e] = s_sf[col * EPC + e];
-        const T* pz = z + row0 * ldz + col * EPC;
-        const T* pr = kRes ? res + row0 * ldr + col * EPC : nullptr;
-        T* py = y + row0 * ldy + col * EPC;
-        const long sz = (long)rm.RT * ldz, sr = (long)rm.RT * ldr, sy = (long)rm.RT * ldy;
-        for (int it = 0; it < rm.iters; it += kUnroll) {
-            uint4 vz[kUnroll], vr[kUnroll];
-            bool ok[kUnroll];
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                ok[u] = (it + u < rm.iters) && (row0 + (long)(it + u) * rm.RT < M);
-                vz[u] = vr[u] = make_uint4(0, 0, 0, 0);
-                if (ok[u]) {
-                    vz[u] = ld16(pz + (it + u) * sz);
-                    if (kRes) vr[u] = ld16(pr + (it + u) * sr);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                float v[EPC];
-                VecIO<T>::unpack(vz[u], v);
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) {
-                    v[e] = fmaf(v[e], sc[e], sf[e]);
-                    v[e] = relu ? fmaxf(v[e], 0.f) : v[e];
-                }
-                if (kRes) {
-                    float rr[EPC];
-                    VecIO<T>::unpack(vr[u], rr);
-#pragma unroll
-                    for (int e = 0; e < EPC; ++e) v[e] += rr[e];
-                }
-                if (ok[u]) st16(py + (it + u) * sy, VecIO<T>::pack(v));
-            }
-        }
-    }
-}
-
-// dz = a*g - b*z + d; grid (row blocks, channel groups of Cg channels)
-template <typename T>
-__global__ void __launch_bounds__(kThreads)
-bn_bwd_fin_apply_kernel(const VtFinBwd f, const T* __restrict__ dy, int lddy, const T* __restrict__ z, int ldz,
-                        const float* __restrict__ scale, const float* __restrict__ shift, T* __restrict__ dz, int lddz, long M,
-                        RowMap rm, int relu, int Cg) {
-    constexpr int EPC = VecIO<T>::EPC;
-    __shared__ float s_a[kFinCg], s_b[kFinCg], s_d[kFinCg];
-    const int t = threadIdx.x;
-    const int cg0 = blockIdx.y * Cg;
-    vt_pair_sums<false>(f.sums, f.C, cg0, cg0 + Cg, [&](int c) { return vt_fin_bwd_pre(f, c); },
-                        [&](int c, double s1, double s2, const VtFinBwdPre& p) {
-                            float b, d;
-                            vt_fin_bwd_channel(f, c, s1, s2, p.a, p.mu, p.istd, p.dg, p.db, b, d, blockIdx.x == 0);
-                            s_a[c - cg0] = p.a, s_b[c - cg0] = b, s_d[c - cg0] = d;
-                        });
-    __syncthreads();
-    dy += cg0, z += cg0, dz += cg0, scale += cg0, shift += cg0;
-    const int r = t / rm.CT;
-    if (r >= rm.RT) return;
-    const long row0 = (long)(rm.rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * rm.RT * rm.iters + r;
-    for (int col = t % rm.CT; col < rm.CPR; col += rm.CT) {
-        float sc[EPC], sf[EPC], ca[EPC], cb[EPC], cd[EPC];
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-            const int c = col * EPC + e;
-            sc[e] = scale[c];
-            sf[e] = shift[c];
-            ca[e] = s_a[c], cb[e] = s_b[c], cd[e] = s_d[c];
-        }
-        for (int it = 0; it < rm.iters; it += kUnroll) {
-            uint4 vg[kUnroll], vz[kUnroll];
-            bool ok[kUnroll];
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                const long row = row0 + (long)(it + u) * rm.RT;
-                ok[u] = (it + u < rm.iters) && row < M;
-                vg[u] = vz[u] = make_uint4(0, 0, 0, 0);
-                if (ok[u]) {
-                    vg[u] = ld16(dy + row * lddy + col * EPC);
-                    vz[u] = ld16(z + row * ldz + col * EPC);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                if (!ok[u]) continue;
-                const long row = row0 + (long)(it + u) * rm.RT;
-                float g[EPC], zz[EPC];
-                VecIO<T>::unpack(vg[u], g);
-                VecIO<T>::unpack(vz[u], zz);
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) {
-                    const float gg = (!relu || fmaf(zz[e], sc[e], sf[e]) > 0.f) ? g[e] : 0.f;
-                    g[e] = fmaf(ca[e], gg, fmaf(-cb[e], zz[e], cd[e]));
-                }
-                st16(dz + row * lddz + col * EPC, VecIO<T>::pack(g));
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------
 // BN backward, pass 1: per-channel sum(g) and sum(g*xhat), g = dy * [z*scale+shift > 0]
 // ---------------------------------------------------------------------------------
 template <typename T, bool GEN = false>
@@ -553,17 +412,13 @@ bn_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ z
                      const float* __restrict__ scale, const float* __restrict__ shift,
                      const float* __restrict__ mean, const float* __restrict__ invstd, long M, int C,
                      RowMap rm, int relu_flags, float* __restrict__ sums, int Ctot) {
-    const int relu = relu_flags & 1;  // bit 1: dev switch, LDS staging of every row lane (the pre-round-2 fold)
+    const int relu = relu_flags & 1;
     const int act = relu_flags >> 4;  // (GEN: the activation code)
     constexpr int EPC = VecIO<T>::EPC;
-    // [RT][2][CT*EPC] partial sums: each thread parks its 2*EPC partials, then the first
-    // 2*CT*EPC threads fold the RT row lanes (no LDS atomics: with RT rows per column they
-    // serialised RT-way and cost as much as the streaming itself on the 28x28..7x7 maps).
-    extern __shared__ __attribute__((aligned(16))) float sred[];
+    extern __shared__ __attribute__((aligned(16))) float sred[];  // rowlane_fold_bytes(2, CT, RT, EPC)
     const int t = threadIdx.x;
     const int r = t / rm.CT;
     const int tc = t % rm.CT;
-    const int W = rm.CT * EPC;  // channels covered per pass
     const long row0 = (long)(rm.rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * rm.RT * rm.iters + r;
     const int rep = blockIdx.x % kStatReplicas;
     // blockIdx.y: channel group (C channels each of Ctot; round 4).  On the small maps a block's 2 * C fixed-point atomics
@@ -575,7 +430,8 @@ bn_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ z
     for (int cbase = 0; cbase < rm.CPR; cbase += rm.CT) {
         const int col = cbase + tc;
         const bool active = (r < rm.RT) && (col < rm.CPR);
-        float s1[EPC], s2[EPC];
+        float s[2][EPC];
+        float(&s1)[EPC] = s[0], (&s2)[EPC] = s[1];
 #pragma unroll
         for (int e = 0; e < EPC; ++e) s1[e] = s2[e] = 0.f;
         if (active) {
@@ -616,47 +472,12 @@ bn_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ z
                 }
             }
         }
-        // Rows of the fold: with CT a power of two below 64 a wave holds 64 / CT row lanes of every column it
-        // touches; those are folded in registers first (xor shuffles), so the LDS staging shrinks from RT to
-        // kThreads / 64 rows -- 4 KiB instead of 16 KiB at C = 128.  (This kernel runs beside the filter gradients
-        // of the side stream, whose workgroups hold most of a CU's LDS: at 16 KiB per block its occupancy, not HBM,
-        // set its in-step time.)
-        const bool inwave = rm.CT < 64 && (rm.CT & (rm.CT - 1)) == 0 && !(relu_flags & 2);
-        int rows_l = rm.RT, r_l = r;
-        if (inwave) {
-            for (int off = rm.CT; off < 64; off <<= 1) {
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) {
-                    s1[e] += __shfl_xor(s1[e], off, 64);
-                    s2[e] += __shfl_xor(s2[e], off, 64);
-                }
-            }
-            rows_l = kThreads / 64;
-            r_l = (t & 63) < rm.CT ? (t >> 6) : -1;  // one writer per (wave, column)
-        } else if (r >= rm.RT) {
-            r_l = -1;
-        }
-        if (r_l >= 0) {
-            float4* d1 = (float4*)(sred + ((long)(r_l * 2 + 0) * W + tc * EPC));
-            float4* d2 = (float4*)(sred + ((long)(r_l * 2 + 1) * W + tc * EPC));
-#pragma unroll
-            for (int q = 0; q < EPC / 4; ++q) {
-                d1[q] = make_float4(s1[4 * q], s1[4 * q + 1], s1[4 * q + 2], s1[4 * q + 3]);
-                d2[q] = make_float4(s2[4 * q], s2[4 * q + 1], s2[4 * q + 2], s2[4 * q + 3]);
-            }
-        }
-        __syncthreads();
-        for (int i = t; i < 2 * W; i += kThreads) {
-            const int which = i / W, lc = i % W;
+        rowlane_fold(sred, s, rm.CT, rm.RT, [&](int which, int lc, float acc) {
             const int c = cbase * EPC + lc;
-            if (c < C) {
-                float acc = 0.f;
-                for (int rr = 0; rr < rows_l; ++rr) acc += sred[(long)(rr * 2 + which) * W + lc];
-                if (which) acc *= invstd[c];
-                vt_stat_add(sums, ((long)rep * 2 + which) * Ctot + cg0 * EPC + c, acc);
-            }
-        }
-        __syncthreads();
+            if (c >= C) return;
+            if (which) acc *= invstd[c];
+            vt_stat_add(sums, ((long)rep * 2 + which) * Ctot + cg0 * EPC + c, acc);
+        });
     }
 }
 
@@ -672,15 +493,22 @@ __global__ void bn_bwd_finalize_kernel(const VtFinBwd f) {
     vt_fin_bwd_channel(f, c, s1, s2, a, mu, istd, dg, db, b, d);
 }
 
-// dz = a*g - b*z + d
-template <typename T, bool GEN = false>
+// dz = a*g - b*z + d; kFin: grid (row blocks, channel groups of Cg channels), the backward finalize step inside the launch
+// (a, b, d from the workgroup's LDS rows, `coef` is written by row block 0); else a, b, d = coef[0..2][c] and `f` is unused
+template <typename T, bool GEN = false, bool kFin = false>
 __global__ void __launch_bounds__(kThreads)
-bn_bwd_apply_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ z, int ldz,
+bn_bwd_apply_kernel(const VtFinBwd f, const T* __restrict__ dy, int lddy, const T* __restrict__ z, int ldz,
                     const float* __restrict__ scale, const float* __restrict__ shift,
                     const float* __restrict__ coef, T* __restrict__ dz, int lddz, long M, int C, RowMap rm,
-                    int relu) {
+                    int relu, int Cg) {
     constexpr int EPC = VecIO<T>::EPC;
+    __shared__ float s_a[kFinCg], s_b[kFinCg], s_d[kFinCg];
     const int t = threadIdx.x;
+    if constexpr (kFin) {
+        const int cg0 = blockIdx.y * Cg;
+        vt_fin_bwd_to_lds(f, cg0, Cg, s_a, s_b, s_d);
+        dy += cg0, z += cg0, dz += cg0, scale += cg0, shift += cg0;
+    }
     const int r = t / rm.CT;
     if (r >= rm.RT) return;
     const long row0 = (long)(rm.rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * rm.RT * rm.iters + r;
@@ -689,7 +517,11 @@ bn_bwd_apply_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ z,
 #pragma unroll
         for (int e = 0; e < EPC; ++e) {
             const int c = col * EPC + e;
-            if constexpr (GEN) {  // (no coefficients: dz = dy * act'(z), the unit without a BatchNorm)
+            if constexpr (kFin) {
+                sc[e] = scale[c];
+                sf[e] = shift[c];
+                ca[e] = s_a[c], cb[e] = s_b[c], cd[e] = s_d[c];
+            } else if constexpr (GEN) {  // (no coefficients: dz = dy * act'(z), the unit without a BatchNorm)
                 sc[e] = scale ? scale[c] : 1.f;
                 sf[e] = shift ? shift[c] : 0.f;
                 ca[e] = coef ? coef[c] : 1.f;
@@ -1674,17 +1506,18 @@ int vt_bn_act_apply(const void* z, int32_t ldz, const float* scale, const float*
     RowMap rm = RowMap::make(C, vt_epc(dtype), M);
     rm.rev = (vt_bn_order() >> 0) & 1;
     VT_REQUIRE(relu >= 0 && relu <= 6, VT_ERR_INVALID, "vt_bn_act_apply: activation code %d", relu);
+    const VtFinFwd f{};
     if (relu >= 2) {  // LeakyReLU(0.2) / SiLU / GELU: the generic instantiation (off the Darknet / VoVNet path)
         if (residual) {
             VT_DISPATCH_T(dtype, "vt_bn_act_apply",
                           hipLaunchKernelGGL((bn_act_apply_kernel<T, true, true>), dim3(rm.blocks(M)), dim3(kThreads), 0,
-                                             (hipStream_t)stream, (const T*)z, ldz, scale, shift, (const T*)residual, ldr,
-                                             (T*)y, ldy, (long)M, rm, relu));
+                                             (hipStream_t)stream, f, (const T*)z, ldz, scale, shift, (const T*)residual, ldr,
+                                             (T*)y, ldy, (long)M, rm, relu, C));
         } else {
             VT_DISPATCH_T(dtype, "vt_bn_act_apply",
                           hipLaunchKernelGGL((bn_act_apply_kernel<T, false, true>), dim3(rm.blocks(M)), dim3(kThreads), 0,
-                                             (hipStream_t)stream, (const T*)z, ldz, scale, shift, (const T*)residual, ldr,
-                                             (T*)y, ldy, (long)M, rm, relu));
+                                             (hipStream_t)stream, f, (const T*)z, ldz, scale, shift, (const T*)residual, ldr,
+                                             (T*)y, ldy, (long)M, rm, relu, C));
         }
         VT_CHECK_LAUNCH("vt_bn_act_apply");
         return VT_OK;
@@ -1692,19 +1525,19 @@ int vt_bn_act_apply(const void* z, int32_t ldz, const float* scale, const float*
     if (residual) {
         VT_DISPATCH_T(dtype, "vt_bn_act_apply",
                       VT_LAUNCH_STOP((bn_act_apply_kernel<T, true>), dim3(rm.blocks(M)), dim3(kThreads), 0,
-                                     (hipStream_t)stream, (const T*)z, ldz, scale, shift, (const T*)residual,
-                                     ldr, (T*)y, ldy, (long)M, rm, relu));
+                                     (hipStream_t)stream, f, (const T*)z, ldz, scale, shift, (const T*)residual,
+                                     ldr, (T*)y, ldy, (long)M, rm, relu, C));
     } else {
         VT_DISPATCH_T(dtype, "vt_bn_act_apply",
                       VT_LAUNCH_STOP((bn_act_apply_kernel<T, false>), dim3(rm.blocks(M)), dim3(kThreads), 0,
-                                     (hipStream_t)stream, (const T*)z, ldz, scale, shift, (const T*)residual,
-                                     ldr, (T*)y, ldy, (long)M, rm, relu));
+                                     (hipStream_t)stream, f, (const T*)z, ldz, scale, shift, (const T*)residual,
+                                     ldr, (T*)y, ldy, (long)M, rm, relu, C));
     }
     VT_CHECK_LAUNCH("vt_bn_act_apply");
     return VT_OK;
 }
 
-// vt_bn_finalize + vt_bn_act_apply in one launch (see bn_fin_apply_kernel); activation codes >= 2 and VT_BN_FIN_APPLY=0:
+// vt_bn_finalize + vt_bn_act_apply in one launch (bn_act_apply_kernel<.., kFin = true>); activation codes >= 2 and VT_BN_FIN_APPLY=0:
 // the two launches.  `ready`: 4 zeroed bytes.
 int vt_bn_finalize_apply(const float* stats, int32_t C, double count, const float* gamma, const float* beta, float eps,
                          float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked, float* scale,
@@ -1734,18 +1567,20 @@ int vt_bn_finalize_apply(const float* stats, int32_t C, double count, const floa
     const dim3 grid(rm.blocks(M), groups);
     if (residual) {
         VT_DISPATCH_T(dtype, "vt_bn_finalize_apply",
-                      VT_LAUNCH_STOP((bn_fin_apply_kernel<T, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, f,
-                                     (const T*)z, ldz, (const T*)residual, ldr, (T*)y, ldy, (long)M, rm, relu, Cg));
+                      VT_LAUNCH_STOP((bn_act_apply_kernel<T, true, false, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, f,
+                                     (const T*)z, ldz, (const float*)nullptr, (const float*)nullptr, (const T*)residual, ldr,
+                                     (T*)y, ldy, (long)M, rm, relu, Cg));
     } else {
         VT_DISPATCH_T(dtype, "vt_bn_finalize_apply",
-                      VT_LAUNCH_STOP((bn_fin_apply_kernel<T, false>), grid, dim3(kThreads), 0, (hipStream_t)stream, f,
-                                     (const T*)z, ldz, (const T*)residual, ldr, (T*)y, ldy, (long)M, rm, relu, Cg));
+                      VT_LAUNCH_STOP((bn_act_apply_kernel<T, false, false, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, f,
+                                     (const T*)z, ldz, (const float*)nullptr, (const float*)nullptr, (const T*)residual, ldr,
+                                     (T*)y, ldy, (long)M, rm, relu, Cg));
     }
     VT_CHECK_LAUNCH("vt_bn_finalize_apply");
     return VT_OK;
 }
 
-// vt_bn_bwd_finalize + vt_bn_act_bwd_apply in one launch (see bn_bwd_fin_apply_kernel)
+// vt_bn_bwd_finalize + vt_bn_act_bwd_apply in one launch (bn_bwd_apply_kernel<.., kFin = true>)
 int vt_bn_bwd_finalize_apply(const float* sums, int32_t C, double count, double pscale, const float* scale,
                              const float* shift, const float* mean, const float* invstd, int32_t train, float* dgamma,
                              float* dbeta, float* coef, const void* dy, int32_t lddy, const void* z, int32_t ldz,
@@ -1767,8 +1602,9 @@ int vt_bn_bwd_finalize_apply(const float* sums, int32_t C, double count, double 
     rm.rev = (vt_bn_order() >> 2) & 1;
     const VtFinBwd f{sums, scale, mean, invstd, dgamma, dbeta, coef, 1.0 / count, pscale, C, train};
     VT_DISPATCH_T(dtype, "vt_bn_bwd_finalize_apply",
-                  VT_LAUNCH_STOP(bn_bwd_fin_apply_kernel<T>, dim3(rm.blocks(M), groups), dim3(kThreads), 0, (hipStream_t)stream, f,
-                                 (const T*)dy, lddy, (const T*)z, ldz, scale, shift, (T*)dz, lddz, (long)M, rm, relu, Cg));
+                  VT_LAUNCH_STOP((bn_bwd_apply_kernel<T, false, true>), dim3(rm.blocks(M), groups), dim3(kThreads), 0, (hipStream_t)stream, f,
+                                 (const T*)dy, lddy, (const T*)z, ldz, scale, shift, (const float*)nullptr, (T*)dz, lddz, (long)M, C,
+                                 rm, relu, Cg));
     VT_CHECK_LAUNCH("vt_bn_bwd_finalize_apply");
     return VT_OK;
 }
@@ -1795,22 +1631,20 @@ int vt_bn_act_bwd_reduce(const void* dy, int32_t lddy, const void* z, int32_t ld
     const int target = blocks_knob / cgroups > 0 ? blocks_knob / cgroups : 1;
     RowMap rm = RowMap::make(Cg, epc, M, target);
     rm.rev = (vt_bn_order() >> 1) & 1;
-    const int inwave_env = (1);
-    const bool inwave = inwave_env && rm.CT < 64 && (rm.CT & (rm.CT - 1)) == 0;  // (as in the kernel)
-    const int smem = (inwave ? kThreads / 64 : rm.RT) * 2 * rm.CT * epc * (int)sizeof(float);
+    const int smem = rowlane_fold_bytes(2, rm.CT, rm.RT, epc);
     VT_REQUIRE(relu >= 0 && relu <= 6, VT_ERR_INVALID, "vt_bn_act_bwd_reduce: activation code %d", relu);
     if (relu >= 2) {
         VT_DISPATCH_T(dtype, "vt_bn_act_bwd_reduce",
                       hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true>), dim3(rm.blocks(M), cgroups), dim3(kThreads), smem,
                                          (hipStream_t)stream, (const T*)dy, lddy, (const T*)z, ldz, scale, shift, mean,
-                                         invstd, (long)M, Cg, rm, (relu << 4) | (inwave_env ? 0 : 2), sums, C));
+                                         invstd, (long)M, Cg, rm, relu << 4, sums, C));
         VT_CHECK_LAUNCH("vt_bn_act_bwd_reduce");
         return VT_OK;
     }
     VT_DISPATCH_T(dtype, "vt_bn_act_bwd_reduce",
                   hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, dim3(rm.blocks(M), cgroups), dim3(kThreads), smem,
                                      (hipStream_t)stream, (const T*)dy, lddy, (const T*)z, ldz, scale, shift,
-                                     mean, invstd, (long)M, Cg, rm, (relu ? 1 : 0) | (inwave_env ? 0 : 2), sums, C));
+                                     mean, invstd, (long)M, Cg, rm, relu ? 1 : 0, sums, C));
     VT_CHECK_LAUNCH("vt_bn_act_bwd_reduce");
     return VT_OK;
 }
@@ -1838,18 +1672,19 @@ int vt_bn_act_bwd_apply(const void* dy, int32_t lddy, const void* z, int32_t ldz
     RowMap rm = RowMap::make(C, vt_epc(dtype), M);
     rm.rev = (vt_bn_order() >> 2) & 1;
     VT_REQUIRE(relu >= 0 && relu <= 6, VT_ERR_INVALID, "vt_bn_act_bwd_apply: activation code %d", relu);
+    const VtFinBwd f{};
     if (relu >= 2 || act_only) {
         VT_DISPATCH_T(dtype, "vt_bn_act_bwd_apply",
                       hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true>), dim3(rm.blocks(M)), dim3(kThreads), 0,
-                                         (hipStream_t)stream, (const T*)dy, lddy, (const T*)z, ldz, scale, shift, coef,
-                                         (T*)dz, lddz, (long)M, C, rm, relu));
+                                         (hipStream_t)stream, f, (const T*)dy, lddy, (const T*)z, ldz, scale, shift, coef,
+                                         (T*)dz, lddz, (long)M, C, rm, relu, C));
         VT_CHECK_LAUNCH("vt_bn_act_bwd_apply");
         return VT_OK;
     }
     VT_DISPATCH_T(dtype, "vt_bn_act_bwd_apply",
                   VT_LAUNCH_STOP(bn_bwd_apply_kernel<T>, dim3(rm.blocks(M)), dim3(kThreads), 0,
-                                 (hipStream_t)stream, (const T*)dy, lddy, (const T*)z, ldz, scale, shift,
-                                 coef, (T*)dz, lddz, (long)M, C, rm, relu));
+                                 (hipStream_t)stream, f, (const T*)dy, lddy, (const T*)z, ldz, scale, shift,
+                                 coef, (T*)dz, lddz, (long)M, C, rm, relu, C));
     VT_CHECK_LAUNCH("vt_bn_act_bwd_apply");
     return VT_OK;
 }
@@ -1893,10 +1728,9 @@ int vt_bn_act_bwd_reduce_pool(const void* dp, int32_t lddp, const uint8_t* argma
     const long Mo = (long)B * Ho * Wo;
     const int epc = vt_epc(dtype);
     RowMap rm = RowMap::make(C, epc, Mo, 256);
-    const bool inwave = rm.CT < 64 && (rm.CT & (rm.CT - 1)) == 0;  // (as in the kernel)
-    const int smem = (inwave ? kThreads / 64 : rm.RT) * 2 * rm.CT * epc * (int)sizeof(float);
     VT_DISPATCH_T(dtype, "vt_bn_act_bwd_reduce_pool",
-                  hipLaunchKernelGGL((bn_bwd_pool_kernel<T, false>), dim3(rm.blocks(Mo)), dim3(kThreads), smem,
+                  hipLaunchKernelGGL((bn_bwd_pool_kernel<T, false>), dim3(rm.blocks(Mo)), dim3(kThreads),
+                                     rowlane_fold_bytes(2, rm.CT, rm.RT, epc),
                                      (hipStream_t)stream, (const T*)dp, lddp, argmax, (const T*)z, ldz, scale, shift, mean, invstd,
                                      (T*)nullptr, 0, H, W, Ho, Wo, C, Mo, rm, relu, sums));
     VT_CHECK_LAUNCH("vt_bn_act_bwd_reduce_pool");

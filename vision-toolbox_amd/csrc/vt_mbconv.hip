@@ -14,7 +14,8 @@
 //    inside the BatchNorm backward, instead of being added to an already rounded d(y) by a pass of its own.
 //    Forward and backward apply exist with the finalize step inside the launch (vt_bn_fin.h) and with ready coefficients,
 //    as in vt_resnet.hip; every activation code of vt_act.h is taken.  Streaming kernels on the RowMap: 16 bytes per lane,
-//    kUnroll rows in flight, plain vector stores; the only atomics are the integer ones of the statistics buffer.
+//    kUnroll rows in flight, plain vector stores; the reduce pass and the pool of pass 2 add their row lanes with
+//    rowlane_fold (vt_rowmap.h); the only atomics are the integer ones of the statistics buffer.
 // 2. Normalise + activation + per-image average pool in one pass: y = act(z*scale + shift) and pooled[b][c] = the mean over
 //    the image's pixels of y AS STORED (rounded to the compute dtype) -- the operand of the Squeeze-Excitation MLP, which
 //    otherwise costs one more read of the expanded map (vt_global_avgpool_fwd).  A workgroup owns one (image, row slab,
@@ -41,13 +42,7 @@ bn_keep_apply_kernel(const VtFinFwd f, const float* __restrict__ scale, const fl
     const int t = threadIdx.x;
     const int cg0 = blockIdx.y * Cg;
     if constexpr (kFin) {
-        vt_pair_sums<false>(f.stats, f.C, cg0, cg0 + Cg, [&](int c) { return vt_fin_fwd_pre(f, c); },
-                            [&](int c, double s, double ss, const VtFinFwdPre& p) {
-                                float sc, sf;
-                                vt_fin_fwd_channel(f, c, s, ss, p.g, p.b, p.rm, p.rv, sc, sf, blockIdx.x == 0);
-                                s_sc[c - cg0] = sc, s_sf[c - cg0] = sf;
-                            });
-        __syncthreads();
+        vt_fin_fwd_to_lds(f, cg0, Cg, s_sc, s_sf);
     }
     z += cg0, y += cg0, r += cg0;
     const int rl = t / rm.CT;
@@ -99,8 +94,8 @@ bn_keep_apply_kernel(const VtFinFwd f, const float* __restrict__ scale, const fl
 }
 
 // ---------------------------------------------------------------------------------
-// backward, pass 1: per-channel sum(g) and sum(g*xhat), g = keep[b] * dy * act'(z*scale + shift) (the structure of
-// bn_bwd_reduce_kernel, vt_elementwise.hip); grid (row blocks, channel groups of C channels each of Ctot)
+// backward, pass 1: per-channel sum(g) and sum(g*xhat), g = keep[b] * dy * act'(z*scale + shift); the row lanes meet in
+// rowlane_fold (vt_rowmap.h); grid (row blocks, channel groups of C channels each of Ctot)
 // ---------------------------------------------------------------------------------
 // (kAdd: the addend form is an instantiation of its own, so that the passes of a residual block keep their registers)
 template <typename T, bool kAdd>
@@ -110,12 +105,10 @@ bn_keep_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restric
                           const float* __restrict__ keep, const T* __restrict__ add, int lda, unsigned HW, long M, int C, RowMap rm,
                           int act, float* __restrict__ sums, int Ctot) {
     constexpr int EPC = VecIO<T>::EPC;
-    // [rows][2][CT*EPC] partial sums, folded by the first 2*CT*EPC threads (no LDS atomics)
-    extern __shared__ __attribute__((aligned(16))) float sred[];
+    extern __shared__ __attribute__((aligned(16))) float sred[];  // rowlane_fold_bytes(2, CT, RT, EPC)
     const int t = threadIdx.x;
     const int r = t / rm.CT;
     const int tc = t % rm.CT;
-    const int W = rm.CT * EPC;  // channels covered per pass
     const long row0 = (long)blockIdx.x * rm.RT * rm.iters + r;
     const int rep = blockIdx.x % kStatReplicas;
     const int cg0 = blockIdx.y * rm.CPR;  // first 16-byte chunk of this channel group
@@ -126,7 +119,8 @@ bn_keep_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restric
     for (int cbase = 0; cbase < rm.CPR; cbase += rm.CT) {
         const int col = cbase + tc;
         const bool active = (r < rm.RT) && (col < rm.CPR);
-        float s1[EPC], s2[EPC];
+        float s[2][EPC];
+        float(&s1)[EPC] = s[0], (&s2)[EPC] = s[1];
 #pragma unroll
         for (int e = 0; e < EPC; ++e) s1[e] = s2[e] = 0.f;
         if (active) {
@@ -177,44 +171,12 @@ bn_keep_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restric
                 }
             }
         }
-        // with CT a power of two below 64 a wave holds 64 / CT row lanes of every column it touches: folded in registers
-        // first (xor shuffles), so the LDS staging is kThreads / 64 rows instead of RT
-        const bool inwave = rm.CT < 64 && (rm.CT & (rm.CT - 1)) == 0;
-        int rows_l = rm.RT, r_l = r;
-        if (inwave) {
-            for (int off = rm.CT; off < 64; off <<= 1) {
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) {
-                    s1[e] += __shfl_xor(s1[e], off, 64);
-                    s2[e] += __shfl_xor(s2[e], off, 64);
-                }
-            }
-            rows_l = kThreads / 64;
-            r_l = (t & 63) < rm.CT ? (t >> 6) : -1;  // one writer per (wave, column)
-        } else if (r >= rm.RT) {
-            r_l = -1;
-        }
-        if (r_l >= 0) {
-            float4* d1 = (float4*)(sred + ((long)(r_l * 2 + 0) * W + tc * EPC));
-            float4* d2 = (float4*)(sred + ((long)(r_l * 2 + 1) * W + tc * EPC));
-#pragma unroll
-            for (int q = 0; q < EPC / 4; ++q) {
-                d1[q] = make_float4(s1[4 * q], s1[4 * q + 1], s1[4 * q + 2], s1[4 * q + 3]);
-                d2[q] = make_float4(s2[4 * q], s2[4 * q + 1], s2[4 * q + 2], s2[4 * q + 3]);
-            }
-        }
-        __syncthreads();
-        for (int i = t; i < 2 * W; i += kThreads) {
-            const int which = i / W, lc = i % W;
+        rowlane_fold(sred, s, rm.CT, rm.RT, [&](int which, int lc, float acc) {
             const int c = cbase * EPC + lc;
-            if (c < C) {
-                float acc = 0.f;
-                for (int rr = 0; rr < rows_l; ++rr) acc += sred[(long)(rr * 2 + which) * W + lc];
-                if (which) acc *= invstd[c];
-                vt_stat_add(sums, ((long)rep * 2 + which) * Ctot + cg0 * EPC + c, acc);
-            }
-        }
-        __syncthreads();
+            if (c >= C) return;
+            if (which) acc *= invstd[c];
+            vt_stat_add(sums, ((long)rep * 2 + which) * Ctot + cg0 * EPC + c, acc);
+        });
     }
 }
 
@@ -233,13 +195,7 @@ bn_keep_bwd_apply_kernel(const VtFinBwd f, const float* __restrict__ coef, const
     const int t = threadIdx.x;
     const int cg0 = blockIdx.y * Cg;
     if constexpr (kFin) {
-        vt_pair_sums<false>(f.sums, f.C, cg0, cg0 + Cg, [&](int c) { return vt_fin_bwd_pre(f, c); },
-                            [&](int c, double s1, double s2, const VtFinBwdPre& p) {
-                                float b, d;
-                                vt_fin_bwd_channel(f, c, s1, s2, p.a, p.mu, p.istd, p.dg, p.db, b, d, blockIdx.x == 0);
-                                s_a[c - cg0] = p.a, s_b[c - cg0] = b, s_d[c - cg0] = d;
-                            });
-        __syncthreads();
+        vt_fin_bwd_to_lds(f, cg0, Cg, s_a, s_b, s_d);
     }
     dy += cg0, z += cg0, dz += cg0, shift += cg0;
     if constexpr (kAdd) add += cg0;
@@ -315,17 +271,12 @@ bn_act_avgpool_kernel(const VtFinFwd f, const float* __restrict__ scale, const f
                       int Ctot, PoolPlan pp, int act) {
     constexpr int EPC = VecIO<T>::EPC;
     __shared__ float s_sc[kFinCg], s_sf[kFinCg];
-    __shared__ float sred[kThreads * EPC];  // [rows][CT*EPC] partial sums of the row lanes
+    // the one-sum rowlane_fold: rowlane_fold_bytes(1, CT, RT, EPC) <= kThreads * EPC floats, since rows * CT <= kThreads
+    __shared__ __attribute__((aligned(16))) float sred[kThreads * EPC];
     const int t = threadIdx.x;
     const int cg0 = blockIdx.y * pp.Cg;
     if constexpr (kFin) {
-        vt_pair_sums<false>(f.stats, f.C, cg0, cg0 + pp.Cg, [&](int c) { return vt_fin_fwd_pre(f, c); },
-                            [&](int c, double s, double ss, const VtFinFwdPre& p) {
-                                float sc, sf;
-                                vt_fin_fwd_channel(f, c, s, ss, p.g, p.b, p.rm, p.rv, sc, sf, blockIdx.x == 0);
-                                s_sc[c - cg0] = sc, s_sf[c - cg0] = sf;
-                            });
-        __syncthreads();
+        vt_fin_fwd_to_lds(f, cg0, pp.Cg, s_sc, s_sf);
     } else {
         scale += cg0, shift += cg0;
     }
@@ -333,12 +284,12 @@ bn_act_avgpool_kernel(const VtFinFwd f, const float* __restrict__ scale, const f
     const int lo = slab * pp.rps, hi = min(HW, lo + pp.rps);
     z += (long)b * HW * ldz + cg0, y += (long)b * HW * ldy + cg0;
     const int r = t / pp.CT, tc = t % pp.CT;
-    const int W = pp.CT * EPC;
     const float inv = 1.f / (float)HW;
     for (int cbase = 0; cbase < pp.CPR; cbase += pp.CT) {
         const int col = cbase + tc;
         const bool active = (r < pp.RT) && (col < pp.CPR);
-        float s[EPC];
+        float ps[1][EPC];
+        float(&s)[EPC] = ps[0];
 #pragma unroll
         for (int e = 0; e < EPC; ++e) s[e] = 0.f;
         if (active) {
@@ -370,34 +321,12 @@ bn_act_avgpool_kernel(const VtFinFwd f, const float* __restrict__ scale, const f
                 }
             }
         }
-        // the fold of bn_keep_bwd_reduce_kernel: row lanes of a wave in registers where CT is a power of two below 64
-        const bool inwave = pp.CT < 64 && (pp.CT & (pp.CT - 1)) == 0;
-        int rows_l = pp.RT, r_l = r;
-        if (inwave) {
-            for (int off = pp.CT; off < 64; off <<= 1) {
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) s[e] += __shfl_xor(s[e], off, 64);
-            }
-            rows_l = kThreads / 64;
-            r_l = (t & 63) < pp.CT ? (t >> 6) : -1;  // one writer per (wave, column)
-        } else if (r >= pp.RT) {
-            r_l = -1;
-        }
-        if (r_l >= 0) {
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) sred[(long)r_l * W + tc * EPC + e] = s[e];
-        }
-        __syncthreads();
-        for (int lc = t; lc < W; lc += kThreads) {
+        rowlane_fold(sred, ps, pp.CT, pp.RT, [&](int, int lc, float acc) {
             const int c = cbase * EPC + lc;  // (within the channel group)
-            if (c < pp.Cg) {
-                float acc = 0.f;
-                for (int rr = 0; rr < rows_l; ++rr) acc += sred[(long)rr * W + lc];
-                if (pp.S == 1) pooled[(long)b * ldp + cg0 + c] = from_float<T>(acc * inv);
-                else vt_stat_add(scratch, (long)b * Ctot + cg0 + c, acc);
-            }
-        }
-        __syncthreads();
+            if (c >= pp.Cg) return;
+            if (pp.S == 1) pooled[(long)b * ldp + cg0 + c] = from_float<T>(acc * inv);
+            else vt_stat_add(scratch, (long)b * Ctot + cg0 + c, acc);
+        });
     }
 }
 
@@ -549,9 +478,8 @@ int vt_bn_keep_bwd_reduce(const void* dy, int32_t lddy, const void* z, int32_t l
     const int Cg = C / cgroups;
     const int blocks_knob = VT_KNOB("VT_BN_RED_BLOCKS", 1024);
     const RowMap rm = RowMap::make(Cg, epc, M, blocks_knob / cgroups > 0 ? blocks_knob / cgroups : 1);
-    const bool inwave = rm.CT < 64 && (rm.CT & (rm.CT - 1)) == 0;  // (as in the kernel)
-    const int smem = (inwave ? kThreads / 64 : rm.RT) * 2 * rm.CT * epc * (int)sizeof(float);
-#define VT_KEEP_RED(ADD)                                                                                                        \
+    const int smem = rowlane_fold_bytes(2, rm.CT, rm.RT, epc);
+#define VT_KEEP_RED(ADD)                                                                                                       \
     VT_DISPATCH_T(dtype, "vt_bn_keep_bwd_reduce",                                                                               \
                   hipLaunchKernelGGL((bn_keep_bwd_reduce_kernel<T, ADD>), dim3(rm.blocks(M), cgroups), dim3(kThreads), smem,     \
                                      (hipStream_t)stream, (const T*)dy, lddy, (const T*)z, ldz, scale, shift, mean, invstd, keep, \

@@ -44,7 +44,7 @@
 //
 // Producer fold (template flag PROD, vt_pw_desc::pcoef): x is the stored PRE-activation z0 of the BatchNorm unit that
 // produces the unit's input, and every pass applies that unit's normalise step y0 = act(z0 * scale + shift), rounded to
-// bf16, to the 16 bytes a lane has just loaded -- the expression and the rounding of bn_fin_apply_kernel
+// bf16, to the 16 bytes a lane has just loaded -- the expression and the rounding of bn_act_apply_kernel
 // (vt_elementwise.hip), so the operand is bit for bit what the passes read from a stored y0, and neither that tensor nor
 // the pass that writes it exists.  Nothing crosses a workgroup: the producer's statistics are complete when the first
 // pass starts, and that pass (STATS) may finalize them in its prologue, every workgroup for itself, as the apply passes

@@ -10,8 +10,9 @@
 //    forward's decision, which a recomputed z*scale + shift + r (r rounded, the sum rounded again) would not be.
 //    Forward and backward apply exist with the finalize step inside the launch (vt_bn_fin.h: every workgroup finalizes the
 //    channels of its own channel group from the complete sums, row block 0 stores them) and with ready coefficients
-//    (eval mode, a frozen bn.eval(), SyncBatchNorm).  Streaming kernels on the RowMap of vt_elementwise.hip: 16 bytes per
-//    lane, kUnroll rows in flight, plain vector stores; the only atomics are the integer ones of the statistics buffer.
+//    (eval mode, a frozen bn.eval(), SyncBatchNorm).  Streaming kernels on the RowMap of vt_rowmap.h: 16 bytes per lane,
+//    kUnroll rows in flight, plain vector stores; the reduce pass adds its row lanes with rowlane_fold (same header); the
+//    only atomics are the integer ones of the statistics buffer.
 // 2. The stem Conv2d(3, 64, 7, 2, 3): 49 taps against VT_MAX_TAPS = 36.  Padded to 8x8 with a zero first row and column it
 //    is a 4x4 stride-1 filter over the space-to-depth image (12 channels (py, px, c)), taps at offsets -2 .. +1, which the
 //    convolution descriptor expresses and the existing forward and filter-gradient kernels run.  Here: the image gather,
@@ -35,13 +36,7 @@ bn_add_act_kernel(const VtFinFwd f, const float* __restrict__ scale, const float
     const int t = threadIdx.x;
     const int cg0 = blockIdx.y * Cg;
     if constexpr (kFin) {
-        vt_pair_sums<false>(f.stats, f.C, cg0, cg0 + Cg, [&](int c) { return vt_fin_fwd_pre(f, c); },
-                            [&](int c, double s, double ss, const VtFinFwdPre& p) {
-                                float sc, sf;
-                                vt_fin_fwd_channel(f, c, s, ss, p.g, p.b, p.rm, p.rv, sc, sf, blockIdx.x == 0);
-                                s_sc[c - cg0] = sc, s_sf[c - cg0] = sf;
-                            });
-        __syncthreads();
+        vt_fin_fwd_to_lds(f, cg0, Cg, s_sc, s_sf);
     }
     z += cg0, y += cg0, r += cg0;
     const int rl = t / rm.CT;
@@ -85,7 +80,7 @@ bn_add_act_kernel(const VtFinFwd f, const float* __restrict__ scale, const float
 }
 
 // ---------------------------------------------------------------------------------
-// backward, pass 1: per-channel sum(g) and sum(g*xhat), g = dy * [y > 0] (the structure of bn_bwd_reduce_kernel)
+// backward, pass 1: per-channel sum(g) and sum(g*xhat), g = dy * [y > 0]; the row lanes meet in rowlane_fold (vt_rowmap.h)
 // ---------------------------------------------------------------------------------
 template <typename T>
 __global__ void __launch_bounds__(kThreads)
@@ -93,12 +88,10 @@ bn_add_act_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __rest
                              const float* __restrict__ mean, const float* __restrict__ invstd, long M, int C, RowMap rm,
                              float* __restrict__ sums, int Ctot) {
     constexpr int EPC = VecIO<T>::EPC;
-    // [rows][2][CT*EPC] partial sums, folded by the first 2*CT*EPC threads (no LDS atomics)
-    extern __shared__ __attribute__((aligned(16))) float sred[];
+    extern __shared__ __attribute__((aligned(16))) float sred[];  // rowlane_fold_bytes(2, CT, RT, EPC)
     const int t = threadIdx.x;
     const int r = t / rm.CT;
     const int tc = t % rm.CT;
-    const int W = rm.CT * EPC;  // channels covered per pass
     const long row0 = (long)blockIdx.x * rm.RT * rm.iters + r;
     const int rep = blockIdx.x % kStatReplicas;
     const int cg0 = blockIdx.y * rm.CPR;  // first 16-byte chunk of this channel group (C channels each of Ctot)
@@ -107,7 +100,8 @@ bn_add_act_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __rest
     for (int cbase = 0; cbase < rm.CPR; cbase += rm.CT) {
         const int col = cbase + tc;
         const bool active = (r < rm.RT) && (col < rm.CPR);
-        float s1[EPC], s2[EPC];
+        float s[2][EPC];
+        float(&s1)[EPC] = s[0], (&s2)[EPC] = s[1];
 #pragma unroll
         for (int e = 0; e < EPC; ++e) s1[e] = s2[e] = 0.f;
         if (active) {
@@ -145,44 +139,12 @@ bn_add_act_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __rest
                 }
             }
         }
-        // with CT a power of two below 64 a wave holds 64 / CT row lanes of every column it touches: folded in registers
-        // first (xor shuffles), so the LDS staging is kThreads / 64 rows instead of RT
-        const bool inwave = rm.CT < 64 && (rm.CT & (rm.CT - 1)) == 0;
-        int rows_l = rm.RT, r_l = r;
-        if (inwave) {
-            for (int off = rm.CT; off < 64; off <<= 1) {
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) {
-                    s1[e] += __shfl_xor(s1[e], off, 64);
-                    s2[e] += __shfl_xor(s2[e], off, 64);
-                }
-            }
-            rows_l = kThreads / 64;
-            r_l = (t & 63) < rm.CT ? (t >> 6) : -1;  // one writer per (wave, column)
-        } else if (r >= rm.RT) {
-            r_l = -1;
-        }
-        if (r_l >= 0) {
-            float4* d1 = (float4*)(sred + ((long)(r_l * 2 + 0) * W + tc * EPC));
-            float4* d2 = (float4*)(sred + ((long)(r_l * 2 + 1) * W + tc * EPC));
-#pragma unroll
-            for (int q = 0; q < EPC / 4; ++q) {
-                d1[q] = make_float4(s1[4 * q], s1[4 * q + 1], s1[4 * q + 2], s1[4 * q + 3]);
-                d2[q] = make_float4(s2[4 * q], s2[4 * q + 1], s2[4 * q + 2], s2[4 * q + 3]);
-            }
-        }
-        __syncthreads();
-        for (int i = t; i < 2 * W; i += kThreads) {
-            const int which = i / W, lc = i % W;
+        rowlane_fold(sred, s, rm.CT, rm.RT, [&](int which, int lc, float acc) {
             const int c = cbase * EPC + lc;
-            if (c < C) {
-                float acc = 0.f;
-                for (int rr = 0; rr < rows_l; ++rr) acc += sred[(long)(rr * 2 + which) * W + lc];
-                if (which) acc *= invstd[c];
-                vt_stat_add(sums, ((long)rep * 2 + which) * Ctot + cg0 * EPC + c, acc);
-            }
-        }
-        __syncthreads();
+            if (c >= C) return;
+            if (which) acc *= invstd[c];
+            vt_stat_add(sums, ((long)rep * 2 + which) * Ctot + cg0 * EPC + c, acc);
+        });
     }
 }
 
@@ -200,13 +162,7 @@ bn_add_act_bwd_apply_kernel(const VtFinBwd f, const float* __restrict__ coef, co
     const int t = threadIdx.x;
     const int cg0 = blockIdx.y * Cg;
     if constexpr (kFin) {
-        vt_pair_sums<false>(f.sums, f.C, cg0, cg0 + Cg, [&](int c) { return vt_fin_bwd_pre(f, c); },
-                            [&](int c, double s1, double s2, const VtFinBwdPre& p) {
-                                float b, d;
-                                vt_fin_bwd_channel(f, c, s1, s2, p.a, p.mu, p.istd, p.dg, p.db, b, d, blockIdx.x == 0);
-                                s_a[c - cg0] = p.a, s_b[c - cg0] = b, s_d[c - cg0] = d;
-                            });
-        __syncthreads();
+        vt_fin_bwd_to_lds(f, cg0, Cg, s_a, s_b, s_d);
     }
     dy += cg0, y += cg0, z += cg0, dz += cg0, dr += cg0;
     const int r = t / rm.CT;
@@ -389,10 +345,9 @@ int vt_bn_add_act_bwd_reduce(const void* dy, int32_t lddy, const void* y, int32_
     const int Cg = C / cgroups;
     const int blocks_knob = VT_KNOB("VT_BN_RED_BLOCKS", 1024);
     const RowMap rm = RowMap::make(Cg, epc, M, blocks_knob / cgroups > 0 ? blocks_knob / cgroups : 1);
-    const bool inwave = rm.CT < 64 && (rm.CT & (rm.CT - 1)) == 0;  // (as in the kernel)
-    const int smem = (inwave ? kThreads / 64 : rm.RT) * 2 * rm.CT * epc * (int)sizeof(float);
     VT_DISPATCH_T(dtype, "vt_bn_add_act_bwd_reduce",
-                  hipLaunchKernelGGL(bn_add_act_bwd_reduce_kernel<T>, dim3(rm.blocks(M), cgroups), dim3(kThreads), smem,
+                  hipLaunchKernelGGL(bn_add_act_bwd_reduce_kernel<T>, dim3(rm.blocks(M), cgroups), dim3(kThreads),
+                                     rowlane_fold_bytes(2, rm.CT, rm.RT, epc),
                                      (hipStream_t)stream, (const T*)dy, lddy, (const T*)y, ldy, (const T*)z, ldz, mean, invstd,
                                      (long)M, Cg, rm, sums, C));
     VT_CHECK_LAUNCH("vt_bn_add_act_bwd_reduce");
