@@ -6,8 +6,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 constexpr int kT = 64;  // rows of a tile, both sides
 
 // the fragment of row `row` (the lane's), reduction elements 32 kk + 8 g + j

@@ -11,6 +11,7 @@ typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;  // operand of the transposing LDS read ds_read_tr16_b64
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 // ---- host side error plumbing ----------------------------------------------
@@ -123,7 +124,29 @@ extern thread_local hipEvent_t vt_pending_stop_event;
         }                             \
     } while (0)
 
-#define VT_CHECK_LAUNCH(name)                                                     \
+// pass a failed check or launch of a callee (which has set the error text) up to the C entry point
+#define VT_TRY(expr)                    \
+    do {                                \
+        const int rc__ = (expr);        \
+        if (rc__ != VT_OK) return rc__; \
+    } while (0)
+
+// run the statement with T = the element type of `dtype`
+#define VT_DISPATCH_T(dtype, NAME, ...)                               \
+    do {                                                              \
+        if ((dtype) == VT_BF16) {                                     \
+            typedef bf16_t T;                                         \
+            __VA_ARGS__;                                              \
+        } else if ((dtype) == VT_F32) {                               \
+            typedef float T;                                          \
+            __VA_ARGS__;                                              \
+        } else {                                                      \
+            vt_set_error("%s: unsupported dtype %d", NAME, (dtype)); \
+            return VT_ERR_UNSUPPORTED;                                \
+        }                                                             \
+    } while (0)
+
+#define VT_CHECK_LAUNCH(name)                                                    \
     do {                                                                          \
         hipError_t e__ = hipGetLastError();                                       \
         if (e__ != hipSuccess) {                                                  \
@@ -136,6 +159,14 @@ extern thread_local hipEvent_t vt_pending_stop_event;
 static inline bool vt_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 static inline int vt_elem_size(int dtype) { return dtype == VT_BF16 ? 2 : 4; }
 static inline int vt_epc(int dtype) { return dtype == VT_BF16 ? 8 : 4; }  // elements per 16 B
+// a [rows][ld] operand of C channels that the kernels read in 16-byte chunks (the attention entry points)
+static inline int vt_check_rows(const char* who, const char* what, const void* ptr, int ld, int C, int dtype) {
+    VT_REQUIRE(ptr && vt_aligned16(ptr) && ld >= C && ld % vt_epc(dtype) == 0, VT_ERR_INVALID,
+               "%s: %s null, not 16-byte aligned, or its row stride %d is below %d channels / no multiple of a 16-byte chunk (%d "
+               "elements)",
+               who, what, ld, C, vt_epc(dtype));
+    return VT_OK;
+}
 
 // ---- device helpers ----------------------------------------------------------
 template <typename T>

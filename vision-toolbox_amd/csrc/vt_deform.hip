@@ -578,12 +578,6 @@ int tiles_held(int rows) {
     return nt;
 }
 
-#define VT_TRY(expr)                    \
-    do {                                \
-        int rc__ = (expr);              \
-        if (rc__ != VT_OK) return rc__; \
-    } while (0)
-
 #define VT_DEFORM_NT(NTV, ...)                                      \
     do {                                                            \
         switch (NTV) {                                              \

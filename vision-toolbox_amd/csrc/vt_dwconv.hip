@@ -24,22 +24,6 @@ namespace {
 
 constexpr int kT = 256;
 
-#define VT_DISPATCH_T(dtype, NAME, ...)                               \
-    do {                                                              \
-        if ((dtype) == VT_BF16) {                                     \
-            typedef bf16_t T;                                         \
-            __VA_ARGS__;                                              \
-        } else {                                                      \
-            typedef float T;                                          \
-            __VA_ARGS__;                                              \
-        }                                                             \
-    } while (0)
-#define VT_TRY(expr)              \
-    do {                          \
-        int rc__ = (expr);        \
-        if (rc__ != VT_OK) return rc__; \
-    } while (0)
-
 struct DwArgs {
     const void* x;
     const float* w;

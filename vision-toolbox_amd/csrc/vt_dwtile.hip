@@ -31,12 +31,6 @@ namespace {
 constexpr int kT = 256;
 constexpr int kLdsMax = 64 * 1024, kLdsAim = 48 * 1024;
 
-#define VT_TRY(expr)              \
-    do {                          \
-        int rc__ = (expr);        \
-        if (rc__ != VT_OK) return rc__; \
-    } while (0)
-
 struct DwtArgs {
     const void* x;
     const float* w;

@@ -520,12 +520,6 @@ int se_check(const char* who, int B, int C, int S, int dtype) {
 
 }  // namespace
 
-#define VT_TRY(expr)                    \
-    do {                                \
-        int rc__ = (expr);              \
-        if (rc__ != VT_OK) return rc__; \
-    } while (0)
-
 extern "C" {
 
 int vt_gconv3_fwd(const void* x, int32_t ldx, const void* w, void* z, int32_t ldz, float* stats, int32_t B, int32_t Hi, int32_t Wi,

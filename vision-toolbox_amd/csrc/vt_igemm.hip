@@ -23,7 +23,7 @@
 // 16-byte zero page, so every lane of every wave issues every load (the LDS
 // destination of an LDS-DMA is lane-linear and cannot be predicated).
 // The LDS image is XOR-swizzled through the source side: LDS slot q of a stage is
-// written linearly, and the lane that owns slot q fetches chunk (q&3)^swz(q>>2)
+// written linearly, and the lane that owns slot q fetches chunk (q&3)^swz4(q>>4)
 // of row q>>2, which makes the ds_read_b128 of the MFMA fragments conflict free.
 //
 // The loads are issued from inline asm on purpose: hipcc would otherwise treat
@@ -50,6 +50,7 @@
 
 #include "vt_common.h"
 #include "vt_igemm_args.h"
+#include "vt_lds_dma.h"
 
 namespace {
 
@@ -57,47 +58,7 @@ constexpr int kTapBytes = VT_MAX_TAPS * 16;  // int4 per tap
 // statistics scratch, per row-wave (sum, sumsq): WM * 2 * BN floats, at least 2 KiB
 constexpr int stat_bytes(int WM, int BN) { return WM * 2 * BN * 4 > 2048 ? WM * 2 * BN * 4 : 2048; }
 
-__device__ __attribute__((aligned(16))) unsigned int vt_zero16[4];  // source of every padded chunk
-
-// chunk swizzle of a 64-byte LDS row: conflict free for ds_read_b128 issued as
-// (row = l&15, chunk = l>>4).
-__device__ __forceinline__ int swz(int row) { return (0x1320 >> (((row >> 2) & 3) * 4)) & 3; }
-
-// one LDS-DMA wave-instruction: lane l copies 16 B from its own global address to
-// LDS byte address lds_base + 16*l.  M0 carries the LDS base and is restored.
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_base) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_base)
-        : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-template <typename T>
-__device__ __forceinline__ void mma(const uint4& a, const uint4& b, f32x4& acc);
-
-template <>
-__device__ __forceinline__ void mma<bf16_t>(const uint4& a, const uint4& b, f32x4& acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                  __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ void mma<float>(const uint4& a, const uint4& b, f32x4& acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
-}
+// glds16_m0_saved, vm_wait<N>, mma<T>, swz4 and the zero source vt_zero16: vt_lds_dma.h
 
 template <int BM, int BN, int PD, int NW, int WM>
 struct Geom {
@@ -164,7 +125,7 @@ __global__ void __launch_bounds__(64 * WM * WN) igemm_kernel(const IgemmArgs p) 
 
     // ---- per-lane DMA geometry (fixed for the whole K loop) --------------------
     // instruction j = wave + NW*i of a stage fills slots [64j, 64j+64); lane l owns slot
-    // q = 64j + l = row (q>>2), position (q&3), and fetches chunk (q&3) ^ swz(row).
+    // q = 64j + l = row (q>>2), position (q&3), and fetches chunk (q&3) ^ swz4(row>>2).
     // (row>>2)&3 == (l>>4)&3 for every j, so the chunk is the same for all of a lane's loads.
     const int cj = (lane & 3) ^ ((0x1320 >> (((lane >> 4) & 3) * 4)) & 3);
     int hb[IT], wb[IT];
@@ -247,7 +208,7 @@ __global__ void __launch_bounds__(64 * WM * WN) igemm_kernel(const IgemmArgs p) 
                     ps = bptr[i];                                                               \
                     bptr[i] += bstep[i];                                                        \
                 }                                                                               \
-                glds16((const void*)ps, ring_base + (unsigned)(((st)*SS + j * 64) * 16));       \
+                glds16_m0_saved(ps, ring_base + (unsigned)(((st)*SS + j * 64) * 16));           \
             }                                                                                   \
             c0_u += BK;                                                                         \
             if (c0_u >= p.Cin) {                                                                \
@@ -268,7 +229,7 @@ __global__ void __launch_bounds__(64 * WM * WN) igemm_kernel(const IgemmArgs p) 
             const unsigned long pa = (unsigned long)(xg + (off0[i] + te.z + c));                \
             const unsigned long pb = (unsigned long)(wg + (off0[i] + kk));                      \
             const unsigned long ps = isA ? (va ? pa : zero_src) : ((isB && kval && valid[i]) ? pb : zero_src); \
-            glds16((const void*)ps, ring_base + (unsigned)(((st)*SS + j * 64) * 16));           \
+            glds16_m0_saved(ps, ring_base + (unsigned)(((st)*SS + j * 64) * 16));               \
         }                                                                                       \
         kk += BK;                                                                               \
         c += BK;                                                                                \
@@ -284,7 +245,7 @@ __global__ void __launch_bounds__(64 * WM * WN) igemm_kernel(const IgemmArgs p) 
 #pragma unroll
         for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const int lane_off = (lane & 15) * 4 + ((lane >> 4) ^ swz(lane & 15));
+    const int lane_off = (lane & 15) * 4 + ((lane >> 4) ^ swz4((lane & 15) >> 2));
     const int nk = (p.Ktot + BK - 1) / BK;
 
     // prologue: PD stages in flight

@@ -29,6 +29,7 @@
 
 #include "vt_common.h"
 #include "vt_igemm_args.h"
+#include "vt_lds_dma.h"
 
 namespace {
 
@@ -65,66 +66,29 @@ struct PsArgs {
     int8_t t_q[kMaxSteps], t_rs[kMaxSteps];  // its plane and its filter tap
 };
 
-__device__ __forceinline__ int swz4(int g) { return (0x1320 >> ((g & 3) * 4)) & 3; }  // filter-slice image
-__device__ __forceinline__ int swzA(int g) { return (g & 1) << 1; }                   // span image (span6's)
+// The LDS-DMA forms of the loaders (glds16_m0_written_sbase and its _rfl wrapper, get_m0 / set_m0), vm_wait<N>, wg_barrier,
+// swz4 (filter-slice image), swzA (span image), row_sum16 and the zero source: vt_lds_dma.h
 
-__device__ __forceinline__ const void* uniform_ptr(const void* p) {
-    const unsigned long v = (unsigned long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (const void*)(((unsigned long)hi << 32) | lo);
-}
-// LDS-DMA, 16 B per lane: LDS address = M0 + lane*16, global address = sbase + voff.  (s_nop 4: the scalar base may have
-// just been written by a VALU instruction; a VMEM instruction reading such an SGPR needs 5 wait states, which hipcc does
-// not insert in front of an asm statement.)
-__device__ __forceinline__ void glds_s(unsigned voff, const void* sbase, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1"
-                 ::"v"(voff), "s"(uniform_ptr(sbase)), "s"(__builtin_amdgcn_readfirstlane(lds_addr))
-                 : "memory");
-}
-// the same with operands the caller has already made wave-uniform (one readfirstlane per plane, not three per piece)
-__device__ __forceinline__ void glds_u(unsigned voff, const void* sbase_uniform, unsigned lds_addr_uniform) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1"
-                 ::"v"(voff), "s"(sbase_uniform), "s"(lds_addr_uniform)
-                 : "memory");
-}
-__device__ __forceinline__ unsigned get_m0() {
-    unsigned v;
-    asm volatile("s_mov_b32 %0, m0" : "=s"(v)::"memory");
-    return v;
-}
-__device__ __forceinline__ void set_m0(unsigned v) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(__builtin_amdgcn_readfirstlane(v)) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void vmw() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
+// Not span6's tree (cap 28): a loader here has up to nbuf - 1 whole span sets in flight, so groups of 8 up to 32.
 __device__ __forceinline__ void vm_wait_dyn(int n) {  // wave-uniform count; waits a little early above 32
-    if (n <= 0) { vmw<0>(); return; }
+    if (n <= 0) { vm_wait<0>(); return; }
 #define VT_W8(b)                                 \
     switch (n - (b)) {                           \
-        case 0: vmw<(b) + 0>(); break;           \
-        case 1: vmw<(b) + 1>(); break;           \
-        case 2: vmw<(b) + 2>(); break;           \
-        case 3: vmw<(b) + 3>(); break;           \
-        case 4: vmw<(b) + 4>(); break;           \
-        case 5: vmw<(b) + 5>(); break;           \
-        case 6: vmw<(b) + 6>(); break;           \
-        default: vmw<(b) + 7>(); break;          \
+        case 0: vm_wait<(b) + 0>(); break;       \
+        case 1: vm_wait<(b) + 1>(); break;       \
+        case 2: vm_wait<(b) + 2>(); break;       \
+        case 3: vm_wait<(b) + 3>(); break;       \
+        case 4: vm_wait<(b) + 4>(); break;       \
+        case 5: vm_wait<(b) + 5>(); break;       \
+        case 6: vm_wait<(b) + 6>(); break;       \
+        default: vm_wait<(b) + 7>(); break;      \
     }
     if (n < 8) { VT_W8(0) }
     else if (n < 16) { VT_W8(8) }
     else if (n < 24) { VT_W8(16) }
     else if (n < 32) { VT_W8(24) }
-    else vmw<32>();
+    else vm_wait<32>();
 #undef VT_W8
-}
-__device__ __forceinline__ void wg_barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
 }
 // n / d and n % d for 0 <= n < 2^31 by multiply-high with magic = min(ceil(2^32 / d), 2^32 - 1) and one correction each way
 __device__ __forceinline__ int div_magic(int n, int d, unsigned magic, int& rem) {
@@ -139,17 +103,6 @@ __host__ __device__ inline unsigned magic_of(int d) {
     const unsigned long long m = (0x100000000ull + (unsigned)d - 1) / (unsigned)d;
     return m > 0xffffffffull ? 0xffffffffu : (unsigned)m;
 }
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float x) {
-    return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float row_sum16(float x) {  // sum over the 16 lanes of a DPP row, in every lane of it
-    x = dpp_add<0x128>(x);
-    x = dpp_add<0x124>(x);
-    x = dpp_add<0x122>(x);
-    return dpp_add<0x121>(x);
-}
-
 // LDS map (bytes): [tap table 256][row tables 2 x (mask u32[BM] | output pixel i32[BM])][filter nsteps x BN x 64]
 //                  [span sets nbuf x set_bytes][zero block 64]
 template <int BM>
@@ -219,9 +172,9 @@ __global__ void __launch_bounds__(768, 3) pspan_kernel(const PsArgs a) {
                 const int cj = (lane & 3) ^ swz4(2 * q + (lane >> 5));
                 const unsigned voff = (unsigned)((n * p.ldw + cj * 8) * 2);
                 const char* sb = wg + ((long)a.t_rs[it] * p.Cin + (long)ic * 32) * 2;
-                glds_s(voff, sb, f_base + (unsigned)(id * 1024));
+                glds16_m0_written_sbase_rfl(voff, sb, f_base + (unsigned)(id * 1024));
                 if (++inflight == 24) {  // (the counter is 6 bits wide)
-                    vmw<8>();
+                    vm_wait<8>();
                     inflight = 8;
                 }
             }
@@ -324,7 +277,7 @@ __global__ void __launch_bounds__(768, 3) pspan_kernel(const PsArgs a) {
                             off -= dq + ((back1 && ((wrapm >> P) & 1u)) ? wrap : 0);
                             off = min(max(off, 0), maxoff48);
                         }
-                        glds_u((unsigned)off, sb, lds0 + (unsigned)(P * 4096));
+                        glds16_m0_written_sbase((unsigned)off, sb, lds0 + (unsigned)(P * 4096));
                     }
                 }
             }
@@ -373,7 +326,7 @@ __global__ void __launch_bounds__(768, 3) pspan_kernel(const PsArgs a) {
         // prologue: sets 0 .. nbuf-2, the first tile's tables; everything landed before barrier 0
         for (int g = 0; g < nbuf - 1 && g < G; ++g) issue_set(g);
         row_tables(0);
-        vmw<0>();
+        vm_wait<0>();
         wg_barrier();  // barrier 0
         for (int gc = 0; gc < G; ++gc) {
             // behind barrier gc: chunk gc-1 has been left by every compute wave, its buffer takes set gc + nbuf - 1
@@ -386,12 +339,12 @@ __global__ void __launch_bounds__(768, 3) pspan_kernel(const PsArgs a) {
             // set gc+1 (everything but this wave's share of the younger sets) has landed before barrier gc+1
             {
                 const int younger = min(nbuf - 2, max(0, G - 2 - gc));  // sets gc+2 .. issued so far
-                if (younger <= 0) vmw<0>();
+                if (younger <= 0) vm_wait<0>();
                 else vm_wait_dyn(younger * set_pieces);
             }
             wg_barrier();  // barrier gc + 1
         }
-        vmw<0>();
+        vm_wait<0>();
         set_m0(m0_keep);
         if (MODE == 1) wg_barrier();  // (the statistics fold below: every wave of the workgroup takes its barrier)
         return;

@@ -34,12 +34,14 @@
 
 #include "vt_common.h"
 #include "vt_igemm_args.h"
+#include "vt_lds_dma.h"
 
 namespace {
 
 constexpr int kTapBytes = 32 * 16;  // ntaps <= 32 on this path
 
-__device__ __attribute__((aligned(16))) unsigned int vt_span_zero16[4];
+// glds16_m0_saved, glds16_m0_saved_sbase, vm_wait<N>, lds_fence, mma<T> and the zero source vt_zero16: vt_lds_dma.h
+// The swizzle stays here because a diagnostic build swaps its table (with the shipped one it is swzA(row >> 2)):
 // chunk ^= 2 * ((row >> 2) & 1): the one 4-entry swizzle family (found by enumeration) under which a ds_read_b128 of
 // 16 consecutive 64-byte rows is conflict free for EVERY starting row -- a tap shifts the fragment rows by an
 // arbitrary offset; the table 0x1320 used before is conflict free only for offsets that are multiples of 4.
@@ -49,39 +51,9 @@ __device__ __attribute__((aligned(16))) unsigned int vt_span_zero16[4];
 #endif
 __device__ __forceinline__ int swz(int row) { return (VT_SPAN_SWZ_TABLE >> (((row >> 2) & 3) * 4)) & 3; }
 
-__device__ __forceinline__ void glds16(unsigned long gsrc, unsigned lds_base) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_base)
-        : "memory");
-}
-
-// same, SGPR base + per-lane 32-bit byte offset: no 64-bit VALU address arithmetic per instruction
-__device__ __forceinline__ void glds16s(unsigned voff, const void* sbase, unsigned lds_base) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 2\n\t"  // 5 wait states in all before a VMEM instruction may read a VALU-written (e.g. reloaded) SGPR base
-        "global_load_lds_dwordx4 %1, %2\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(sbase), "s"(lds_base)
-        : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// counted wait with a run-time count (wave-uniform): vmcnt takes an immediate
+// counted wait with a run-time count (wave-uniform): vmcnt takes an immediate.  A flat switch capped at 16 (a
+// larger count waits a little early): every wave of this kernel issues only its own share of two filter slices and one
+// span; the loader waves of span6 and pspan keep more in flight and carry deeper trees (caps 28 and 32).
 __device__ __forceinline__ void vm_wait_dyn(int n) {
     switch (n) {
         case 0: vm_wait<0>(); break;
@@ -102,23 +74,6 @@ __device__ __forceinline__ void vm_wait_dyn(int n) {
         case 15: vm_wait<15>(); break;
         default: vm_wait<16>(); break;
     }
-}
-
-__device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-template <typename T>
-__device__ __forceinline__ void mma(const uint4& a, const uint4& b, f32x4& acc);
-template <>
-__device__ __forceinline__ void mma<bf16_t>(const uint4& a, const uint4& b, f32x4& acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                  __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ void mma<float>(const uint4& a, const uint4& b, f32x4& acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
 }
 
 // LDS map (bytes): [taps 512][row masks BM*4][row output pixel BM*4][filter ring 3 x BROWS*64]
@@ -201,7 +156,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) span_kernel(const IgemmArgs p
     if (tid < 4) ((unsigned*)sZ)[tid] = 0u;
     const T* __restrict__ xg = (const T*)p.x;
     const T* __restrict__ wg = (const T*)p.w;
-    const unsigned long zero_src = (unsigned long)(const void*)vt_span_zero16;
+    const unsigned long zero_src = (unsigned long)(const void*)vt_zero16;
     const unsigned a_base = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)sA;
     const unsigned b_base = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)sB;
 
@@ -271,13 +226,13 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) span_kernel(const IgemmArgs p
         if (a_fast) {                                                                        \
             const char* sb = a_sbase + cofs;                                                 \
             for (int i = 0; i < ita; ++i)                                                    \
-                glds16s(a_voff0 + i * a_vstep, sb, a_base + (unsigned)(((sl)*aslot + (wave + NW * i) * 64) * 16)); \
+                glds16_m0_saved_sbase(a_voff0 + i * a_vstep, sb, a_base + (unsigned)(((sl)*aslot + (wave + NW * i) * 64) * 16)); \
             break;                                                                           \
         }                                                                                    \
         for (int i = 0; i < ita; ++i) {                                                      \
             const long pix = pix0 + 16l * NW * i;                                            \
             const unsigned long src = (pix >= 0 && pix < p.M) ? a_src0 + i * a_istep + cofs : zero_src; \
-            glds16(src, a_base + (unsigned)(((sl)*aslot + (wave + NW * i) * 64) * 16));      \
+            glds16_m0_saved(src, a_base + (unsigned)(((sl)*aslot + (wave + NW * i) * 64) * 16));      \
         }                                                                                    \
     } while (0)
     // S2: span of plane class q, channel chunk ic, into the class's own slot; returns the instructions issued.  A row
@@ -294,7 +249,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) span_kernel(const IgemmArgs p
             if (wave + NW * P < np) {
                 int off = s2_off[P] - dq - ((back1 && ((s2_wrap >> P) & 1u)) ? g.wrap : 0);
                 off = min(max(off, 0), g.maxoff + 48);  // (+48: the last position keeps its chunk position)
-                glds16s((unsigned)off, sb, lds0 + (unsigned)((wave + NW * P) * 1024));
+                glds16_m0_saved_sbase((unsigned)off, sb, lds0 + (unsigned)((wave + NW * P) * 1024));
                 ++n;
             }
         }
@@ -307,12 +262,12 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) span_kernel(const IgemmArgs p
         if (b_fast) {                                                                      \
             const char* sb = (const char*)wg + koff;                                       \
             _Pragma("unroll") for (int i = 0; i < ITB; ++i)                                \
-                glds16s(b_voff[i], sb, b_base + (unsigned)(((bslot)*BSLOT + (wave + NW * i) * 64) * 16)); \
+                glds16_m0_saved_sbase(b_voff[i], sb, b_base + (unsigned)(((bslot)*BSLOT + (wave + NW * i) * 64) * 16)); \
             break;                                                                         \
         }                                                                                  \
         _Pragma("unroll") for (int i = 0; i < ITB; ++i) {                                  \
             const unsigned long ps = bvalid[i] ? bbase[i] + koff : zero_src;               \
-            glds16(ps, b_base + (unsigned)(((bslot)*BSLOT + (wave + NW * i) * 64) * 16));  \
+            glds16_m0_saved(ps, b_base + (unsigned)(((bslot)*BSLOT + (wave + NW * i) * 64) * 16));  \
         }                                                                                  \
     } while (0)
     // (S2: step `it` of a chunk multiplies filter tap t_rs[it])

@@ -33,6 +33,7 @@
 
 #include "vt_common.h"
 #include "vt_igemm_args.h"
+#include "vt_lds_dma.h"
 
 #ifndef VT_SPAN6_FMX
 #define VT_SPAN6_FMX 7
@@ -71,8 +72,6 @@ __device__ unsigned long long vt_span6_pstamps[512 * 16];  // prologue detail (l
         if (VT_DBG(16) && lane == 0 && blockIdx.x < 512) vt_span6_pstamps[blockIdx.x * 16 + (k)] = wall_clock64(); \
     } while (0)
 
-__device__ __attribute__((aligned(16))) unsigned int vt_span6_zero16[4];  // source of every padding row
-
 struct S6Args {
     IgemmArgs p;
     int dmin, halo;  // span row of tap t = (eh*W + ew) - dmin, in [0, halo]
@@ -92,52 +91,21 @@ struct S6Args {
     int debug;       // dev ablations (VT_SPAN6_ABL): 1 no DMA in the loop, 2 no MFMA / reads, 4 no vmcnt wait, 16 stamps
 };
 
-__device__ __forceinline__ int swz4(int g) { return (0x1320 >> ((g & 3) * 4)) & 3; }  // filter-slice image
-// Span image: chunk ^= 2 * ((row >> 2) & 1).  A tap shifts the fragment's 16 rows by an arbitrary offset; this is the
-// swizzle (found by enumeration over all 4-entry tables) under which the four 16-lane groups of a ds_read_b128 hit 16
-// distinct 16-byte slots for EVERY row offset -- the 0x1320 table is conflict free only for offsets that are
-// multiples of 4 (2-way on half of the taps).
-__device__ __forceinline__ int swzA(int g) { return (g & 1) << 1; }
+// The LDS-DMA forms of the loaders (set_m0 + glds16_m0_preset / glds16_m0_preset_sbase_rfl, get_m0), vm_wait<N>, wg_barrier,
+// swz4 (filter-slice image), swzA (span image), row_sum16, I_<T> and the zero source vt_zero16: vt_lds_dma.h
 
-__device__ __forceinline__ const void* uniform_ptr(const void* p) {
-    const unsigned long v = (unsigned long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (const void*)(((unsigned long)hi << 32) | lo);
-}
-// LDS-DMA, 16 B per lane: LDS address = M0 + lane*16, global address = sbase + voff (or the per-lane address)
-// (s_nop 4: the scalar base may have just been written by a VALU instruction -- v_readfirstlane here, or a
-//  v_readlane reloading a spilled SGPR -- and a VMEM instruction reading such an SGPR needs 5 wait states, which
-//  hipcc does not insert in front of an asm statement.  Without it the load can use a stale base: a memory fault.)
-__device__ __forceinline__ void glds_s(unsigned voff, const void* sbase) {
-    asm volatile("s_nop 4\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(uniform_ptr(sbase)) : "memory");
-}
-__device__ __forceinline__ void glds_v(unsigned long gsrc) {
-    asm volatile("global_load_lds_dwordx4 %0, off" ::"v"(gsrc) : "memory");
-}
-__device__ __forceinline__ void set_m0(unsigned v) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(__builtin_amdgcn_readfirstlane(v)) : "memory");
-}
-__device__ __forceinline__ unsigned get_m0() {
-    unsigned v;
-    asm volatile("s_mov_b32 %0, m0" : "=s"(v)::"memory");
-    return v;
-}
-template <int N>
-__device__ __forceinline__ void vmw() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// counted wait with a run-time, wave-uniform count (vmcnt takes an immediate)
+// counted wait with a run-time, wave-uniform count (vmcnt takes an immediate).  Not vt_igemm_span.hip's flat switch (cap
+// 16): a loader counts both groups' span pieces and three slices, so this is a compare tree over groups of 4, capped at 28.
 __device__ __forceinline__ void vm_wait_dyn(int n) {
 #define VT_W4(b)                                  \
     switch (n - (b)) {                            \
-        case 0: vmw<(b) + 0>(); break;            \
-        case 1: vmw<(b) + 1>(); break;            \
-        case 2: vmw<(b) + 2>(); break;            \
-        default: vmw<(b) + 3>(); break;           \
+        case 0: vm_wait<(b) + 0>(); break;        \
+        case 1: vm_wait<(b) + 1>(); break;        \
+        case 2: vm_wait<(b) + 2>(); break;        \
+        default: vm_wait<(b) + 3>(); break;       \
     }
-    if (n <= 0) { vmw<0>(); return; }
-    if (n >= 28) { vmw<28>(); return; }  // (a loader never has more than ~12 in flight: larger counts wait a little early)
+    if (n <= 0) { vm_wait<0>(); return; }
+    if (n >= 28) { vm_wait<28>(); return; }  // (a loader never has more than ~12 in flight: larger counts wait a little early)
     if (n < 16) {
         if (n < 8) { if (n < 4) { VT_W4(0) } else { VT_W4(4) } }
         else { if (n < 12) { VT_W4(8) } else { VT_W4(12) } }
@@ -159,33 +127,11 @@ struct L6 {
     __host__ __device__ static constexpr int bytes(int npc, bool ksplit) { return a_off(ksplit) + 4 * npc * 1024; }
 };
 
-// sum of a value over the 16 lanes of its DPP row (lanes 16k .. 16k+15), returned in every lane of the row
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float x) {
-    return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float row_sum16(float x) {
-    x = dpp_add<0x128>(x);  // row_ror:8
-    x = dpp_add<0x124>(x);  // row_ror:4
-    x = dpp_add<0x122>(x);  // row_ror:2
-    return dpp_add<0x121>(x);  // row_ror:1
-}
-
-template <int T>
-using I_ = std::integral_constant<int, T>;
-
 typedef const __attribute__((address_space(4))) S6Args* ArgsPtr;
 __device__ __forceinline__ ArgsPtr fresh_args() {
     ArgsPtr q = (ArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(q));
     return q;
-}
-
-__device__ __forceinline__ void wg_barrier() {
-    __builtin_amdgcn_sched_barrier(0);  // nothing migrates across a tick boundary
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
 }
 
 // diagnostics: a barrier that adds the cycles this wave spent waiting in it to `w` (debug bit 16 only)
@@ -256,7 +202,7 @@ __global__ void __launch_bounds__(768, 3) span6_kernel(const S6Args a) {
     const long ldx2 = (long)p.ldx * 2;
     const int Mp = a.Mp, Wp = a.Wp, Hp = a.Hp, W_ = p.Wi, H_ = p.Hi;
     const unsigned wp_magic = a.wp_magic, hp_magic = a.hp_magic;
-    const unsigned long zero_src = (unsigned long)(const void*)vt_span6_zero16;
+    const unsigned long zero_src = (unsigned long)(const void*)vt_zero16;
 
     // Pixels are enumerated in PADDED coordinates: every image is (H+1) x (W+1) positions whose extra row and
     // column are zero pixels, so a tap is a constant offset in the flat padded index (the zero column right of
@@ -362,10 +308,10 @@ __global__ void __launch_bounds__(768, 3) span6_kernel(const S6Args a) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 set_m0(b_base + (unsigned)(slot * kBS + (2 * lj + i) * 1024));
-                glds_s(b_voff[i], sb);
+                glds16_m0_preset_sbase_rfl(b_voff[i], sb);
                 if constexpr (KSPLIT) {
                     set_m0(b_base + (unsigned)(slot * kBS + kBSlot + (2 * lj + i) * 1024));
-                    glds_s(b_voff[i], sb + koff);
+                    glds16_m0_preset_sbase_rfl(b_voff[i], sb + koff);
                 }
             }
         };
@@ -407,7 +353,7 @@ __global__ void __launch_bounds__(768, 3) span6_kernel(const S6Args a) {
                 for (int T = 0; T < 7; ++T)
                     if (lj + 4 * T < a.npc) {
                         set_m0(a_base + (unsigned)((g * 2) * aslot_bytes + (lj + 4 * T) * 1024));
-                        glds_v(ab_cur[g][T] + ((g == 1 && ((vm_cur[g] >> T) & 1u)) ? (unsigned long)koff : 0ul));
+                        glds16_m0_preset(ab_cur[g][T] + ((g == 1 && ((vm_cur[g] >> T) & 1u)) ? (unsigned long)koff : 0ul));
                     }
             }
             row_tables(0, 0, m0c[0]);
@@ -454,8 +400,8 @@ __global__ void __launch_bounds__(768, 3) span6_kernel(const S6Args a) {
                         constexpr int kYounger = (KSPLIT ? 8 : 4) + 2 * (P(T - 1) + P(T - 2));
                         // ---- even tick 2s: slice s (and everything older: both groups' spans of its chunk) has landed
                         if (!VT_DBG(4)) {
-                            if (sleft > 2 && sleft != S) vmw<kYounger>();
-                            else vmw<0>();  // (the first step: the prologue issued the slices before the spans)
+                            if (sleft > 2 && sleft != S) vm_wait<kYounger>();
+                            else vm_wait<0>();  // (the first step: the prologue issued the slices before the spans)
                         }
                         VT_TBAR(lwait);
                         if constexpr (T == 0 && kCwPro) {
@@ -479,7 +425,7 @@ __global__ void __launch_bounds__(768, 3) span6_kernel(const S6Args a) {
                             const unsigned long base = nx ? ab_nxt[0][T] : ab_cur[0][T];
                             const unsigned v = ((nx ? vm_nxt[0] : vm_cur[0]) >> T) & 1u;
                             set_m0(m0g[0] + T * 4096);
-                            glds_v(base + (v ? cb64 : 0ul));
+                            glds16_m0_preset(base + (v ? cb64 : 0ul));
                         }
                         // the next tiles' row tables, behind taps 6 (group 0) and 7 (group 1) of this tile's first chunk:
                         // the halves they go to were last read by the previous tiles' epilogues, which every compute
@@ -495,7 +441,7 @@ __global__ void __launch_bounds__(768, 3) span6_kernel(const S6Args a) {
                             const unsigned long base = nx ? ab_nxt[1][T] : ab_cur[1][T];
                             const unsigned v = ((nx ? vm_nxt[1] : vm_cur[1]) >> T) & 1u;
                             set_m0(m0g[1] + T * 4096);
-                            glds_v(base + (v ? cb64 + (unsigned long)koff : 0ul));
+                            glds16_m0_preset(base + (v ? cb64 + (unsigned long)koff : 0ul));
                         }
                         // group 1 has left its MFMA tick of step s-1 (whose second pair of filter fragments it read
                         // during that tick): the ring slot of slice s-1 takes slice s+3
@@ -504,14 +450,14 @@ __global__ void __launch_bounds__(768, 3) span6_kernel(const S6Args a) {
                             const char* sb = (T < 6 ? wb_cur : wb_nxt) + (long)(T3 * cin2);
                             const unsigned m0b = b_base + (unsigned)(bnext * kBS + 2 * lj * 1024);
                             set_m0(m0b);
-                            glds_s(b_voff[0], sb);
+                            glds16_m0_preset_sbase_rfl(b_voff[0], sb);
                             set_m0(m0b + 1024);
-                            glds_s(b_voff[1], sb);
+                            glds16_m0_preset_sbase_rfl(b_voff[1], sb);
                             if constexpr (KSPLIT) {
                                 set_m0(m0b + kBSlot);
-                                glds_s(b_voff[0], sb + koff);
+                                glds16_m0_preset_sbase_rfl(b_voff[0], sb + koff);
                                 set_m0(m0b + kBSlot + 1024);
-                                glds_s(b_voff[1], sb + koff);
+                                glds16_m0_preset_sbase_rfl(b_voff[1], sb + koff);
                             }
                         }
                         if (T == 7 && ic == 0 && has_next) {
@@ -553,7 +499,7 @@ __global__ void __launch_bounds__(768, 3) span6_kernel(const S6Args a) {
             vt_span6_stamps[blockIdx.x * 16 + 13] = lwait;
             vt_span6_stamps[blockIdx.x * 16 + 14] = clock64() - lc0;
         }
-        vmw<0>();
+        vm_wait<0>();
         if constexpr (KSPLIT) {
             wg_barrier();  // every LDS-DMA of this workgroup has landed: group 1 may overwrite the ring and the span slots
             wg_barrier();  // group 1's accumulators are in LDS
@@ -589,7 +535,7 @@ __global__ void __launch_bounds__(768, 3) span6_kernel(const S6Args a) {
         for (int T = 0; T < 7; ++T)
             if (lj + 4 * T < a.npc) {
                 set_m0(a_base + (unsigned)((grp * 2) * aslot_bytes + (lj + 4 * T) * 1024));
-                glds_v(ab0[T] + ((grp == 1 && ((vm0 >> T) & 1u)) ? (unsigned long)koff : 0ul));
+                glds16_m0_preset(ab0[T] + ((grp == 1 && ((vm0 >> T) & 1u)) ? (unsigned long)koff : 0ul));
             }
         if (wave == 0) VT_S6_PSTAMP(3);
         {  // the piece sources for loader lj (see the loader's prologue): its four first pieces of this group's second span slot
@@ -601,7 +547,7 @@ __global__ void __launch_bounds__(768, 3) span6_kernel(const S6Args a) {
             }
         }
         row_tables(grp, 0, m0g);
-        vmw<0>();  // landed before this wave's next barrier: group 0 reads the chunk in tick 0, group 1 in tick 1
+        vm_wait<0>();  // landed before this wave's next barrier: group 0 reads the chunk in tick 0, group 1 in tick 1
         set_m0(m0_keep);
         if (wave == 0) VT_S6_PSTAMP(4);
     }

@@ -19,12 +19,6 @@ namespace {
 constexpr int kT = 256;
 constexpr int kWaves = kT / 64;
 
-#define VT_TRY(expr)              \
-    do {                          \
-        int rc__ = (expr);        \
-        if (rc__ != VT_OK) return rc__; \
-    } while (0)
-
 __device__ __forceinline__ float group_sum(float v, int g) {
     for (int o = 1; o < g; o <<= 1) v += __shfl_xor(v, o, 64);
     return v;

@@ -30,22 +30,6 @@ constexpr int kT = 256;
 constexpr int kWaves = kT / 64;
 constexpr int kLdsMax = 160 * 1024;
 
-#define VT_DISPATCH_T(dtype, NAME, ...)                               \
-    do {                                                              \
-        if ((dtype) == VT_BF16) {                                     \
-            typedef bf16_t T;                                         \
-            __VA_ARGS__;                                              \
-        } else {                                                      \
-            typedef float T;                                          \
-            __VA_ARGS__;                                              \
-        }                                                             \
-    } while (0)
-#define VT_TRY(expr)              \
-    do {                          \
-        int rc__ = (expr);        \
-        if (rc__ != VT_OK) return rc__; \
-    } while (0)
-
 __device__ __forceinline__ float gelu_f(float u) { return 0.5f * u * (1.f + erff(u * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_d(float u) {
     return 0.5f * (1.f + erff(u * 0.70710678118654752f)) + u * 0.3989422804014327f * expf(-0.5f * u * u);

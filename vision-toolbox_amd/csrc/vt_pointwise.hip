@@ -62,7 +62,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 
 enum { PW_STATS = 0, PW_APPLY = 1, PW_REDUCE = 2, PW_BWD = 3 };

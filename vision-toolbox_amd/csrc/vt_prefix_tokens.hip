@@ -334,12 +334,6 @@ __global__ void __launch_bounds__(kT) prefix_pool_bwd_kernel(const T* __restrict
     }
 }
 
-#define VT_TRY(expr)                    \
-    do {                                \
-        int rc__ = (expr);              \
-        if (rc__ != VT_OK) return rc__; \
-    } while (0)
-
 int check_shape(const char* who, int C, int dtype, int P, bool in_registers) {
     VT_REQUIRE(dtype == VT_F32 || dtype == VT_BF16, VT_ERR_UNSUPPORTED, "%s: dtype %d", who, dtype);
     const int epc = vt_epc(dtype);

@@ -108,20 +108,6 @@ __host__ inline int fin_group(int C, int epc) {
     return 0;
 }
 
-#define VT_DISPATCH_T(dtype, NAME, ...)                               \
-    do {                                                              \
-        if ((dtype) == VT_BF16) {                                     \
-            typedef bf16_t T;                                         \
-            __VA_ARGS__;                                              \
-        } else if ((dtype) == VT_F32) {                               \
-            typedef float T;                                          \
-            __VA_ARGS__;                                              \
-        } else {                                                      \
-            vt_set_error("%s: unsupported dtype %d", NAME, (dtype)); \
-            return VT_ERR_UNSUPPORTED;                                \
-        }                                                             \
-    } while (0)
-
 inline int check_mat(const char* name, const void* p, int ld, int C, int dtype) {
     const int epc = vt_epc(dtype);
     if (!p || !vt_aligned16(p)) {
@@ -134,10 +120,4 @@ inline int check_mat(const char* name, const void* p, int ld, int C, int dtype) 
     }
     return VT_OK;
 }
-#define VT_TRY(expr)              \
-    do {                          \
-        int rc__ = (expr);        \
-        if (rc__ != VT_OK) return rc__; \
-    } while (0)
-
 }  // namespace

@@ -395,12 +395,6 @@ int plan(const char* who, SppGeo* g, int B, int H, int W, int C, int k, int repe
     return VT_OK;
 }
 
-#define VT_TRY(expr)                    \
-    do {                                \
-        int rc__ = (expr);              \
-        if (rc__ != VT_OK) return rc__; \
-    } while (0)
-
 #define VT_SPP_BY_K(LAUNCH, T, P)           \
     do {                                    \
         switch (k) {                        \

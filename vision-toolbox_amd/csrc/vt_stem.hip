@@ -18,25 +18,11 @@
 
 #include "vt_common.h"
 #include "vt_igemm_args.h"
+#include "vt_lds_dma.h"
 
 namespace {
 
-__device__ __attribute__((aligned(16))) unsigned int vt_stem_zero16[4];
-
-__device__ __forceinline__ void glds16(unsigned long gsrc, unsigned lds_base) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_base)
-        : "memory");
-}
-
-__device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// glds16_m0_saved, vm_wait<N>, lds_fence and the zero source vt_zero16: vt_lds_dma.h
 
 constexpr int kBM = 256;
 constexpr int kMaskOff = 0;             // 256 x 4 B
@@ -68,12 +54,12 @@ __global__ void __launch_bounds__(256) stem_kernel(const IgemmArgs p, const int 
 
     // ---- stage: input span by LDS-DMA, filter image and row masks by ordinary loads --------------
     const unsigned span_base = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)sSpan;
-    const unsigned long zero_src = (unsigned long)(const void*)vt_stem_zero16;
+    const unsigned long zero_src = (unsigned long)(const void*)vt_zero16;
     const bf* __restrict__ xg = (const bf*)p.x;
     for (int i = wave; i < span_instr; i += 4) {
         const long pix = m0 - W - 1 + 64l * i + lane;
         const unsigned long src = (pix >= 0 && pix < p.M) ? (unsigned long)(xg + pix * 8) : zero_src;
-        glds16(src, span_base + (unsigned)i * 1024u);
+        glds16_m0_saved(src, span_base + (unsigned)i * 1024u);
     }
     if (tid < 4) ((unsigned*)(smem + kZeroOff))[tid] = 0u;
     {
@@ -98,7 +84,7 @@ __global__ void __launch_bounds__(256) stem_kernel(const IgemmArgs p, const int 
         }
         sMask[r] = bits;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
     __syncthreads();
 
     // ---- 3 K-steps: one filter row each ---------------------------------------------------------
@@ -261,12 +247,12 @@ __global__ void __launch_bounds__(256, 4) stem_t_kernel(const IgemmArgs p, const
     // ---- stage: input span by LDS-DMA, filter image and padding masks by ordinary stores ------------------------
     const unsigned lds0 = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)smem;
     const unsigned span_base = lds0 + L::kSpanOff;
-    const unsigned long zero_src = (unsigned long)(const void*)vt_stem_zero16;
+    const unsigned long zero_src = (unsigned long)(const void*)vt_zero16;
     const bf* __restrict__ xg = (const bf*)p.x;
     for (int i = wave; i < span_instr; i += 4) {
         const long pix = m0 - W - 1 + 64l * i + lane;
         const unsigned long src = (pix >= 0 && pix < p.M) ? (unsigned long)(xg + pix * 8) : zero_src;
-        glds16(src, span_base + (unsigned)i * 1024u);
+        glds16_m0_saved(src, span_base + (unsigned)i * 1024u);
     }
     if (tid < 4) ((unsigned*)(smem + L::kZero))[tid] = 0u;
     {
@@ -317,7 +303,7 @@ __global__ void __launch_bounds__(256, 4) stem_t_kernel(const IgemmArgs p, const
                 sf[j][r] = p.shift[n];
             }
         }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
     __syncthreads();
 
     // filter fragments (A): row u of block j = channel 8*(u>>2) + 4j + (u&3); k chunk q = tap (e, q), q == 3 -> zeros

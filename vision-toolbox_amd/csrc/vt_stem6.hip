@@ -24,23 +24,11 @@
 
 #include "vt_common.h"
 #include "vt_igemm_args.h"
+#include "vt_lds_dma.h"
 
 namespace {
 
-__device__ __attribute__((aligned(16))) unsigned int vt_stem6_zero16[4];
-
-__device__ __forceinline__ void glds16(unsigned long gsrc, unsigned lds_base) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_base))
-        : "memory");
-}
+// glds16_m0_saved_rfl, vm_wait<N> and the zero source vt_zero16: vt_lds_dma.h
 
 constexpr int kTH = 4, kTW = 64;                       // output block: one row per wave x 64 columns
 constexpr int kPR = 2 * kTH + 4, kPC = 2 * kTW + 4;    // 12 x 132 input pixels, stored [row][column parity][66]
@@ -69,7 +57,7 @@ __global__ void __launch_bounds__(256, 2) stem6_kernel(const IgemmArgs p, const 
     const int g = lane >> 4, c16 = lane & 15;
     const unsigned w_base = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)smem;
     const unsigned patch_base = w_base + kWBytes;
-    const unsigned long zero_src = (unsigned long)(const void*)vt_stem6_zero16;
+    const unsigned long zero_src = (unsigned long)(const void*)vt_zero16;
     const bf16_t* __restrict__ xg = (const bf16_t*)p.x;
     const bf16_t* __restrict__ wg = (const bf16_t*)p.w;
     const int H = p.Hi, W = p.Wi;
@@ -81,7 +69,7 @@ __global__ void __launch_bounds__(256, 2) stem6_kernel(const IgemmArgs p, const 
         const int c = (slot & 3) ^ ((0x1320 >> (((R >> 2) & 3) * 4)) & 3);
         const bool ok = slot < kWSlots;
         const int ch = stem6_channel(R >> 4, R & 15);
-        glds16(ok ? (unsigned long)(wg + ((long)ch * p.ldw + (4 * s_ + c) * 8)) : zero_src, w_base + (unsigned)k * 1024u);
+        glds16_m0_saved_rfl(ok ? (unsigned long)(wg + ((long)ch * p.ldw + (4 * s_ + c) * 8)) : zero_src, w_base + (unsigned)k * 1024u);
     }
 
     // XCD-blocked block order: workgroups b, b + 8, ... share an XCD (and its L2) and walk one contiguous eighth of
@@ -103,7 +91,7 @@ __global__ void __launch_bounds__(256, 2) stem6_kernel(const IgemmArgs p, const 
             const int pc = 2 * (rem - par * kHalf) + par;
             const int ih = row0 + pr, iw = col0 + pc;
             const bool ok = slot < kPatchSlots && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
-            glds16(ok ? (unsigned long)(xg + (((long)b * H + ih) * W + iw) * 8) : zero_src, patch_base + (unsigned)k * 1024u);
+            glds16_m0_saved_rfl(ok ? (unsigned long)(xg + (((long)b * H + ih) * W + iw) * 8) : zero_src, patch_base + (unsigned)k * 1024u);
         }
     };
 
@@ -131,7 +119,7 @@ __global__ void __launch_bounds__(256, 2) stem6_kernel(const IgemmArgs p, const 
     int cur = tile_of(lt);
     if (cur >= 0) issue_patch(cur);
     while (cur >= 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vm_wait<0>();
         __syncthreads();  // this block's input (and, the first time, the filter) is in LDS
 
         f32x4 acc[4][5];
@@ -183,7 +171,7 @@ __global__ void __launch_bounds__(256, 2) stem6_kernel(const IgemmArgs p, const 
         }
         cur = nxt;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (a workgroup without blocks still has the filter in flight)
+    vm_wait<0>();  // (a workgroup without blocks still has the filter in flight)
 }
 
 }  // namespace

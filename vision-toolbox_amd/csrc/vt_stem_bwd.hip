@@ -48,8 +48,6 @@ struct SbArgs {
     unsigned magic_pw, magic_ph;
 };
 
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 struct Pos {  // a padded position, decomposed
     int b, i, j;
     __device__ __forceinline__ void init(long P, int S, int PW) {

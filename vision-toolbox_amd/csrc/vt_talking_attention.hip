@@ -853,14 +853,6 @@ __global__ void __launch_bounds__(256) token_prepend_param_kernel(const T* __res
     dparam[c] += sacc;
 }
 
-int check_rows(const char* who, const char* what, const void* ptr, int ld, int C, int dtype) {
-    VT_REQUIRE(ptr && vt_aligned16(ptr) && ld >= C && ld % vt_epc(dtype) == 0, VT_ERR_INVALID,
-               "%s: %s null, not 16-byte aligned, or its row stride %d is below %d channels / no multiple of a 16-byte chunk (%d "
-               "elements)",
-               who, what, ld, C, vt_epc(dtype));
-    return VT_OK;
-}
-
 int check_talk(const char* who, int B, int heads, int L, int head_dim, int dtype) {
     VT_REQUIRE(dtype == VT_F32 || dtype == VT_BF16, VT_ERR_INVALID, "%s: dtype %d", who, dtype);
     VT_REQUIRE(B > 0 && heads > 0 && L > 0 && head_dim > 0, VT_ERR_INVALID, "%s: B=%d heads=%d L=%d head_dim=%d", who, B, heads, L,
@@ -923,12 +915,6 @@ int launch_talk(K kern, int lds, const TalkArgs& p, hipStream_t st, const char* 
 
 }  // namespace
 
-#define VT_TRY(expr)                    \
-    do {                                \
-        const int rc__ = (expr);        \
-        if (rc__ != VT_OK) return rc__; \
-    } while (0)
-
 extern "C" {
 
 int vt_talk_attn_fwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv, void* o, int32_t ldo,
@@ -937,10 +923,10 @@ int vt_talk_attn_fwd(const void* q, int32_t ldq, const void* k, int32_t ldk, con
     const char* who = "vt_talk_attn_fwd";
     VT_TRY(check_talk(who, B, heads, L, head_dim, dtype));
     const int C = heads * head_dim;
-    VT_TRY(check_rows(who, "q", q, ldq, C, dtype));
-    VT_TRY(check_rows(who, "k", k, ldk, C, dtype));
-    VT_TRY(check_rows(who, "v", v, ldv, C, dtype));
-    VT_TRY(check_rows(who, "o", o, ldo, C, dtype));
+    VT_TRY(vt_check_rows(who, "q", q, ldq, C, dtype));
+    VT_TRY(vt_check_rows(who, "k", k, ldk, C, dtype));
+    VT_TRY(vt_check_rows(who, "v", v, ldv, C, dtype));
+    VT_TRY(vt_check_rows(who, "o", o, ldo, C, dtype));
     VT_REQUIRE(lse && wl && ww, VT_ERR_INVALID, "%s: lse, wl or ww null", who);
     TalkArgs p = {};
     p.q = q, p.k = k, p.v = v, p.out = o, p.lse = lse, p.wl = wl, p.bl = bl, p.ww = ww, p.bw = bw;
@@ -967,13 +953,13 @@ int vt_talk_attn_bwd(const void* q, int32_t ldq, const void* k, int32_t ldk, con
     const char* who = "vt_talk_attn_bwd";
     VT_TRY(check_talk(who, B, heads, L, head_dim, dtype));
     const int C = heads * head_dim;
-    VT_TRY(check_rows(who, "q", q, ldq, C, dtype));
-    VT_TRY(check_rows(who, "k", k, ldk, C, dtype));
-    VT_TRY(check_rows(who, "v", v, ldv, C, dtype));
-    VT_TRY(check_rows(who, "dout", dout, lddo, C, dtype));
-    if (dq) VT_TRY(check_rows(who, "dq", dq, lddq, C, dtype));
-    if (dk) VT_TRY(check_rows(who, "dk", dk, lddk, C, dtype));
-    if (dv) VT_TRY(check_rows(who, "dv", dv, lddv, C, dtype));
+    VT_TRY(vt_check_rows(who, "q", q, ldq, C, dtype));
+    VT_TRY(vt_check_rows(who, "k", k, ldk, C, dtype));
+    VT_TRY(vt_check_rows(who, "v", v, ldv, C, dtype));
+    VT_TRY(vt_check_rows(who, "dout", dout, lddo, C, dtype));
+    if (dq) VT_TRY(vt_check_rows(who, "dq", dq, lddq, C, dtype));
+    if (dk) VT_TRY(vt_check_rows(who, "dk", dk, lddk, C, dtype));
+    if (dv) VT_TRY(vt_check_rows(who, "dv", dv, lddv, C, dtype));
     const bool params = dwl || dbl || dww || dbw;
     VT_REQUIRE(dq || dk || dv || params, VT_ERR_INVALID, "%s: no output", who);
     VT_REQUIRE(lse && wl && ww, VT_ERR_INVALID, "%s: lse, wl or ww null", who);
@@ -1004,10 +990,10 @@ int vt_cls_attn_fwd(const void* q, int32_t ldq, const void* k, int32_t ldk, cons
     const char* who = "vt_cls_attn_fwd";
     VT_TRY(check_cls(who, B, heads, Lk, head_dim, dtype));
     const int C = heads * head_dim;
-    VT_TRY(check_rows(who, "q", q, ldq, C, dtype));
-    VT_TRY(check_rows(who, "k", k, ldk, C, dtype));
-    VT_TRY(check_rows(who, "v", v, ldv, C, dtype));
-    VT_TRY(check_rows(who, "o", o, ldo, C, dtype));
+    VT_TRY(vt_check_rows(who, "q", q, ldq, C, dtype));
+    VT_TRY(vt_check_rows(who, "k", k, ldk, C, dtype));
+    VT_TRY(vt_check_rows(who, "v", v, ldv, C, dtype));
+    VT_TRY(vt_check_rows(who, "o", o, ldo, C, dtype));
     VT_REQUIRE(lse, VT_ERR_INVALID, "%s: lse null", who);
     ClsArgs p = {};
     p.q = q, p.k = k, p.v = v, p.out = o, p.lse = lse;
@@ -1026,14 +1012,14 @@ int vt_cls_attn_bwd(const void* q, int32_t ldq, const void* k, int32_t ldk, cons
     const char* who = "vt_cls_attn_bwd";
     VT_TRY(check_cls(who, B, heads, Lk, head_dim, dtype));
     const int C = heads * head_dim;
-    VT_TRY(check_rows(who, "q", q, ldq, C, dtype));
-    VT_TRY(check_rows(who, "k", k, ldk, C, dtype));
-    VT_TRY(check_rows(who, "v", v, ldv, C, dtype));
-    VT_TRY(check_rows(who, "o", o, ldo, C, dtype));
-    VT_TRY(check_rows(who, "dout", dout, lddo, C, dtype));
-    if (dq) VT_TRY(check_rows(who, "dq", dq, lddq, C, dtype));
-    if (dk) VT_TRY(check_rows(who, "dk", dk, lddk, C, dtype));
-    if (dv) VT_TRY(check_rows(who, "dv", dv, lddv, C, dtype));
+    VT_TRY(vt_check_rows(who, "q", q, ldq, C, dtype));
+    VT_TRY(vt_check_rows(who, "k", k, ldk, C, dtype));
+    VT_TRY(vt_check_rows(who, "v", v, ldv, C, dtype));
+    VT_TRY(vt_check_rows(who, "o", o, ldo, C, dtype));
+    VT_TRY(vt_check_rows(who, "dout", dout, lddo, C, dtype));
+    if (dq) VT_TRY(vt_check_rows(who, "dq", dq, lddq, C, dtype));
+    if (dk) VT_TRY(vt_check_rows(who, "dk", dk, lddk, C, dtype));
+    if (dv) VT_TRY(vt_check_rows(who, "dv", dv, lddv, C, dtype));
     VT_REQUIRE(dq || dk || dv, VT_ERR_INVALID, "%s: no output", who);
     VT_REQUIRE(lse, VT_ERR_INVALID, "%s: lse null", who);
     ClsArgs p = {};

@@ -31,8 +31,6 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 constexpr int kMT = 64;        // output rows per workgroup
 constexpr int kCT = 64;        // channels per item
 constexpr int kKC = 128;       // reduction rows of x staged per step
@@ -455,12 +453,6 @@ int wgrad_splits(int tiles, int total) {
 }
 
 }  // namespace
-
-#define VT_TRY(expr)                  \
-    do {                              \
-        const int rc__ = (expr);      \
-        if (rc__ != VT_OK) return rc__; \
-    } while (0)
 
 extern "C" {
 

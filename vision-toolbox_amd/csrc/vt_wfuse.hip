@@ -259,12 +259,6 @@ unsigned grid_for(long items) {
     return (unsigned)(b < 1 ? 1 : b);
 }
 
-#define VT_TRY(expr)                    \
-    do {                                \
-        int rc__ = (expr);              \
-        if (rc__ != VT_OK) return rc__; \
-    } while (0)
-
 #define VT_WFUSE_DISPATCH(dtype, n, ...)                    \
     do {                                                    \
         if ((dtype) == VT_BF16) {                           \

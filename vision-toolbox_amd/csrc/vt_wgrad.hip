@@ -26,6 +26,7 @@
 #include <stdlib.h>
 
 #include "vt_common.h"
+#include "vt_lds_dma.h"
 
 namespace {
 
@@ -50,27 +51,7 @@ struct WgradArgs {
     float* dws[kWgMaxGroup];
 };
 
-__device__ __attribute__((aligned(16))) unsigned int vt_wg_zero16[4];
-
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-__device__ __forceinline__ void glds16(unsigned long gsrc, unsigned lds_base) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_base)
-        : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
+// glds16_m0_saved, vm_wait<N> and the zero source vt_zero16: vt_lds_dma.h
 
 constexpr int kTapHdr = VT_MAX_TAPS * 8;
 
@@ -125,7 +106,7 @@ __global__ void __launch_bounds__(256 * G) wgrad_kernel(const WgradArgs p) {
     const T* __restrict__ xg = (const T*)(p.nlayers > 1 ? p.xs[layer] : p.x);
     const T* __restrict__ zg = (const T*)(p.nlayers > 1 ? p.dzs[layer] : p.dz);
     float* __restrict__ dwg = p.nlayers > 1 ? p.dws[layer] : p.dw;
-    const unsigned long zero_src = (unsigned long)(const void*)vt_wg_zero16;
+    const unsigned long zero_src = (unsigned long)(const void*)vt_zero16;
     const unsigned ring_base = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)sRing +
                                (unsigned)(grp * kNS * STAGE * (int)sizeof(T));
 
@@ -194,7 +175,7 @@ __global__ void __launch_bounds__(256 * G) wgrad_kernel(const WgradArgs p) {
             const int jj = wave + 4 * i;                                                          \
             const bool mv = mrow[i] < m_end;                                                      \
             const unsigned long pz = (unsigned long)(zg + (unsigned)zoff[i]);                     \
-            glds16((mv && nvalid) ? pz : zero_src, ring_base + (unsigned)((((st)*STAGE) * (int)sizeof(T)) + jj * 1024)); \
+            glds16_m0_saved((mv && nvalid) ? pz : zero_src, ring_base + (unsigned)((((st)*STAGE) * (int)sizeof(T)) + jj * 1024)); \
             zoff[i] += zadv;                                                                      \
         }                                                                                         \
         _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                           \
@@ -202,7 +183,7 @@ __global__ void __launch_bounds__(256 * G) wgrad_kernel(const WgradArgs p) {
             if constexpr (kUnit) {                                                                \
                 const bool xv = mrow[i] < m_end && kvalid;                                        \
                 const unsigned long px = (unsigned long)(xg + (unsigned)xoff[i]);                 \
-                glds16(xv ? px : zero_src,                                                        \
+                glds16_m0_saved(xv ? px : zero_src,                                               \
                        ring_base + (unsigned)((((st)*STAGE + TILE) * (int)sizeof(T)) + jj * 1024)); \
                 mrow[i] += PKG;                                                                   \
                 xoff[i] += xadv_unit;                                                             \
@@ -210,7 +191,7 @@ __global__ void __launch_bounds__(256 * G) wgrad_kernel(const WgradArgs p) {
                 const bool xv = mrow[i] < m_end && kvalid && (unsigned)(hs[i] + tap_h) < (unsigned)p.Hi && \
                                 (unsigned)(ws[i] + tap_w) < (unsigned)p.Wi;                       \
                 const unsigned long px = (unsigned long)(xg + (unsigned)(xoff[i] + tap_off));     \
-                glds16(xv ? px : zero_src,                                                        \
+                glds16_m0_saved(xv ? px : zero_src,                                               \
                        ring_base + (unsigned)((((st)*STAGE + TILE) * (int)sizeof(T)) + jj * 1024)); \
                 mrow[i] += PKG;                                                                   \
                 /* PKG pixels ahead: at most one column wrap, then at most one row wrap (rH + 1 <= Ho) */ \

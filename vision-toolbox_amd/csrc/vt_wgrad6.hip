@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "vt_common.h"
+#include "vt_lds_dma.h"
 
 #ifndef VT_W6_SETPRIO
 #define VT_W6_SETPRIO 1  // 1: s_setprio(1) around a compute wave's MFMA tick (measured: see NOTEBOOK R6.8)
@@ -66,77 +67,23 @@ struct W6Args {
     long rowx;               // elements between image rows of x
 };
 
-__device__ __attribute__((aligned(16))) unsigned int vt_w6_zero16[4];
 #ifdef VT_W6_DIAG
 __device__ unsigned long long vt_w6_diag[256 * 16];  // per workgroup: [0..3] loader 0: barrier wait, loop, vmcnt wait, steps | [4..6] g0 wave 0: wait, read tick, mfma tick | [8..10] g1 wave 4
 #endif
 
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-__device__ __forceinline__ void w6_set_m0(unsigned v) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(__builtin_amdgcn_readfirstlane(v)) : "memory");
-}
-__device__ __forceinline__ unsigned w6_get_m0() {
-    unsigned v;
-    asm volatile("s_mov_b32 %0, m0" : "=s"(v)::"memory");
-    return v;
-}
-__device__ __forceinline__ void w6_glds(unsigned long gsrc) {
-    asm volatile("global_load_lds_dwordx4 %0, off" ::"v"(gsrc) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void w6_vmw() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void w6_barrier() {
-    __builtin_amdgcn_sched_barrier(0);  // nothing migrates across a tick boundary
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
+// The LDS-DMA form of the loaders (set_m0 + glds16_m0_preset, get_m0), vm_wait<N>, wg_barrier, Pos / PosStep<kStep>, I_<T>
+// and the zero source vt_zero16: vt_lds_dma.h
 
 #ifdef VT_W6_DIAG
 #define VT_W6_BAR(wacc)                              \
     do {                                             \
         const unsigned long long c0_ = clock64();    \
-        w6_barrier();                                \
+        wg_barrier();                                \
         (wacc) += clock64() - c0_;                   \
     } while (0)
 #else
-#define VT_W6_BAR(wacc) w6_barrier()
+#define VT_W6_BAR(wacc) wg_barrier()
 #endif
-
-struct W6Pos {  // a padded position, decomposed, and the element offset of its pixel
-    int b, i, j, off;
-    __device__ __forceinline__ void init(long P, int S, int PW, int H, long row, int ld) {
-        long bb = P / S;
-        long rem = P - bb * S;
-        if (rem < 0) rem += S, --bb;
-        b = (int)bb;
-        i = (int)(rem / PW);
-        j = (int)(rem - (long)i * PW);
-        off = (int)(((long)b * H + i) * row + (long)j * ld);  // (mod 2^32 while b < 0; exact for every real pixel)
-    }
-};
-struct W6PosStep {  // advance by kStep positions with additions only
-    int q, r;        // kStep = q * PW + r
-    int c0, c1, c2;  // offset deltas: kStep positions ahead | a column wrap | a row wrap (next image)
-    __device__ __forceinline__ void init(int PH, int PW, int H, long row, int ld) {
-        q = kStep / PW, r = kStep - q * PW;
-        c0 = (int)(r * (long)ld + q * row);
-        c1 = (int)(row - (long)PW * ld);
-        c2 = (int)((long)(H - PH) * row);
-    }
-    __device__ __forceinline__ void advance(W6Pos& p, int PH, int PW) const {
-        p.j += r, p.i += q, p.off += c0;
-        if (p.j >= PW) p.j -= PW, ++p.i, p.off += c1;
-        if (p.i >= PH) p.i -= PH, ++p.b, p.off += c2;
-        if (p.i >= PH) p.i -= PH, ++p.b, p.off += c2;  // (q + 1 < 2 PH: checked by the launcher)
-    }
-};
-
-template <int T>
-using I_ = std::integral_constant<int, T>;
 
 // 12 waves: 0-3 compute group 0 (taps 0..tgn-1), 4-7 compute group 1 (taps tgn..8), 8-11 loaders; three per SIMD
 template <int PD>
@@ -171,20 +118,20 @@ __global__ void __launch_bounds__(768, 3) wgrad6_kernel(const W6Args p) {
         // (l&7) ^ 2*((row>>1)&3).  Loader lj owns rows 16 lj .. 16 lj + 15 of every 64-row block: two instructions
         // (h = 0, 1) per operand and step.
         const int lj = wave - 8;
-        const unsigned m0_keep = w6_get_m0();
+        const unsigned m0_keep = get_m0();
         const int r8 = lane >> 3;
         const int srcc = (lane & 7) ^ (2 * ((r8 >> 1) & 3));
         const bool z_col_ok = n0 + srcc * 8 < p.Cout;
         const bool x_col_ok = c0 + srcc * 8 < p.Cin;
         const bf16_t* __restrict__ zb = p.dz[layer] + (n0 + srcc * 8);
         const bf16_t* __restrict__ xb = p.x[layer] + (c0 + srcc * 8);
-        const unsigned long zero_src = (unsigned long)(const void*)vt_w6_zero16;
+        const unsigned long zero_src = (unsigned long)(const void*)vt_zero16;
         const unsigned dz_base = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)sDz;
         const int B_ = p.B, H_ = p.H, W_ = p.W, PH_ = p.PH, PW_ = p.PW;
-        W6PosStep sz, sx;
+        PosStep<kStep> sz, sx;
         sz.init(PH_, PW_, H_, (long)W_ * p.ldy, p.ldy);
         sx.init(PH_, PW_, H_, p.rowx, p.ldx);
-        W6Pos pz[2], px[2];
+        Pos pz[2], px[2];
         int left[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -196,15 +143,15 @@ __global__ void __launch_bounds__(768, 3) wgrad6_kernel(const W6Args p) {
         const unsigned rowoff = (unsigned)(16 * lj) * 128u;
         auto issue_z = [&](int h, int slot) {
             const bool ok = z_col_ok && left[h] > 0 && (unsigned)pz[h].b < (unsigned)B_ && pz[h].i < H_ && pz[h].j < W_;
-            w6_set_m0(dz_base + (unsigned)(slot * kDzSlot) + rowoff + (unsigned)h * 1024u);
-            w6_glds(ok ? (unsigned long)(zb + (unsigned)pz[h].off) : zero_src);
+            set_m0(dz_base + (unsigned)(slot * kDzSlot) + rowoff + (unsigned)h * 1024u);
+            glds16_m0_preset(ok ? (unsigned long)(zb + (unsigned)pz[h].off) : zero_src);
             left[h] -= kStep;
             sz.advance(pz[h], PH_, PW_);
         };
         auto issue_x = [&](int h, int xc) {
             const bool ok = x_col_ok && (unsigned)px[h].b < (unsigned)B_ && px[h].i < H_ && px[h].j < W_;
-            w6_set_m0((((unsigned)xc * 8192u) & kRingMask) + rowoff + (unsigned)h * 1024u);
-            w6_glds(ok ? (unsigned long)(xb + (unsigned)px[h].off) : zero_src);
+            set_m0((((unsigned)xc * 8192u) & kRingMask) + rowoff + (unsigned)h * 1024u);
+            glds16_m0_preset(ok ? (unsigned long)(xb + (unsigned)px[h].off) : zero_src);
             sx.advance(px[h], PH_, PW_);
         };
         // ---- prologue: the halo chunks of x, then PD steps of both operands ----------------------------------
@@ -236,8 +183,8 @@ __global__ void __launch_bounds__(768, 3) wgrad6_kernel(const W6Args p) {
         VT_W6_T(unsigned long long lwait = 0, lvm = 0; const unsigned long long lt0 = clock64();)
         for (int s = 0; s < nsteps; ++s) {
             VT_W6_T(const unsigned long long v0_ = clock64();)
-            if (s + PD - 1 < nsteps) w6_vmw<4 * (PD - 1)>();  // the PD - 1 younger steps may stay in flight
-            else w6_vmw<0>();
+            if (s + PD - 1 < nsteps) vm_wait<4 * (PD - 1)>();  // the PD - 1 younger steps may stay in flight
+            else vm_wait<0>();
             VT_W6_T(lvm += clock64() - v0_;)
             VT_W6_BAR(lwait);
             const bool more = s + PD < nsteps && !VT_W6DBG(1);
@@ -253,9 +200,9 @@ __global__ void __launch_bounds__(768, 3) wgrad6_kernel(const W6Args p) {
             }
             zs = (zs + 1 == NS) ? 0 : zs + 1;
         }
-        w6_barrier();  // tick 2 nsteps: group 1's last MFMA tick
-        w6_vmw<0>();
-        w6_set_m0(m0_keep);
+        wg_barrier();  // tick 2 nsteps: group 1's last MFMA tick
+        vm_wait<0>();
+        set_m0(m0_keep);
 #ifdef VT_W6_DIAG
         if (lj == 0 && lane == 0 && blockIdx.x < 256) {
             vt_w6_diag[blockIdx.x * 16 + 0] = lwait, vt_w6_diag[blockIdx.x * 16 + 1] = clock64() - lt0;
@@ -290,7 +237,7 @@ __global__ void __launch_bounds__(768, 3) wgrad6_kernel(const W6Args p) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) acc[t][i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-        if (grp == 1) w6_barrier();  // tick 0: group 0 reads its first step
+        if (grp == 1) wg_barrier();  // tick 0: group 0 reads its first step
 
         auto run = [&](auto ntl_c) {
             constexpr int NTL = decltype(ntl_c)::value;
@@ -394,7 +341,7 @@ __global__ void __launch_bounds__(768, 3) wgrad6_kernel(const W6Args p) {
             case 4: run(I_<4>{}); break;
             default: run(I_<0>{}); break;  // (never launched: the launcher requires 9 taps, 5 | 4)
         }
-        if (grp == 0) w6_barrier();  // tick 2 nsteps: group 1's last MFMA tick
+        if (grp == 0) wg_barrier();  // tick 2 nsteps: group 1's last MFMA tick
 
         // ---- combine, part 1 happens below with all twelve waves ------------------------------------------------
         if (VT_W6DBG(8)) {

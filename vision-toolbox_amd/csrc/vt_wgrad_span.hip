@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "vt_common.h"
+#include "vt_lds_dma.h"
 
 #ifndef VT_WS_PD
 #define VT_WS_PD 2
@@ -62,61 +63,7 @@ struct WsArgs {
     signed char map[9][4];   // (-1: the column is dropped)
 };
 
-__device__ __attribute__((aligned(16))) unsigned int vt_ws_zero16[4];
-
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-__device__ __forceinline__ void glds16(unsigned long gsrc, unsigned lds_base_v) {
-    const unsigned lds_base = __builtin_amdgcn_readfirstlane(lds_base_v);  // (wave-uniform by construction)
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_base)
-        : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-struct Pos {  // a padded position, decomposed, and the element offset of its pixel; advanced 32 positions per step
-    int b, i, j, off;
-    __device__ __forceinline__ void init(long P, int S, int PW, int H, long row, int ld) {
-        long bb = P / S;
-        long rem = P - bb * S;
-        if (rem < 0) rem += S, --bb;
-        b = (int)bb;
-        i = (int)(rem / PW);
-        j = (int)(rem - (long)i * PW);
-        off = (int)(((long)b * H + i) * row + (long)j * ld);  // (mod 2^32 while b < 0; exact for every real pixel)
-    }
-};
-// The advance is additions only: round 2 recomputed (b, i, j) by multiply-high quotients and the offset by 64-bit
-// multiplies every step -- 18 quarter-rate integer multiplies among ~100 vector instructions per wave and step, against
-// 20 MFMAs: the loop was bound by vector issue (rocprofv3 PMC, 128 -> 128 @28x28: SQ_INSTS_VALU 22.4 M, SQ_INSTS_MFMA
-// 3.9 M, LDS array 16 % busy, no bank conflicts), not by the transposing reads.
-struct PosStep {
-    int q32, r32;    // 32 = q32 * PW + r32
-    int c0, c1, c2;  // offset deltas: 32 positions ahead | a column wrap | a row wrap (next image)
-    __device__ __forceinline__ void init(int PH, int PW, int H, long row, int ld) {
-        q32 = 32 / PW, r32 = 32 - q32 * PW;
-        c0 = (int)(r32 * (long)ld + q32 * row);
-        c1 = (int)(row - (long)PW * ld);
-        c2 = (int)((long)(H - PH) * row);
-    }
-    __device__ __forceinline__ void advance(Pos& p, int PH, int PW) const {
-        p.j += r32, p.i += q32, p.off += c0;
-        if (p.j >= PW) p.j -= PW, ++p.i, p.off += c1;
-        if (p.i >= PH) p.i -= PH, ++p.b, p.off += c2;
-        if (p.i >= PH) p.i -= PH, ++p.b, p.off += c2;  // (q32 + 1 < 2 PH: launch_ws_taps)
-    }
-};
+// glds16_m0_saved_rfl, vm_wait<N>, Pos / PosStep<32> (32 positions per step) and the zero source vt_zero16: vt_lds_dma.h
 
 constexpr int kDzSlot = 32 * 128;  // bytes: 32 positions x 64 channels
 
@@ -159,7 +106,7 @@ __global__ void __launch_bounds__(512, 1) wgrad_span_kernel(const WsArgs p) {
     if (Pbeg >= Pend) return;
     const int nsteps = (int)((Pend - Pbeg + 31) / 32);
 
-    const unsigned long zero_src = (unsigned long)(const void*)vt_ws_zero16;
+    const unsigned long zero_src = (unsigned long)(const void*)vt_zero16;
     const unsigned dz_base = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)sDz;
     const unsigned x_base = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)sX;
     const unsigned xmask = (unsigned)p.RX * 128u - 1u;
@@ -174,7 +121,7 @@ __global__ void __launch_bounds__(512, 1) wgrad_span_kernel(const WsArgs p) {
     const int src_ld = tg ? p.ldx : p.ldy;
     const long src_row = tg ? p.rowx : (long)p.W * p.ldy;
     Pos ps;
-    PosStep pst;
+    PosStep<32> pst;
     pst.init(p.PH, p.PW, p.H, src_row, src_ld);
     const long Ps0 = Pbeg + (tg ? p.dmin : 0) + 8 * wave + r8;  // this lane's stream position
     ps.init(Ps0, p.S, p.PW, p.H, src_row, src_ld);
@@ -185,7 +132,7 @@ __global__ void __launch_bounds__(512, 1) wgrad_span_kernel(const WsArgs p) {
 #define VT_WS_ISSUE(dst)                                                                          \
     do {                                                                                          \
         const bool ok = col_ok && left > 0 && (unsigned)ps.b < (unsigned)p.B && ps.i < p.H && ps.j < p.W; \
-        glds16(ok ? (unsigned long)(src_base + (unsigned)ps.off) : zero_src, (dst) + (unsigned)wave * 1024u); \
+        glds16_m0_saved_rfl(ok ? (unsigned long)(src_base + (unsigned)ps.off) : zero_src, (dst) + (unsigned)wave * 1024u); \
         ++nissued;                                                                                \
         if (!tg) left -= 32;                                                                      \
         pst.advance(ps, p.PH, p.PW);                                                              \

@@ -490,12 +490,6 @@ int win_check(const char* who, int B, int H, int W, int heads, int head_dim, int
 
 }  // namespace
 
-#define VT_TRY(expr)                    \
-    do {                                \
-        const int rc__ = (expr);        \
-        if (rc__ != VT_OK) return rc__; \
-    } while (0)
-
 extern "C" {
 
 int vt_win_attn_fwd(const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv, void* o, int32_t ldo,
