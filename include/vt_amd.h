@@ -1154,6 +1154,69 @@ int vt_adamw(float* p, const float* g, float* m, float* v, void* mirror, int32_t
              int64_t n, double beta1, double beta2, float eps, float weight_decay,
              float grad_scale, int32_t decoupled, const float* hyper, void* stream);
 
+/* ---- gradient norm, clipping, LAMB ----------------------------------------------------------------------------------
+ * Notation: g the flat gradient as backward left it, s = grad_scale (1 / world), N = s * sqrt(sum g^2) the norm of the
+ * averaged gradient; t, bc1 = 1 - beta1^t, sqrt(bc2) = sqrt(1 - beta2^t) as vt_adam_tick keeps them in `hyper`.
+ *
+ * A flat buffer is reduced in ITEMS of VT_OPT_ITEM elements: a workgroup turns an item into one double, written with a
+ * plain store, so no sum depends on the grid or the CU count and none uses a float atomic; results are bit-identical
+ * from run to run.  Whoever needs a total adds the partials of an earlier launch, in index order per lane and a fixed
+ * tree over the lanes, in double.
+ *
+ * vt_grad_sumsq:  partials[i] = sum of g^2 over item i, i < VT_OPT_ITEMS(n).  16-byte loads; any n > 0.
+ * vt_clip_coef:   one workgroup.  ctl is a device float[8] (16-byte aligned):
+ *     ctl[VT_CTL_CLIP]     C, the trainer-level threshold    (in)   a value <= 0, infinite or NaN means "off"
+ *     ctl[VT_CTL_LAMB_MAX] M, LAMB's max_grad_norm           (in)   likewise
+ *     ctl[VT_CTL_FACTOR]   s * c1 / c2                       (out)  what every consumer below multiplies g by
+ *     ctl[VT_CTL_NORM]     N                                 (out)
+ *   c1 = min(1, C / (N + 1e-6)) -- torch.nn.utils.clip_grad_norm_, i.e. Lightning's gradient_clip_val with the "norm"
+ *   algorithm; a NaN N gives a NaN c1, as torch does.  LAMB's own clip sees the clipped gradient: N' = c1 * N,
+ *   c2 = N' / M if N' > M else 1 (a false comparison, NaN included, gives 1).  Both off: the factor is exactly s.
+ * vt_sgd_momentum_clip / vt_adamw_clip: vt_sgd_momentum / vt_adamw with the device scalar coef[0] in the place of the
+ *   immediate grad_scale (coef = ctl + VT_CTL_FACTOR), same kernel bodies.
+ *
+ * LAMB, in the form of timm.optim.Lamb(bias_correction=True, grad_averaging=True).  timm is not a dependency and was
+ * not at hand: the form below was written down from memory of timm/optim/lamb.py and IS the definition for this
+ * library.  Per element, with g' = coef[0] * g:
+ *     m = beta1*m + (1-beta1)*g';   v = beta2*v + (1-beta2)*g'^2
+ *     u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + wd*p
+ * per parameter tensor, if wd != 0 or VT_LAMB_ALWAYS_ADAPT:  r = ||p|| / ||u|| where both norms are > 0, else 1;
+ * r = min(r, 1) with VT_LAMB_TRUST_CLIP; otherwise r = 1.  Then p -= lr * r * u and mirror = cast(p).
+ * (timm's default eps is 1e-6, not torch.optim.Adam's 1e-8.)
+ *
+ * The tensors come from a device table the host builds once: int32[n_segs][4] = (element offset, elements, first item,
+ * weight decay as float bits), followed by int32[n_items] = the segment of each item; 16-byte aligned.  Offsets and
+ * lengths are multiples of 64 (the flat store's slots), a segment of n elements owns VT_OPT_ITEMS(n) consecutive
+ * items, so an item never straddles two tensors.  The kernels check every entry against n_total, the length of the
+ * flat buffers, before they address anything with it; an unusable entry gets NaN partials and no update.
+ * vt_lamb_moments: reads p g m v, writes m v and partials[2*i], partials[2*i + 1] = sum p^2, sum u^2 of item i.
+ * vt_lamb_apply:   re-forms u from the new m, v and the unchanged p (the same inline function), adds the tensor's
+ *   partials in its prologue (every workgroup for itself), applies r, writes p and the mirror.  g is left alone.
+ * 42 bytes of traffic per parameter with a bf16 mirror (vt_adamw: 30).
+ * VT_ERR_INVALID: a null or misaligned p / g / m / v / table / partials, a null hyper / coef / ctl, counts <= 0. */
+#define VT_OPT_ITEM 4096
+#define VT_OPT_ITEMS(n) (((n) + VT_OPT_ITEM - 1) / VT_OPT_ITEM)
+#define VT_CTL_CLIP 0
+#define VT_CTL_LAMB_MAX 1
+#define VT_CTL_FACTOR 2
+#define VT_CTL_NORM 3
+#define VT_LAMB_TRUST_CLIP 1
+#define VT_LAMB_ALWAYS_ADAPT 2
+int32_t vt_opt_item(void); /* VT_OPT_ITEM of the built library */
+int vt_grad_sumsq(const float* g, int64_t n, double* partials, void* stream);
+int vt_clip_coef(const double* partials, int64_t n_items, float grad_scale, float* ctl, void* stream);
+int vt_sgd_momentum_clip(float* p, const float* g, float* m, void* mirror, int32_t mirror_dtype, int64_t n, float lr,
+                         float momentum, float weight_decay, const float* coef, const float* lr_dev, void* stream);
+int vt_adamw_clip(float* p, const float* g, float* m, float* v, void* mirror, int32_t mirror_dtype, int64_t n,
+                  double beta1, double beta2, float eps, float weight_decay, const float* coef, int32_t decoupled,
+                  const float* hyper, void* stream);
+int vt_lamb_moments(const float* p, const float* g, float* m, float* v, const int32_t* table, int32_t n_segs,
+                    int64_t n_items, int64_t n_total, double* partials, const float* coef, double beta1, double beta2,
+                    float eps, int32_t flags, const float* hyper, void* stream);
+int vt_lamb_apply(float* p, const float* m, const float* v, void* mirror, int32_t mirror_dtype, const int32_t* table,
+                  int32_t n_segs, int64_t n_items, int64_t n_total, const double* partials, float eps, int32_t flags,
+                  const float* hyper, void* stream);
+
 /* ---- layout / precision plumbing ---------------------------------------- */
 /* rows x cols block copy with dtype conversion: dst (=|+=) src */
 int vt_copy2d(const void* src, int32_t src_dtype, int64_t lds, void* dst, int32_t dst_dtype,
@@ -1293,6 +1356,12 @@ enum vt_op_kind {
     VT_OP_DEFORM_FWD,               /* vt_deform_fwd */
     VT_OP_DEFORM_BWD,               /* vt_deform_bwd */
     VT_OP_DEFORM_WGRAD,             /* vt_deform_wgrad */
+    VT_OP_GRAD_SUMSQ,               /* vt_grad_sumsq */
+    VT_OP_CLIP_COEF,                /* vt_clip_coef */
+    VT_OP_SGD_CLIP,                 /* vt_sgd_momentum_clip */
+    VT_OP_ADAMW_CLIP,               /* vt_adamw_clip */
+    VT_OP_LAMB_MOMENTS,             /* vt_lamb_moments */
+    VT_OP_LAMB_APPLY,               /* vt_lamb_apply */
     VT_OP_KIND_END
 };
 

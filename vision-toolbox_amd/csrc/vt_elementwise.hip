@@ -1143,11 +1143,15 @@ xent_kernel(const T* __restrict__ logits, int ldl, const int64_t* __restrict__ l
 // ---------------------------------------------------------------------------------
 // SGD with momentum over a flat f32 buffer (+ optional low-precision mirror)
 // ---------------------------------------------------------------------------------
-template <typename MT>
+// kClip: the gradient factor is the device scalar coef[0] (vt_clip_coef's output) instead of the immediate gs; the
+// plain kernels are the kClip = false instances, where the branch and the operand compile out
+template <typename MT, bool kClip = false>
 __global__ void __launch_bounds__(kThreads)
 sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, MT* __restrict__ mirror,
-           long n, float lr, float mu, float wd, float gs, const float* __restrict__ lr_dev) {
+           long n, float lr, float mu, float wd, float gs, const float* __restrict__ lr_dev,
+           const float* __restrict__ coef = nullptr) {
     if (lr_dev) lr = lr_dev[0];
+    if constexpr (kClip) gs = coef[0];
     const long stride = (long)gridDim.x * kThreads * 4;
     for (long i = ((long)blockIdx.x * kThreads + threadIdx.x) * 4; i < n; i += stride) {
         if (i + 4 <= n) {
@@ -1220,10 +1224,12 @@ __device__ static inline void adam_update(float& p, float g, float& m, float& v,
     p = fmaf(-step, m / denom, p);
 }
 
-template <typename MT>
+template <typename MT, bool kClip = false>
 __global__ void __launch_bounds__(kThreads)
 adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-             MT* __restrict__ mirror, long n, AdamScalars a, const float* __restrict__ hyper) {
+             MT* __restrict__ mirror, long n, AdamScalars a, const float* __restrict__ hyper,
+             const float* __restrict__ coef = nullptr) {
+    if constexpr (kClip) a.gs = coef[0];
     const float lr = hyper[0];
     const float step = lr / hyper[5];  // lr / (1 - beta1^t)
     const float bc2s = hyper[6];       // sqrt(1 - beta2^t)
@@ -1434,6 +1440,58 @@ inline unsigned flat_blocks(long total, int per_thread = 1) {
     if (b > 8192) b = 8192;
     if (b < 1) b = 1;
     return (unsigned)b;
+}
+
+// the optimiser entry points and their clipped twins (templates: C++ linkage, so they live here)
+template <bool kClip>
+int sgd_entry(const char* who, float* p, const float* g, float* m, void* mirror, int32_t mirror_dtype, int64_t n,
+                     float lr, float momentum, float weight_decay, float grad_scale, const float* coef,
+                     const float* lr_dev, void* stream) {
+    VT_REQUIRE(p && g && m && n > 0 && (!kClip || coef), VT_ERR_INVALID, "%s: bad argument", who);
+    VT_REQUIRE(vt_aligned16(p) && vt_aligned16(g) && vt_aligned16(m), VT_ERR_INVALID,
+               "%s: p/g/m must be 16-byte aligned", who);
+    const unsigned blocks = flat_blocks(n, 4);
+    if (mirror && mirror_dtype == VT_BF16)
+        hipLaunchKernelGGL((sgd_kernel<bf16_t, kClip>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, p, g, m,
+                           (bf16_t*)mirror, (long)n, lr, momentum, weight_decay, grad_scale, lr_dev, coef);
+    else if (mirror && mirror_dtype != VT_F32) {
+        vt_set_error("%s: mirror dtype %d", who, mirror_dtype);
+        return VT_ERR_UNSUPPORTED;
+    } else
+        hipLaunchKernelGGL((sgd_kernel<float, kClip>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, p, g, m,
+                           (float*)mirror, (long)n, lr, momentum, weight_decay, grad_scale, lr_dev, coef);
+    VT_CHECK_LAUNCH(who);
+    return VT_OK;
+}
+
+template <bool kClip>
+int adamw_entry(const char* who, float* p, const float* g, float* m, float* v, void* mirror, int32_t mirror_dtype,
+                       int64_t n, double beta1, double beta2, float eps, float weight_decay, float grad_scale,
+                       const float* coef, int32_t decoupled, const float* hyper, void* stream) {
+    VT_REQUIRE(p && g && m && v && hyper && n > 0 && (!kClip || coef), VT_ERR_INVALID, "%s: bad argument", who);
+    VT_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.f, VT_ERR_INVALID,
+               "%s: betas in [0, 1), eps >= 0", who);
+    VT_REQUIRE(vt_aligned16(p) && vt_aligned16(g) && vt_aligned16(m) && vt_aligned16(v), VT_ERR_INVALID,
+               "%s: p/g/m/v must be 16-byte aligned", who);
+    const bool bf = mirror && mirror_dtype == VT_BF16;
+    if (mirror && !bf && mirror_dtype != VT_F32) {
+        vt_set_error("%s: mirror dtype %d", who, mirror_dtype);
+        return VT_ERR_UNSUPPORTED;
+    }
+    VT_REQUIRE(!mirror || ((uintptr_t)mirror & (bf ? 7 : 15)) == 0, VT_ERR_INVALID,
+               "%s: the mirror must be aligned to four of its elements", who);
+    AdamScalars a;
+    a.beta1 = (float)beta1, a.omb1 = (float)(1.0 - beta1), a.beta2 = (float)beta2, a.omb2 = (float)(1.0 - beta2);
+    a.eps = eps, a.wd = weight_decay, a.gs = grad_scale, a.decoupled = decoupled ? 1 : 0;
+    const unsigned blocks = flat_blocks(n, 4);
+    if (bf)
+        hipLaunchKernelGGL((adamw_kernel<bf16_t, kClip>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, p, g, m, v,
+                           (bf16_t*)mirror, (long)n, a, hyper, coef);
+    else
+        hipLaunchKernelGGL((adamw_kernel<float, kClip>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, p, g, m, v,
+                           (float*)mirror, (long)n, a, hyper, coef);
+    VT_CHECK_LAUNCH(who);
+    return VT_OK;
 }
 
 }  // namespace
@@ -1969,21 +2027,14 @@ int vt_softmax_xent_mix(const void* logits, int32_t ldl, const int64_t* labels, 
 int vt_sgd_momentum(float* p, const float* g, float* m, void* mirror, int32_t mirror_dtype, int64_t n,
                     float lr, float momentum, float weight_decay, float grad_scale, const float* lr_dev,
                     void* stream) {
-    VT_REQUIRE(p && g && m && n > 0, VT_ERR_INVALID, "vt_sgd_momentum: bad argument");
-    VT_REQUIRE(vt_aligned16(p) && vt_aligned16(g) && vt_aligned16(m), VT_ERR_INVALID,
-               "vt_sgd_momentum: p/g/m must be 16-byte aligned");
-    const unsigned blocks = flat_blocks(n, 4);
-    if (mirror && mirror_dtype == VT_BF16)
-        hipLaunchKernelGGL(sgd_kernel<bf16_t>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, p, g, m,
-                           (bf16_t*)mirror, (long)n, lr, momentum, weight_decay, grad_scale, lr_dev);
-    else if (mirror && mirror_dtype != VT_F32) {
-        vt_set_error("vt_sgd_momentum: mirror dtype %d", mirror_dtype);
-        return VT_ERR_UNSUPPORTED;
-    } else
-        hipLaunchKernelGGL(sgd_kernel<float>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, p, g, m,
-                           (float*)mirror, (long)n, lr, momentum, weight_decay, grad_scale, lr_dev);
-    VT_CHECK_LAUNCH("vt_sgd_momentum");
-    return VT_OK;
+    return sgd_entry<false>("vt_sgd_momentum", p, g, m, mirror, mirror_dtype, n, lr, momentum, weight_decay, grad_scale,
+                            nullptr, lr_dev, stream);
+}
+
+int vt_sgd_momentum_clip(float* p, const float* g, float* m, void* mirror, int32_t mirror_dtype, int64_t n, float lr,
+                         float momentum, float weight_decay, const float* coef, const float* lr_dev, void* stream) {
+    return sgd_entry<true>("vt_sgd_momentum_clip", p, g, m, mirror, mirror_dtype, n, lr, momentum, weight_decay, 0.f,
+                           coef, lr_dev, stream);
 }
 
 int vt_adam_tick(float* hyper, double beta1, double beta2, void* stream) {
@@ -1997,30 +2048,15 @@ int vt_adam_tick(float* hyper, double beta1, double beta2, void* stream) {
 int vt_adamw(float* p, const float* g, float* m, float* v, void* mirror, int32_t mirror_dtype, int64_t n,
              double beta1, double beta2, float eps, float weight_decay, float grad_scale, int32_t decoupled,
              const float* hyper, void* stream) {
-    VT_REQUIRE(p && g && m && v && hyper && n > 0, VT_ERR_INVALID, "vt_adamw: bad argument");
-    VT_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.f, VT_ERR_INVALID,
-               "vt_adamw: betas in [0, 1), eps >= 0");
-    VT_REQUIRE(vt_aligned16(p) && vt_aligned16(g) && vt_aligned16(m) && vt_aligned16(v), VT_ERR_INVALID,
-               "vt_adamw: p/g/m/v must be 16-byte aligned");
-    const bool bf = mirror && mirror_dtype == VT_BF16;
-    if (mirror && !bf && mirror_dtype != VT_F32) {
-        vt_set_error("vt_adamw: mirror dtype %d", mirror_dtype);
-        return VT_ERR_UNSUPPORTED;
-    }
-    VT_REQUIRE(!mirror || ((uintptr_t)mirror & (bf ? 7 : 15)) == 0, VT_ERR_INVALID,
-               "vt_adamw: the mirror must be aligned to four of its elements");
-    AdamScalars a;
-    a.beta1 = (float)beta1, a.omb1 = (float)(1.0 - beta1), a.beta2 = (float)beta2, a.omb2 = (float)(1.0 - beta2);
-    a.eps = eps, a.wd = weight_decay, a.gs = grad_scale, a.decoupled = decoupled ? 1 : 0;
-    const unsigned blocks = flat_blocks(n, 4);
-    if (bf)
-        hipLaunchKernelGGL(adamw_kernel<bf16_t>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, p, g, m, v,
-                           (bf16_t*)mirror, (long)n, a, hyper);
-    else
-        hipLaunchKernelGGL(adamw_kernel<float>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, p, g, m, v,
-                           (float*)mirror, (long)n, a, hyper);
-    VT_CHECK_LAUNCH("vt_adamw");
-    return VT_OK;
+    return adamw_entry<false>("vt_adamw", p, g, m, v, mirror, mirror_dtype, n, beta1, beta2, eps, weight_decay, grad_scale,
+                              nullptr, decoupled, hyper, stream);
+}
+
+int vt_adamw_clip(float* p, const float* g, float* m, float* v, void* mirror, int32_t mirror_dtype, int64_t n,
+                  double beta1, double beta2, float eps, float weight_decay, const float* coef, int32_t decoupled,
+                  const float* hyper, void* stream) {
+    return adamw_entry<true>("vt_adamw_clip", p, g, m, v, mirror, mirror_dtype, n, beta1, beta2, eps, weight_decay, 0.f,
+                             coef, decoupled, hyper, stream);
 }
 
 int vt_copy2d(const void* src, int32_t src_dtype, int64_t lds, void* dst, int32_t dst_dtype, int64_t ldd,

@@ -484,6 +484,23 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
         case VT_OP_ADAMW:  // ptr: p g m v mirror hyper | i: mirror_dtype decoupled | f: n beta1 beta2 eps wd grad_scale
             return vt_adamw((float*)P[0], (const float*)P[1], (float*)P[2], (float*)P[3], P[4], I[0], (int64_t)F[0], F[1],
                             F[2], (float)F[3], (float)F[4], (float)F[5], I[1], (const float*)P[5], st);
+        case VT_OP_GRAD_SUMSQ:  // ptr: g partials | f: n
+            return vt_grad_sumsq((const float*)P[0], (int64_t)F[0], (double*)P[1], st);
+        case VT_OP_CLIP_COEF:  // ptr: partials ctl | f: n_items grad_scale
+            return vt_clip_coef((const double*)P[0], (int64_t)F[0], (float)F[1], (float*)P[1], st);
+        case VT_OP_SGD_CLIP:  // ptr: p g m mirror lr_dev coef | i: mirror_dtype | f: n lr momentum wd
+            return vt_sgd_momentum_clip((float*)P[0], (const float*)P[1], (float*)P[2], P[3], I[0], (int64_t)F[0], (float)F[1],
+                                        (float)F[2], (float)F[3], (const float*)P[5], (const float*)P[4], st);
+        case VT_OP_ADAMW_CLIP:  // ptr: p g m v mirror hyper coef | i: mirror_dtype decoupled | f: n beta1 beta2 eps wd
+            return vt_adamw_clip((float*)P[0], (const float*)P[1], (float*)P[2], (float*)P[3], P[4], I[0], (int64_t)F[0], F[1],
+                                 F[2], (float)F[3], (float)F[4], (const float*)P[6], I[1], (const float*)P[5], st);
+        case VT_OP_LAMB_MOMENTS:  // ptr: p g m v table partials coef hyper | i: n_segs flags | f: n_items n_total beta1 beta2 eps
+            return vt_lamb_moments((const float*)P[0], (const float*)P[1], (float*)P[2], (float*)P[3], (const int32_t*)P[4], I[0],
+                                   (int64_t)F[0], (int64_t)F[1], (double*)P[5], (const float*)P[6], F[2], F[3], (float)F[4], I[1],
+                                   (const float*)P[7], st);
+        case VT_OP_LAMB_APPLY:  // ptr: p m v mirror table partials hyper | i: mirror_dtype n_segs flags | f: n_items n_total eps
+            return vt_lamb_apply((float*)P[0], (const float*)P[1], (const float*)P[2], P[3], I[0], (const int32_t*)P[4], I[1],
+                                 (int64_t)F[0], (int64_t)F[1], (const double*)P[5], (float)F[2], I[2], (const float*)P[6], st);
         case VT_OP_COPY2D:  // ptr: src dst | i: src_dtype dst_dtype cols accumulate | f: lds ldd rows
             return vt_copy2d(P[0], I[0], (int64_t)F[0], P[1], I[1], (int64_t)F[1], (int64_t)F[2], I[2], I[3], st);
         case VT_OP_NCHW_TO_NHWC:  // ptr: x y [mix] | i: B C H W Cpad dtype

@@ -19,8 +19,32 @@ VT_F32, VT_BF16, VT_I64 = 0, 1, 2  # (VT_I64: collectives only)
 VT_MAX_TAPS = 36
 VT_CONV_RELU, VT_CONV_STATS, VT_CONV_RESIDUAL, VT_CONV_AFFINE, VT_CONV_D2S, VT_CONV_NOSTORE = 1, 2, 4, 8, 16, 32
 VT_STAT_REPLICAS = 16
+# gradient norm / clipping / LAMB (vt_amd.h): the item of every deterministic sum, the slots of the control buffer, flags
+VT_OPT_ITEM = 4096
+VT_CTL_CLIP, VT_CTL_LAMB_MAX, VT_CTL_FACTOR, VT_CTL_NORM = 0, 1, 2, 3
+VT_LAMB_TRUST_CLIP, VT_LAMB_ALWAYS_ADAPT = 1, 2
 # a statistics buffer is int64[VT_STAT_REPLICAS][2][C][2]: value = hi * 2^12 + lo / 2^33 (vt_amd.h)
 STAT_MARKER = 1 << 40  # what a non-finite or |v| >= 2^50 contribution adds to the hi limb instead of its value
+
+
+def opt_items(n: int) -> int:
+    """items of a flat buffer of n elements (VT_OPT_ITEMS)"""
+    return (n + VT_OPT_ITEM - 1) // VT_OPT_ITEM
+
+
+def lamb_table(offsets, sizes, wds):
+    """the host side of the LAMB work table (vt_amd.h): segments (element offset, elements, weight decay) -> (int32 array
+    [n_segs * 4 + n_items], n_items).  Offsets and sizes are multiples of 64."""
+    import numpy as np
+
+    segs = np.zeros((len(offsets), 4), dtype=np.int32)
+    item_seg = []
+    for k, (o, n, wd) in enumerate(zip(offsets, sizes, wds)):
+        if o < 0 or n <= 0 or o % 64 or n % 64:
+            raise ValueError(f"lamb_table: segment {k} = ({o}, {n}): offsets and sizes are positive multiples of 64")
+        segs[k] = (o, n, len(item_seg), np.float32(wd).view(np.int32))
+        item_seg += [k] * opt_items(n)
+    return np.concatenate([segs.reshape(-1), np.asarray(item_seg, dtype=np.int32)]), len(item_seg)
 
 
 def stat_floats(C_: int) -> int:
@@ -177,7 +201,13 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_DEFORM_FWD,
     OP_DEFORM_BWD,
     OP_DEFORM_WGRAD,
-) = range(1, 116)
+    OP_GRAD_SUMSQ,
+    OP_CLIP_COEF,
+    OP_SGD_CLIP,
+    OP_ADAMW_CLIP,
+    OP_LAMB_MOMENTS,
+    OP_LAMB_APPLY,
+) = range(1, 122)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -277,6 +307,12 @@ OP_NAMES = {
     OP_DEFORM_FWD: "deform_fwd",
     OP_DEFORM_BWD: "deform_bwd",
     OP_DEFORM_WGRAD: "deform_wgrad",
+    OP_GRAD_SUMSQ: "grad_sumsq",
+    OP_CLIP_COEF: "clip_coef",
+    OP_SGD_CLIP: "sgd_clip",
+    OP_ADAMW_CLIP: "adamw_clip",
+    OP_LAMB_MOMENTS: "lamb_moments",
+    OP_LAMB_APPLY: "lamb_apply",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -557,6 +593,13 @@ SYMBOLS = {
     "vt_sgd_momentum": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _f32, _f32, _f32, _f32, _vp, _vp]),
     "vt_adam_tick": (_i32, [_vp, _f64, _f64, _vp]),
     "vt_adamw": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _f64, _f64, _f32, _f32, _f32, _i32, _vp, _vp]),
+    "vt_opt_item": (_i32, []),
+    "vt_grad_sumsq": (_i32, [_vp, _i64, _vp, _vp]),
+    "vt_clip_coef": (_i32, [_vp, _i64, _f32, _vp, _vp]),
+    "vt_sgd_momentum_clip": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _f32, _f32, _f32, _vp, _vp, _vp]),
+    "vt_adamw_clip": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _f64, _f64, _f32, _f32, _vp, _i32, _vp, _vp]),
+    "vt_lamb_moments": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _vp, _vp, _f64, _f64, _f32, _i32, _vp, _vp]),
+    "vt_lamb_apply": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i64, _vp, _f32, _i32, _vp, _vp]),
     "vt_copy2d": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i64, _i32, _i32, _vp]),
     "vt_nchw_to_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_nhwc_to_nchw": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -10,7 +10,8 @@ program per rank:
            -> bucketed gradient all-reduce (RCCL over xGMI); each bucket is issued as soon
               as the backward segment that completes it has been enqueued
            -> the optimiser over the flat buffers, which also refreshes the bf16 weights: SGD(momentum), or
-              AdamW / Adam (optimizer=...; the step count lives on the device, see _emit_opt)
+              AdamW / Adam / Lamb (optimizer=...; the step count lives on the device, see _emit_opt), optionally behind
+              a clip of the global gradient norm (clip_grad_norm=...; the norm is formed on the device, see _emit_opt)
 
 The step is one launch list cut into segments at the bucket boundaries; every segment runs
 through the native executor on two streams (main + filter-gradient side stream, left open
@@ -44,10 +45,14 @@ from .program import Program, current_stream_handle, draw_keep_factors
 
 _NORMS = (nn.modules.batchnorm._BatchNorm, nn.modules.instancenorm._InstanceNorm, nn.LayerNorm, nn.GroupNorm)
 GROUP_NORM, GROUP_BIAS, GROUP_OTHER = 0, 1, 2  # flat-buffer order: small, late-produced groups first
-OPTIMIZERS = ("SGD", "AdamW", "Adam")  # classifier.py:46,157-169 takes the name; RMSprop and the timm names are not built
+# classifier.py:46,157-169 takes the name.  RMSprop is not built; of the timm names (classifier.py:165) only Lamb is
+OPTIMIZERS = ("SGD", "AdamW", "Adam", "Lamb")
 # HYPER buffer (16 floats): [0..3] learning rate; [4] optimiser step count t (int32 bits), [5] 1 - beta1^t,
 # [6] sqrt(1 - beta2^t), [7] free (vt_adam_tick / vt_adamw); [8..15] MixUp / CutMix block
 HYPER_STEP = 4
+# OPTWS buffer (clip_grad_norm / Lamb only), in bytes: the control floats of vt_clip_coef (thresholds in, factor and norm
+# out: N.VT_CTL_*), then the double partials of the gradient's sum of squares, then LAMB's partials and work table
+OPTWS_CTL_BYTES = 64
 
 
 def param_groups(model: nn.Module) -> dict:
@@ -155,12 +160,36 @@ class TrainStep:
         eps: float = 1e-8,
         include_pool: bool = True,
         drop_seed: int = 0,
+        clip_grad_norm: Optional[float] = None,
+        lamb_max_grad_norm: Optional[float] = 1.0,
+        trust_clip: bool = False,
+        always_adapt: bool = False,
     ):
+        """optimizer="Lamb": LAMB in the form of timm.optim.Lamb(bias_correction=True, grad_averaging=True) as
+        include/vt_amd.h states it (timm is no dependency; that statement is the definition).  `lamb_max_grad_norm`,
+        `trust_clip` and `always_adapt` are timm's `max_grad_norm`, `trust_clip` and `always_adapt`; timm's default
+        `eps` is 1e-6, while the `eps` argument here keeps torch.optim.Adam's 1e-8 as its default -- pass eps=1e-6 for
+        timm's recipe.
+        clip_grad_norm=C (any optimiser): the averaged gradient is scaled by min(1, C / (norm + 1e-6)) before the optimiser
+        sees it, as torch.nn.utils.clip_grad_norm_ (Lightning's gradient_clip_val, "norm" algorithm) does.  None builds
+        today's launch lists; float("inf") builds the clipping ops with a factor of exactly 1 / world.  The thresholds
+        live on the device: set_clip_grad_norm changes C under a captured graph, last_grad_norm reads the norm back."""
         N.lib()
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer={optimizer!r}: supported are {', '.join(OPTIMIZERS)}")
         self.optimizer, self._betas, self._eps = optimizer, (float(betas[0]), float(betas[1])), float(eps)
-        self._adam = optimizer != "SGD"
+        self._adam = optimizer != "SGD"  # the Adam family keeps m, v and the device step count: AdamW, Adam, Lamb
+        self._lamb = optimizer == "Lamb"
+        for name, val in (("clip_grad_norm", clip_grad_norm), ("lamb_max_grad_norm", lamb_max_grad_norm)):
+            if val is not None and not float(val) >= 0.0:
+                raise ValueError(f"{name}={val!r}: a threshold is None or >= 0 (0 or inf: built, but off)")
+        self._clip = clip_grad_norm is not None or self._lamb  # the list carries GRAD_SUMSQ / CLIP_COEF
+        self._clip_user = clip_grad_norm is not None
+        self._lamb_flags = (N.VT_LAMB_TRUST_CLIP if trust_clip else 0) | (N.VT_LAMB_ALWAYS_ADAPT if always_adapt else 0)
+        if exchange == "sharded" and self._clip:
+            raise NotImplementedError("exchange='sharded' with optimizer='Lamb' or clip_grad_norm: a rank owns slices of the "
+                                      "flat buffers, not whole tensors or the whole gradient, and the norms are per tensor / "
+                                      "global; use exchange='allreduce'")
         self.include_pool = bool(include_pool)
         if not self.include_pool:
             from .backbones.cait import CaiT
@@ -305,6 +334,10 @@ class TrainStep:
             # [8..13] MixUp / CutMix block (mode, lambda, x1, y1, x2, y2)
             self.lr_dev = torch.zeros(16, dtype=torch.float32, device=self.device)
             self.lr_dev[:4] = lr
+            self._optws = None
+            if self._clip:
+                self._alloc_optws(clip_grad_norm, lamb_max_grad_norm if self._lamb else None, weight_decay, norm_weight_decay,
+                                  bias_weight_decay, groups)
             self.images = torch.zeros(batch_size, 3, image_size, image_size, device=self.device)
             self.labels = torch.zeros(batch_size, dtype=torch.int64, device=self.device)
         self.lr = lr
@@ -415,7 +448,8 @@ class TrainStep:
             self.arena.data_ptr(), PARAMS=st.pflat.data_ptr(), GRADS=self.gflat.data_ptr(),
             STATE=st.sflat.data_ptr(), MIRROR=st.mirror.data_ptr(), COUNTERS=st.nflat.data_ptr(),
             INPUT=self.images.data_ptr(), LABELS=self.labels.data_ptr(), MOMENTUM=self.mflat.data_ptr(),
-            HYPER=self.lr_dev.data_ptr(), **({"MOMENT2": self.vflat.data_ptr()} if self._adam else {}))
+            HYPER=self.lr_dev.data_ptr(), **({"MOMENT2": self.vflat.data_ptr()} if self._adam else {}),
+            **({"OPTWS": self._optws.data_ptr()} if self._clip else {}))
         self.use_graphs = use_graphs
         self._master_stale = False
         self.model.register_state_dict_pre_hook(self._refuse_stale_export)
@@ -423,8 +457,37 @@ class TrainStep:
         self._graphs = None
         self.steps_done = 0
 
+    def _alloc_optws(self, clip, lamb_max, wd, norm_wd, bias_wd, groups):
+        """the device buffer behind clip_grad_norm / Lamb (OPTWS_CTL_BYTES): control floats | sum-of-squares partials of the
+        flat gradient | LAMB's per-item partials | LAMB's work table (one segment per parameter slot of the store, with
+        the weight decay of the parameter's group)"""
+        st = self.store
+        self._sumsq_items = N.opt_items(st.pflat.numel())
+        self._sumsq_off = OPTWS_CTL_BYTES
+        nbytes = self._sumsq_off + 8 * self._sumsq_items
+        table = None
+        if self._lamb:
+            wd_of = {GROUP_OTHER: wd, GROUP_NORM: norm_wd, GROUP_BIAS: bias_wd}
+            self.lamb_wd = [float(wd_of[groups[id(p)]]) for p in st.params]
+            table, self._lamb_items = N.lamb_table(st.offsets, st.slots, self.lamb_wd)
+            self._lamb_part_off = nbytes
+            self._lamb_table_off = E._round_up(nbytes + 16 * self._lamb_items, 16)
+            nbytes = self._lamb_table_off + 4 * len(table)
+        self._optws = torch.zeros(E._round_up(nbytes, 16), dtype=torch.uint8, device=self.device)
+        self._ctl = self._optws[:32].view(torch.float32)
+        self._ctl[N.VT_CTL_CLIP] = 0.0 if clip is None else float(clip)
+        self._ctl[N.VT_CTL_LAMB_MAX] = 0.0 if lamb_max is None else float(lamb_max)
+        if table is not None:
+            self.lamb_table = torch.from_numpy(table)  # (host copy: what the plan tests read)
+            self._optws[self._lamb_table_off: self._lamb_table_off + 4 * len(table)].view(torch.int32).copy_(self.lamb_table)
+
     def _emit_opt(self, ranges):
         """optimiser launch list: one launch of the chosen optimiser per (element range, weight-decay segment) overlap.
+
+        With clip_grad_norm or Lamb the list is [ADAM_TICK] GRAD_SUMSQ CLIP_COEF <optimiser launches>: the sum of squares
+        of the whole flat gradient as per-item partials, then ONE workgroup that adds them and leaves the factor
+        grad_scale * c1 / c2 in the OPTWS buffer, which the *_CLIP / LAMB launches read in the place of the immediate
+        1 / world.  Lamb is two launches over ONE work table of all parameter tensors (moments + norms, then apply).
 
         Adam family: the list opens with ONE VT_OP_ADAM_TICK, which advances the step count in the HYPER buffer and
         leaves the two bias corrections beside it; every VT_OP_ADAMW of the step reads them (and the learning rate)
@@ -433,10 +496,37 @@ class TrainStep:
         ob = E.Builder(self.store, self.dtype, True, True, grad_base=E.GRADS)
         if self._adam:
             ob.emit(N.OP_ADAM_TICK, [(E.HYPER, 0)], [], [self._betas[0], self._betas[1]])
+        mirror = lambda lo: (E.MIRROR, lo * 2) if self.dtype == N.VT_BF16 else None  # noqa: E731
+        coef = (E.OPTWS, 4 * N.VT_CTL_FACTOR)
+        if self._clip:
+            total = self.store.pflat.numel()
+            assert list(ranges) == [(0, total)], "the gradient norm is global: one range over the whole flat buffer"
+            ob.emit(N.OP_GRAD_SUMSQ, [(E.GRADS, 0), (E.OPTWS, self._sumsq_off)], [], [total])
+            ob.emit(N.OP_CLIP_COEF, [(E.OPTWS, self._sumsq_off), (E.OPTWS, 0)], [], [self._sumsq_items, 1.0 / self.world])
+        if self._lamb:
+            part, table = (E.OPTWS, self._lamb_part_off), (E.OPTWS, self._lamb_table_off)
+            n_segs, total = len(self.store.params), self.store.pflat.numel()
+            ob.emit(N.OP_LAMB_MOMENTS,
+                    [(E.PARAMS, 0), (E.GRADS, 0), (E.MOMENTUM, 0), (E.MOMENT2, 0), table, part, coef, (E.HYPER, 0)],
+                    [n_segs, self._lamb_flags], [self._lamb_items, total, self._betas[0], self._betas[1], self._eps])
+            ob.emit(N.OP_LAMB_APPLY,
+                    [(E.PARAMS, 0), (E.MOMENTUM, 0), (E.MOMENT2, 0), mirror(0), table, part, (E.HYPER, 0)],
+                    [N.VT_BF16, n_segs, self._lamb_flags], [self._lamb_items, total, self._eps])
+            ranges = []
         for r0, r1 in ranges:
             for s0, s1, wd in self.segments:
                 lo, hi = max(r0, s0), min(r1, s1)
-                if hi > lo and self._adam:
+                if hi > lo and self._clip and self._adam:
+                    ob.emit(N.OP_ADAMW_CLIP,
+                            [(E.PARAMS, lo * 4), (E.GRADS, lo * 4), (E.MOMENTUM, lo * 4), (E.MOMENT2, lo * 4), mirror(lo),
+                             (E.HYPER, 0), coef],
+                            [N.VT_BF16, int(self.optimizer == "AdamW")],
+                            [hi - lo, self._betas[0], self._betas[1], self._eps, wd])
+                elif hi > lo and self._clip:
+                    ob.emit(N.OP_SGD_CLIP,
+                            [(E.PARAMS, lo * 4), (E.GRADS, lo * 4), (E.MOMENTUM, lo * 4), mirror(lo), (E.HYPER, 0), coef],
+                            [N.VT_BF16], [hi - lo, self._lr0, self._momentum, wd])
+                elif hi > lo and self._adam:
                     ob.emit(N.OP_ADAMW,
                             [(E.PARAMS, lo * 4), (E.GRADS, lo * 4), (E.MOMENTUM, lo * 4), (E.MOMENT2, lo * 4),
                              (E.MIRROR, lo * 2) if self.dtype == N.VT_BF16 else None, (E.HYPER, 0)],
@@ -681,6 +771,22 @@ class TrainStep:
     def set_lr(self, lr: float) -> None:
         self.lr = lr
         self.lr_dev[:4] = lr
+
+    def set_clip_grad_norm(self, value: float) -> None:
+        """change the clip_grad_norm threshold of the NEXT step(s); like set_lr, a captured graph follows (the value
+        lives on the device).  0 or inf switch the clip off without removing its launches."""
+        if not self._clip_user:
+            raise RuntimeError("this TrainStep was built without clip_grad_norm: its optimiser list has no clipping launches")
+        if not float(value) >= 0.0:
+            raise ValueError(f"clip_grad_norm={value!r}: a threshold is >= 0")
+        self._ctl[N.VT_CTL_CLIP] = float(value)
+
+    def last_grad_norm(self) -> float:
+        """the norm N = sqrt(sum g^2) / world of the averaged gradient of the last step, before any clipping, as the device
+        formed it (clip_grad_norm or Lamb only; synchronises)"""
+        if not self._clip:
+            raise RuntimeError("this TrainStep forms no gradient norm (neither clip_grad_norm nor optimizer='Lamb')")
+        return float(self._ctl[N.VT_CTL_NORM].item())
 
     def opt_steps(self) -> int:
         """optimiser steps taken so far as the DEVICE counts them (Adam family: the int32 in slot HYPER_STEP of the
