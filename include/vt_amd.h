@@ -563,6 +563,34 @@ int vt_bn_add_act_bwd_finalize_apply(const float* sums, int32_t C, double count,
                                      int32_t ldz, void* dz, int32_t lddz, void* dr, int32_t lddr, int32_t accumulate, int64_t M,
                                      int32_t dtype, void* stream);
 
+/* The same five passes with a per-image keep factor: stochastic depth of a ResNet block as timm's ResNet places it, behind
+ * the last BatchNorm and in front of the shortcut,  y = relu(keep[b] * bn(conv(h)) + identity).  `keep` is a device
+ * float[M / HW] of any values (0, or 1 / (1 - p) for a kept image); image b = row / HW, M = B * HW < 2^31 rows.
+ *   forward   y = relu(keep[b] * (z*scale + shift) + r); where keep[b] == 0 the rows of z are not read and y = relu(r)
+ *   backward  g = dy * [y > 0] from the stored y.  The identity receives g (written, or accumulated).  The BatchNorm side
+ *             sees u = keep[b] * g: sums[0][c] += sum u, sums[1][c] += sum u*xhat (a dropped image's rows are not read),
+ *             dz = coef0*u - coef1*z + coef2 (a dropped image's z IS read: under batch statistics its dz is
+ *             -coef1*z + coef2; with the coefficients of a frozen BatchNorm it is 0)
+ * With keep[b] == 1 everywhere every output has the bits of the pass without `keep`.  No float atomics. */
+int vt_bn_add_act_keep_apply(const void* z, int32_t ldz, const float* scale, const float* shift, const void* r, int32_t ldr, void* y,
+                             int32_t ldy, const float* keep, int32_t HW, int64_t M, int32_t C, int32_t dtype, void* stream);
+int vt_bn_add_act_keep_finalize_apply(const float* stats, int32_t C, double count, const float* gamma, const float* beta, float eps,
+                                      float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                      float* scale, float* shift, float* mean, float* invstd, const void* z, int32_t ldz,
+                                      const void* r, int32_t ldr, void* y, int32_t ldy, const float* keep, int32_t HW, int64_t M,
+                                      int32_t dtype, void* stream);
+int vt_bn_add_act_keep_bwd_reduce(const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z, int32_t ldz,
+                                  const float* mean, const float* invstd, const float* keep, int32_t HW, int64_t M, int32_t C,
+                                  int32_t dtype, float* sums, void* stream);
+int vt_bn_add_act_keep_bwd_apply(const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z, int32_t ldz,
+                                 const float* coef, void* dz, int32_t lddz, void* dr, int32_t lddr, int32_t accumulate,
+                                 const float* keep, int32_t HW, int64_t M, int32_t C, int32_t dtype, void* stream);
+int vt_bn_add_act_keep_bwd_finalize_apply(const float* sums, int32_t C, double count, double pscale, const float* scale,
+                                          const float* mean, const float* invstd, int32_t train, float* dgamma, float* dbeta,
+                                          float* coef, const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z,
+                                          int32_t ldz, void* dz, int32_t lddz, void* dr, int32_t lddr, int32_t accumulate,
+                                          const float* keep, int32_t HW, int64_t M, int32_t dtype, void* stream);
+
 /* ---- the ResNet stem Conv2d(3, Cout, 7, stride 2, padding 3) as a 4x4 stride-1 convolution (vt_resnet.hip) -----------
  * 49 taps do not fit VT_MAX_TAPS.  Padded to 8x8 with a zero first row and column the filter is a 4x4 stride-1 filter over
  * the space-to-depth image xs[b][hs][ws][(py, px, c)] = x[b][2hs + py][2ws + px][c] (12 channels, padded with zeros to
@@ -1132,6 +1160,26 @@ int vt_softmax_xent_eval(const void* logits, int32_t ldl, const int64_t* labels,
 int vt_mix_nchw_to_nhwc(const float* x, void* y, int32_t B, int32_t C, int32_t H, int32_t W,
                         int32_t Cpad, int32_t dtype, const float* mix, void* stream);
 
+/* Binary cross-entropy of the training step (loss="bce"): the loss of the "ResNet strikes back" and DeiT III recipes, in the
+ * form of timm.loss.BinaryCrossEntropy behind timm's Mixup.  timm is no dependency; THIS statement is the definition.
+ * For B rows, N classes, logits x, labels y and the `mix` block above (NULL or mode 0: lam = 1, no partner is read):
+ *   mixed one-hot  m[b][c] = lam * [c == y_b] + (1 - lam) * [c == y_{(b-1) mod B}]     (equal labels: the two terms add)
+ *   smoothing      t = (1 - s) * m + s / N                                               (s = label_smoothing)
+ *   threshold      with VT_BCE_THRESHOLD:  t = (t > target_threshold) ? 1 : 0
+ *   element loss   l = max(x, 0) - x * t + log1p(exp(-|x|))       (= F.binary_cross_entropy_with_logits(x, t, "none"))
+ *   batch loss     loss[0] += sum_b sum_c l / D,   D = B * N (a mean over elements), or D = B with VT_BCE_SUM_CLASSES
+ *   gradient       dlogits = (sigmoid(x) - t) * grad_scale * (VT_BCE_SUM_CLASSES ? 1 : 1 / N)      (NULL: loss only)
+ * A label outside [0, N) makes the loss NaN; a label is compared with column indices and never forms an address.  Only
+ * columns [0, N) of a row of dlogits are written.  Every finite logit gives finite results.
+ * `rows` is scratch of B doubles (8-byte aligned): the first launch stores each row's sum of l there, one workgroup per
+ * row; a second one-workgroup launch adds rows[0], rows[1], .. in that order in double.  No float atomic: the loss is a
+ * fixed-order sum, the same bits on every run (vt_softmax_xent's is not). */
+#define VT_BCE_SUM_CLASSES 1
+#define VT_BCE_THRESHOLD 2
+int vt_sigmoid_bce(const void* logits, int32_t ldl, const int64_t* labels, float label_smoothing, float grad_scale,
+                   float* loss, void* dlogits, int32_t lddl, int32_t B, int32_t N, int32_t dtype, const float* mix,
+                   int32_t flags, float target_threshold, double* rows, void* stream);
+
 /* ---- optimiser (classifier.py:161-169: torch.optim.SGD, momentum) -------- */
 /* g' = g*grad_scale + wd*p; m = mu*m + g'; p -= lr*m; mirror = cast(p).
  * lr_dev (optional, device float[1]) overrides `lr`, so a captured graph can
@@ -1362,6 +1410,12 @@ enum vt_op_kind {
     VT_OP_ADAMW_CLIP,               /* vt_adamw_clip */
     VT_OP_LAMB_MOMENTS,             /* vt_lamb_moments */
     VT_OP_LAMB_APPLY,               /* vt_lamb_apply */
+    VT_OP_BCE,                      /* vt_sigmoid_bce */
+    VT_OP_BN_ADD_ACT_KEEP_APPLY,         /* vt_bn_add_act_keep_apply */
+    VT_OP_BN_ADD_ACT_KEEP_FIN_APPLY,     /* vt_bn_add_act_keep_finalize_apply */
+    VT_OP_BN_ADD_ACT_KEEP_BWD_REDUCE,    /* vt_bn_add_act_keep_bwd_reduce */
+    VT_OP_BN_ADD_ACT_KEEP_BWD_APPLY,     /* vt_bn_add_act_keep_bwd_apply */
+    VT_OP_BN_ADD_ACT_KEEP_BWD_FIN_APPLY, /* vt_bn_add_act_keep_bwd_finalize_apply */
     VT_OP_KIND_END
 };
 

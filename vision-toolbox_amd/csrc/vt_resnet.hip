@@ -13,6 +13,9 @@
 //    (eval mode, a frozen bn.eval(), SyncBatchNorm).  Streaming kernels on the RowMap of vt_rowmap.h: 16 bytes per lane,
 //    kUnroll rows in flight, plain vector stores; the reduce pass adds its row lanes with rowlane_fold (same header); the
 //    only atomics are the integer ones of the statistics buffer.
+//    Each pass also exists with a per-image keep factor (kKeep; the vt_bn_add_act_keep_* entry points): stochastic depth as
+//    timm's ResNet places it, y = relu(keep[b] * (z*scale + shift) + r); the identity still receives g, the BatchNorm side
+//    keep[b] * g.
 // 2. The stem Conv2d(3, 64, 7, 2, 3): 49 taps against VT_MAX_TAPS = 36.  Padded to 8x8 with a zero first row and column it
 //    is a 4x4 stride-1 filter over the space-to-depth image (12 channels (py, px, c)), taps at offsets -2 .. +1, which the
 //    convolution descriptor expresses and the existing forward and filter-gradient kernels run.  Here: the image gather,
@@ -27,10 +30,14 @@ namespace {
 // y = relu(z*scale + shift + r); kFin: grid (row blocks, channel groups of Cg channels), coefficients finalized in the launch
 // (r and y are not __restrict__: they may be the same tensor -- every element is read and written by one thread)
 // ---------------------------------------------------------------------------------
-template <typename T, bool kFin>
+// kKeep: stochastic depth, y = relu(keep[b] * (z*scale + shift) + r) with one factor per image, b = row / HW (a workgroup's
+// band of rows may cross images); where keep[b] == 0 the row of z is not read and y = relu(r).  The plain passes are the
+// kKeep = false instances, where the operands and the branch compile out.
+template <typename T, bool kFin, bool kKeep = false>
 __global__ void __launch_bounds__(kThreads)
 bn_add_act_kernel(const VtFinFwd f, const float* __restrict__ scale, const float* __restrict__ shift, const T* __restrict__ z,
-                  int ldz, const T* r, int ldr, T* y, int ldy, long M, RowMap rm, int Cg) {
+                  int ldz, const T* r, int ldr, T* y, int ldy, long M, RowMap rm, int Cg,
+                  const float* __restrict__ keep = nullptr, int HW = 1) {
     constexpr int EPC = VecIO<T>::EPC;
     __shared__ float s_sc[kFinCg], s_sf[kFinCg];
     const int t = threadIdx.x;
@@ -57,12 +64,19 @@ bn_add_act_kernel(const VtFinFwd f, const float* __restrict__ scale, const float
         for (int it = 0; it < rm.iters; it += kUnroll) {
             uint4 vz[kUnroll], vr[kUnroll];
             bool ok[kUnroll];
+            float kf[kUnroll];
 #pragma unroll
             for (int u = 0; u < kUnroll; ++u) {
                 ok[u] = (it + u < rm.iters) && (row0 + (long)(it + u) * rm.RT < M);
                 vz[u] = vr[u] = make_uint4(0, 0, 0, 0);
+                kf[u] = 0.f;
                 if (ok[u]) {
-                    vz[u] = ld16(pz + (it + u) * sz);
+                    if constexpr (kKeep) {
+                        kf[u] = keep[(unsigned)(row0 + (long)(it + u) * rm.RT) / (unsigned)HW];  // (M < 2^31 rows: check_keep)
+                        if (kf[u] != 0.f) vz[u] = ld16(pz + (it + u) * sz);
+                    } else {
+                        vz[u] = ld16(pz + (it + u) * sz);
+                    }
                     vr[u] = ld16(pr + (it + u) * sr);
                 }
             }
@@ -72,7 +86,12 @@ bn_add_act_kernel(const VtFinFwd f, const float* __restrict__ scale, const float
                 VecIO<T>::unpack(vz[u], v);
                 VecIO<T>::unpack(vr[u], rr);
 #pragma unroll
-                for (int e = 0; e < EPC; ++e) v[e] = fmaxf(fmaf(v[e], sc[e], sf[e]) + rr[e], 0.f);
+                for (int e = 0; e < EPC; ++e) {
+                    if constexpr (kKeep)  // (keep = 1: fmaf(1, a, r) is a + r, the plain pass's bits)
+                        v[e] = kf[u] != 0.f ? fmaxf(fmaf(kf[u], fmaf(v[e], sc[e], sf[e]), rr[e]), 0.f) : fmaxf(rr[e], 0.f);
+                    else
+                        v[e] = fmaxf(fmaf(v[e], sc[e], sf[e]) + rr[e], 0.f);
+                }
                 if (ok[u]) st16(py + (it + u) * sy, VecIO<T>::pack(v));
             }
         }
@@ -82,11 +101,12 @@ bn_add_act_kernel(const VtFinFwd f, const float* __restrict__ scale, const float
 // ---------------------------------------------------------------------------------
 // backward, pass 1: per-channel sum(g) and sum(g*xhat), g = dy * [y > 0]; the row lanes meet in rowlane_fold (vt_rowmap.h)
 // ---------------------------------------------------------------------------------
-template <typename T>
+// kKeep: the BatchNorm side sees u = keep[b] * g; a dropped image's rows are not read at all
+template <typename T, bool kKeep = false>
 __global__ void __launch_bounds__(kThreads)
 bn_add_act_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ y, int ldy, const T* __restrict__ z, int ldz,
                              const float* __restrict__ mean, const float* __restrict__ invstd, long M, int C, RowMap rm,
-                             float* __restrict__ sums, int Ctot) {
+                             float* __restrict__ sums, int Ctot, const float* __restrict__ keep = nullptr, int HW = 1) {
     constexpr int EPC = VecIO<T>::EPC;
     extern __shared__ __attribute__((aligned(16))) float sred[];  // rowlane_fold_bytes(2, CT, RT, EPC)
     const int t = threadIdx.x;
@@ -114,11 +134,17 @@ bn_add_act_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __rest
             const long sg = (long)rm.RT * lddy, sy = (long)rm.RT * ldy, sz = (long)rm.RT * ldz;
             for (int it = 0; it < rm.iters; it += kUnroll) {
                 uint4 vg[kUnroll], vy[kUnroll], vz[kUnroll];
+                float kf[kUnroll];
 #pragma unroll
                 for (int u = 0; u < kUnroll; ++u) {
                     const long row = row0 + (long)(it + u) * rm.RT;
                     vg[u] = vy[u] = vz[u] = make_uint4(0, 0, 0, 0);  // y = 0 masks the row out
+                    kf[u] = 0.f;
                     if ((it + u < rm.iters) && row < M) {
+                        if constexpr (kKeep) {
+                            kf[u] = keep[(unsigned)row / (unsigned)HW];
+                            if (kf[u] == 0.f) continue;  // (y stays 0: the row contributes nothing)
+                        }
                         vg[u] = ld16(pg + (it + u) * sg);
                         vy[u] = ld16(py + (it + u) * sy);
                         vz[u] = ld16(pz + (it + u) * sz);
@@ -132,7 +158,8 @@ bn_add_act_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __rest
                     VecIO<T>::unpack(vz[u], zz);
 #pragma unroll
                     for (int e = 0; e < EPC; ++e) {
-                        const float gg = yy[e] > 0.f ? g[e] : 0.f;
+                        float gg = yy[e] > 0.f ? g[e] : 0.f;
+                        if constexpr (kKeep) gg *= kf[u];
                         s1[e] += gg;
                         s2[e] = fmaf(gg, zz[e] - mu[e], s2[e]);  // invstd applied once, below
                     }
@@ -152,11 +179,14 @@ bn_add_act_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __rest
 // backward, pass 2: dz = a*g - b*z + d and dr (=|+=) g, g = dy * [y > 0]; kFin: grid (row blocks, channel groups), the
 // backward finalize step inside the launch.  (dr is not __restrict__: with `acc` it is read and written by one thread.)
 // ---------------------------------------------------------------------------------
-template <typename T, bool kFin>
+// kKeep: dz = a*u - b*z + d with u = keep[b] * g, while the identity receives g itself.  A dropped image's z IS read: under
+// batch statistics its dz is -b*z + d (its rows moved the mean and the variance of the others).
+template <typename T, bool kFin, bool kKeep = false>
 __global__ void __launch_bounds__(kThreads)
 bn_add_act_bwd_apply_kernel(const VtFinBwd f, const float* __restrict__ coef, const T* __restrict__ dy, int lddy,
                             const T* __restrict__ y, int ldy, const T* __restrict__ z, int ldz, T* __restrict__ dz, int lddz, T* dr,
-                            int lddr, int acc, long M, int C, RowMap rm, int Cg) {
+                            int lddr, int acc, long M, int C, RowMap rm, int Cg, const float* __restrict__ keep = nullptr,
+                            int HW = 1) {
     constexpr int EPC = VecIO<T>::EPC;
     __shared__ float s_a[kFinCg], s_b[kFinCg], s_d[kFinCg];
     const int t = threadIdx.x;
@@ -200,10 +230,13 @@ bn_add_act_bwd_apply_kernel(const VtFinBwd f, const float* __restrict__ coef, co
                 VecIO<T>::unpack(vy[u], yy);
                 VecIO<T>::unpack(vz[u], zz);
                 VecIO<T>::unpack(va[u], aa);
+                float kf = 1.f;
+                if constexpr (kKeep) kf = keep[(unsigned)row / (unsigned)HW];
 #pragma unroll
                 for (int e = 0; e < EPC; ++e) {
                     const float gg = yy[e] > 0.f ? g[e] : 0.f;
-                    o[e] = fmaf(ca[e], gg, fmaf(-cb[e], zz[e], cd[e]));
+                    if constexpr (kKeep) o[e] = fmaf(ca[e], kf * gg, fmaf(-cb[e], zz[e], cd[e]));
+                    else o[e] = fmaf(ca[e], gg, fmaf(-cb[e], zz[e], cd[e]));
                     aa[e] += gg;  // (acc = 0: aa was zero)
                 }
                 st16(dz + row * lddz + col * EPC, VecIO<T>::pack(o));
@@ -283,61 +316,83 @@ inline RowMap fin_rowmap(int Cg, int groups, int epc, long M) {
     return RowMap::make(Cg, epc, M, wgs / groups > 0 ? wgs / groups : 1);
 }
 
-}  // namespace
+// ---------------------------------------------------------------------------------
+// the five add-then-ReLU passes, plain (keep == nullptr: the kKeep = false instances) or with per-image keep factors
+// ---------------------------------------------------------------------------------
+#define ADD_ACT_MAT(what, p, ld)                            \
+    do {                                                    \
+        char nm__[96];                                      \
+        snprintf(nm__, sizeof nm__, "%s(%s)", who, what);   \
+        VT_TRY(check_mat(nm__, p, ld, C, dtype));           \
+    } while (0)
 
-extern "C" {
-
-int vt_bn_add_act_apply(const void* z, int32_t ldz, const float* scale, const float* shift, const void* r, int32_t ldr, void* y,
-                        int32_t ldy, int64_t M, int32_t C, int32_t dtype, void* stream) {
-    VT_REQUIRE(M > 0 && scale && shift, VT_ERR_INVALID, "vt_bn_add_act_apply: bad argument");
-    VT_TRY(check_mat("vt_bn_add_act_apply(z)", z, ldz, C, dtype));
-    VT_TRY(check_mat("vt_bn_add_act_apply(r)", r, ldr, C, dtype));
-    VT_TRY(check_mat("vt_bn_add_act_apply(y)", y, ldy, C, dtype));
-    const RowMap rm = RowMap::make(C, vt_epc(dtype), M);
-    const VtFinFwd f{};
-    VT_DISPATCH_T(dtype, "vt_bn_add_act_apply",
-                  hipLaunchKernelGGL((bn_add_act_kernel<T, false>), dim3(rm.blocks(M)), dim3(kThreads), 0, (hipStream_t)stream, f,
-                                     scale, shift, (const T*)z, ldz, (const T*)r, ldr, (T*)y, ldy, (long)M, rm, C));
-    VT_CHECK_LAUNCH("vt_bn_add_act_apply");
+int check_keep(const char* who, const float* keep, int HW, long M) {
+    VT_REQUIRE(keep && HW > 0 && M % HW == 0 && M < (1L << 31), VT_ERR_INVALID,
+               "%s: keep is a float[M / HW] row: HW=%d must divide M=%ld, M below 2^31", who, HW, M);
     return VT_OK;
 }
 
-int vt_bn_add_act_finalize_apply(const float* stats, int32_t C, double count, const float* gamma, const float* beta, float eps,
-                                 float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked,
-                                 float* scale, float* shift, float* mean, float* invstd, const void* z, int32_t ldz, const void* r,
-                                 int32_t ldr, void* y, int32_t ldy, int64_t M, int32_t dtype, void* stream) {
-    VT_REQUIRE(stats && scale && shift && mean && invstd && C > 0 && count > 0 && M > 0, VT_ERR_INVALID,
-               "vt_bn_add_act_finalize_apply: bad argument");
+int add_act_apply(const char* who, const void* z, int ldz, const float* scale, const float* shift, const void* r, int ldr, void* y,
+                  int ldy, const float* keep, int HW, long M, int C, int dtype, void* stream) {
+    VT_REQUIRE(M > 0 && scale && shift, VT_ERR_INVALID, "%s: bad argument", who);
+    ADD_ACT_MAT("z", z, ldz);
+    ADD_ACT_MAT("r", r, ldr);
+    ADD_ACT_MAT("y", y, ldy);
+    const RowMap rm = RowMap::make(C, vt_epc(dtype), M);
+    const VtFinFwd f{};
+    if (keep)
+        VT_DISPATCH_T(dtype, who,
+                      hipLaunchKernelGGL((bn_add_act_kernel<T, false, true>), dim3(rm.blocks(M)), dim3(kThreads), 0,
+                                         (hipStream_t)stream, f, scale, shift, (const T*)z, ldz, (const T*)r, ldr, (T*)y, ldy, M, rm,
+                                         C, keep, HW));
+    else
+        VT_DISPATCH_T(dtype, who,
+                      hipLaunchKernelGGL((bn_add_act_kernel<T, false>), dim3(rm.blocks(M)), dim3(kThreads), 0, (hipStream_t)stream, f,
+                                         scale, shift, (const T*)z, ldz, (const T*)r, ldr, (T*)y, ldy, M, rm, C));
+    VT_CHECK_LAUNCH(who);
+    return VT_OK;
+}
+
+int add_act_finalize_apply(const char* who, const float* stats, int C, double count, const float* gamma, const float* beta,
+                           float eps, float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                           float* scale, float* shift, float* mean, float* invstd, const void* z, int ldz, const void* r, int ldr,
+                           void* y, int ldy, const float* keep, int HW, long M, int dtype, void* stream) {
+    VT_REQUIRE(stats && scale && shift && mean && invstd && C > 0 && count > 0 && M > 0, VT_ERR_INVALID, "%s: bad argument", who);
     VT_REQUIRE((running_mean == nullptr) == (running_var == nullptr), VT_ERR_INVALID,
-               "vt_bn_add_act_finalize_apply: running_mean/var must both be given or both NULL");
-    VT_TRY(check_mat("vt_bn_add_act_finalize_apply(z)", z, ldz, C, dtype));
-    VT_TRY(check_mat("vt_bn_add_act_finalize_apply(r)", r, ldr, C, dtype));
-    VT_TRY(check_mat("vt_bn_add_act_finalize_apply(y)", y, ldy, C, dtype));
+               "%s: running_mean/var must both be given or both NULL", who);
+    ADD_ACT_MAT("z", z, ldz);
+    ADD_ACT_MAT("r", r, ldr);
+    ADD_ACT_MAT("y", y, ldy);
     const int Cg = fin_group(C, vt_epc(dtype));
     if (!Cg || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {  // (no channel group: the two launches)
         VT_TRY(vt_bn_finalize(stats, C, count, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, scale,
                               shift, mean, invstd, stream));
-        return vt_bn_add_act_apply(z, ldz, scale, shift, r, ldr, y, ldy, M, C, dtype, stream);
+        return add_act_apply(who, z, ldz, scale, shift, r, ldr, y, ldy, keep, HW, M, C, dtype, stream);
     }
     const int groups = C / Cg;
     const RowMap rm = fin_rowmap(Cg, groups, vt_epc(dtype), M);
     const VtFinFwd f{stats, gamma, beta, running_mean, running_var, num_batches_tracked, scale, shift, mean, invstd,
                      1.0 / count, count > 1.0 ? count / (count - 1.0) : 1.0, eps, momentum, C};
-    VT_DISPATCH_T(dtype, "vt_bn_add_act_finalize_apply",
-                  hipLaunchKernelGGL((bn_add_act_kernel<T, true>), dim3(rm.blocks(M), groups), dim3(kThreads), 0,
-                                     (hipStream_t)stream, f, (const float*)nullptr, (const float*)nullptr, (const T*)z, ldz,
-                                     (const T*)r, ldr, (T*)y, ldy, (long)M, rm, Cg));
-    VT_CHECK_LAUNCH("vt_bn_add_act_finalize_apply");
+    if (keep)
+        VT_DISPATCH_T(dtype, who,
+                      hipLaunchKernelGGL((bn_add_act_kernel<T, true, true>), dim3(rm.blocks(M), groups), dim3(kThreads), 0,
+                                         (hipStream_t)stream, f, (const float*)nullptr, (const float*)nullptr, (const T*)z, ldz,
+                                         (const T*)r, ldr, (T*)y, ldy, M, rm, Cg, keep, HW));
+    else
+        VT_DISPATCH_T(dtype, who,
+                      hipLaunchKernelGGL((bn_add_act_kernel<T, true>), dim3(rm.blocks(M), groups), dim3(kThreads), 0,
+                                         (hipStream_t)stream, f, (const float*)nullptr, (const float*)nullptr, (const T*)z, ldz,
+                                         (const T*)r, ldr, (T*)y, ldy, M, rm, Cg));
+    VT_CHECK_LAUNCH(who);
     return VT_OK;
 }
 
-int vt_bn_add_act_bwd_reduce(const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z, int32_t ldz,
-                             const float* mean, const float* invstd, int64_t M, int32_t C, int32_t dtype, float* sums,
-                             void* stream) {
-    VT_REQUIRE(M > 0 && mean && invstd && sums, VT_ERR_INVALID, "vt_bn_add_act_bwd_reduce: bad argument");
-    VT_TRY(check_mat("vt_bn_add_act_bwd_reduce(dy)", dy, lddy, C, dtype));
-    VT_TRY(check_mat("vt_bn_add_act_bwd_reduce(y)", y, ldy, C, dtype));
-    VT_TRY(check_mat("vt_bn_add_act_bwd_reduce(z)", z, ldz, C, dtype));
+int add_act_bwd_reduce(const char* who, const void* dy, int lddy, const void* y, int ldy, const void* z, int ldz, const float* mean,
+                       const float* invstd, const float* keep, int HW, long M, int C, int dtype, float* sums, void* stream) {
+    VT_REQUIRE(M > 0 && mean && invstd && sums, VT_ERR_INVALID, "%s: bad argument", who);
+    ADD_ACT_MAT("dy", dy, lddy);
+    ADD_ACT_MAT("y", y, ldy);
+    ADD_ACT_MAT("z", z, ldz);
     const int epc = vt_epc(dtype);
     // the grid of vt_bn_act_bwd_reduce: few, long blocks (each ends with 2*C 64-bit atomics), channel groups of 64 on the
     // small maps with many channels
@@ -345,33 +400,111 @@ int vt_bn_add_act_bwd_reduce(const void* dy, int32_t lddy, const void* y, int32_
     const int Cg = C / cgroups;
     const int blocks_knob = VT_KNOB("VT_BN_RED_BLOCKS", 1024);
     const RowMap rm = RowMap::make(Cg, epc, M, blocks_knob / cgroups > 0 ? blocks_knob / cgroups : 1);
-    VT_DISPATCH_T(dtype, "vt_bn_add_act_bwd_reduce",
-                  hipLaunchKernelGGL(bn_add_act_bwd_reduce_kernel<T>, dim3(rm.blocks(M), cgroups), dim3(kThreads),
-                                     rowlane_fold_bytes(2, rm.CT, rm.RT, epc),
-                                     (hipStream_t)stream, (const T*)dy, lddy, (const T*)y, ldy, (const T*)z, ldz, mean, invstd,
-                                     (long)M, Cg, rm, sums, C));
-    VT_CHECK_LAUNCH("vt_bn_add_act_bwd_reduce");
+    if (keep)
+        VT_DISPATCH_T(dtype, who,
+                      hipLaunchKernelGGL((bn_add_act_bwd_reduce_kernel<T, true>), dim3(rm.blocks(M), cgroups), dim3(kThreads),
+                                         rowlane_fold_bytes(2, rm.CT, rm.RT, epc), (hipStream_t)stream, (const T*)dy, lddy,
+                                         (const T*)y, ldy, (const T*)z, ldz, mean, invstd, M, Cg, rm, sums, C, keep, HW));
+    else
+        VT_DISPATCH_T(dtype, who,
+                      hipLaunchKernelGGL(bn_add_act_bwd_reduce_kernel<T>, dim3(rm.blocks(M), cgroups), dim3(kThreads),
+                                         rowlane_fold_bytes(2, rm.CT, rm.RT, epc),
+                                         (hipStream_t)stream, (const T*)dy, lddy, (const T*)y, ldy, (const T*)z, ldz, mean, invstd,
+                                         M, Cg, rm, sums, C));
+    VT_CHECK_LAUNCH(who);
     return VT_OK;
+}
+
+int add_act_bwd_apply(const char* who, const void* dy, int lddy, const void* y, int ldy, const void* z, int ldz, const float* coef,
+                      void* dz, int lddz, void* dr, int lddr, int accumulate, const float* keep, int HW, long M, int C, int dtype,
+                      void* stream) {
+    VT_REQUIRE(M > 0 && coef, VT_ERR_INVALID, "%s: bad argument", who);
+    ADD_ACT_MAT("dy", dy, lddy);
+    ADD_ACT_MAT("y", y, ldy);
+    ADD_ACT_MAT("z", z, ldz);
+    ADD_ACT_MAT("dz", dz, lddz);
+    ADD_ACT_MAT("dr", dr, lddr);
+    VT_REQUIRE(dz != dr, VT_ERR_INVALID, "%s: dz and dr are two outputs", who);
+    const RowMap rm = RowMap::make(C, vt_epc(dtype), M);
+    const VtFinBwd f{};
+    if (keep)
+        VT_DISPATCH_T(dtype, who,
+                      hipLaunchKernelGGL((bn_add_act_bwd_apply_kernel<T, false, true>), dim3(rm.blocks(M)), dim3(kThreads), 0,
+                                         (hipStream_t)stream, f, coef, (const T*)dy, lddy, (const T*)y, ldy, (const T*)z, ldz, (T*)dz,
+                                         lddz, (T*)dr, lddr, accumulate ? 1 : 0, M, C, rm, C, keep, HW));
+    else
+        VT_DISPATCH_T(dtype, who,
+                      hipLaunchKernelGGL((bn_add_act_bwd_apply_kernel<T, false>), dim3(rm.blocks(M)), dim3(kThreads), 0,
+                                         (hipStream_t)stream, f, coef, (const T*)dy, lddy, (const T*)y, ldy, (const T*)z, ldz, (T*)dz,
+                                         lddz, (T*)dr, lddr, accumulate ? 1 : 0, M, C, rm, C));
+    VT_CHECK_LAUNCH(who);
+    return VT_OK;
+}
+
+int add_act_bwd_finalize_apply(const char* who, const float* sums, int C, double count, double pscale, const float* scale,
+                               const float* mean, const float* invstd, int train, float* dgamma, float* dbeta, float* coef,
+                               const void* dy, int lddy, const void* y, int ldy, const void* z, int ldz, void* dz, int lddz, void* dr,
+                               int lddr, int accumulate, const float* keep, int HW, long M, int dtype, void* stream) {
+    VT_REQUIRE(sums && scale && mean && invstd && coef && C > 0 && count > 0 && M > 0, VT_ERR_INVALID, "%s: bad argument", who);
+    ADD_ACT_MAT("dy", dy, lddy);
+    ADD_ACT_MAT("y", y, ldy);
+    ADD_ACT_MAT("z", z, ldz);
+    ADD_ACT_MAT("dz", dz, lddz);
+    ADD_ACT_MAT("dr", dr, lddr);
+    VT_REQUIRE(dz != dr, VT_ERR_INVALID, "%s: dz and dr are two outputs", who);
+    const int Cg = fin_group(C, vt_epc(dtype));
+    if (!Cg || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {  // (no channel group: the two launches)
+        VT_TRY(vt_bn_bwd_finalize(sums, C, count, pscale, scale, mean, invstd, train, dgamma, dbeta, coef, stream));
+        return add_act_bwd_apply(who, dy, lddy, y, ldy, z, ldz, coef, dz, lddz, dr, lddr, accumulate, keep, HW, M, C, dtype, stream);
+    }
+    const int groups = C / Cg;
+    const RowMap rm = fin_rowmap(Cg, groups, vt_epc(dtype), M);
+    const VtFinBwd f{sums, scale, mean, invstd, dgamma, dbeta, coef, 1.0 / count, pscale, C, train};
+    if (keep)
+        VT_DISPATCH_T(dtype, who,
+                      hipLaunchKernelGGL((bn_add_act_bwd_apply_kernel<T, true, true>), dim3(rm.blocks(M), groups), dim3(kThreads), 0,
+                                         (hipStream_t)stream, f, (const float*)nullptr, (const T*)dy, lddy, (const T*)y, ldy,
+                                         (const T*)z, ldz, (T*)dz, lddz, (T*)dr, lddr, accumulate ? 1 : 0, M, C, rm, Cg, keep, HW));
+    else
+        VT_DISPATCH_T(dtype, who,
+                      hipLaunchKernelGGL((bn_add_act_bwd_apply_kernel<T, true>), dim3(rm.blocks(M), groups), dim3(kThreads), 0,
+                                         (hipStream_t)stream, f, (const float*)nullptr, (const T*)dy, lddy, (const T*)y, ldy,
+                                         (const T*)z, ldz, (T*)dz, lddz, (T*)dr, lddr, accumulate ? 1 : 0, M, C, rm, Cg));
+    VT_CHECK_LAUNCH(who);
+    return VT_OK;
+}
+#undef ADD_ACT_MAT
+
+}  // namespace
+
+extern "C" {
+
+int vt_bn_add_act_apply(const void* z, int32_t ldz, const float* scale, const float* shift, const void* r, int32_t ldr, void* y,
+                        int32_t ldy, int64_t M, int32_t C, int32_t dtype, void* stream) {
+    return add_act_apply("vt_bn_add_act_apply", z, ldz, scale, shift, r, ldr, y, ldy, nullptr, 1, (long)M, C, dtype, stream);
+}
+
+int vt_bn_add_act_finalize_apply(const float* stats, int32_t C, double count, const float* gamma, const float* beta, float eps,
+                                 float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                 float* scale, float* shift, float* mean, float* invstd, const void* z, int32_t ldz, const void* r,
+                                 int32_t ldr, void* y, int32_t ldy, int64_t M, int32_t dtype, void* stream) {
+    return add_act_finalize_apply("vt_bn_add_act_finalize_apply", stats, C, count, gamma, beta, eps, momentum, running_mean,
+                                  running_var, num_batches_tracked, scale, shift, mean, invstd, z, ldz, r, ldr, y, ldy, nullptr, 1,
+                                  (long)M, dtype, stream);
+}
+
+int vt_bn_add_act_bwd_reduce(const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z, int32_t ldz,
+                             const float* mean, const float* invstd, int64_t M, int32_t C, int32_t dtype, float* sums,
+                             void* stream) {
+    return add_act_bwd_reduce("vt_bn_add_act_bwd_reduce", dy, lddy, y, ldy, z, ldz, mean, invstd, nullptr, 1, (long)M, C, dtype, sums,
+                              stream);
 }
 
 int vt_bn_add_act_bwd_apply(const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z, int32_t ldz,
                             const float* coef, void* dz, int32_t lddz, void* dr, int32_t lddr, int32_t accumulate, int64_t M,
                             int32_t C, int32_t dtype, void* stream) {
-    VT_REQUIRE(M > 0 && coef, VT_ERR_INVALID, "vt_bn_add_act_bwd_apply: bad argument");
-    VT_TRY(check_mat("vt_bn_add_act_bwd_apply(dy)", dy, lddy, C, dtype));
-    VT_TRY(check_mat("vt_bn_add_act_bwd_apply(y)", y, ldy, C, dtype));
-    VT_TRY(check_mat("vt_bn_add_act_bwd_apply(z)", z, ldz, C, dtype));
-    VT_TRY(check_mat("vt_bn_add_act_bwd_apply(dz)", dz, lddz, C, dtype));
-    VT_TRY(check_mat("vt_bn_add_act_bwd_apply(dr)", dr, lddr, C, dtype));
-    VT_REQUIRE(dz != dr, VT_ERR_INVALID, "vt_bn_add_act_bwd_apply: dz and dr are two outputs");
-    const RowMap rm = RowMap::make(C, vt_epc(dtype), M);
-    const VtFinBwd f{};
-    VT_DISPATCH_T(dtype, "vt_bn_add_act_bwd_apply",
-                  hipLaunchKernelGGL((bn_add_act_bwd_apply_kernel<T, false>), dim3(rm.blocks(M)), dim3(kThreads), 0,
-                                     (hipStream_t)stream, f, coef, (const T*)dy, lddy, (const T*)y, ldy, (const T*)z, ldz, (T*)dz,
-                                     lddz, (T*)dr, lddr, accumulate ? 1 : 0, (long)M, C, rm, C));
-    VT_CHECK_LAUNCH("vt_bn_add_act_bwd_apply");
-    return VT_OK;
+    return add_act_bwd_apply("vt_bn_add_act_bwd_apply", dy, lddy, y, ldy, z, ldz, coef, dz, lddz, dr, lddr, accumulate, nullptr, 1,
+                             (long)M, C, dtype, stream);
 }
 
 int vt_bn_add_act_bwd_finalize_apply(const float* sums, int32_t C, double count, double pscale, const float* scale,
@@ -379,28 +512,54 @@ int vt_bn_add_act_bwd_finalize_apply(const float* sums, int32_t C, double count,
                                      float* coef, const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z,
                                      int32_t ldz, void* dz, int32_t lddz, void* dr, int32_t lddr, int32_t accumulate, int64_t M,
                                      int32_t dtype, void* stream) {
-    VT_REQUIRE(sums && scale && mean && invstd && coef && C > 0 && count > 0 && M > 0, VT_ERR_INVALID,
-               "vt_bn_add_act_bwd_finalize_apply: bad argument");
-    VT_TRY(check_mat("vt_bn_add_act_bwd_finalize_apply(dy)", dy, lddy, C, dtype));
-    VT_TRY(check_mat("vt_bn_add_act_bwd_finalize_apply(y)", y, ldy, C, dtype));
-    VT_TRY(check_mat("vt_bn_add_act_bwd_finalize_apply(z)", z, ldz, C, dtype));
-    VT_TRY(check_mat("vt_bn_add_act_bwd_finalize_apply(dz)", dz, lddz, C, dtype));
-    VT_TRY(check_mat("vt_bn_add_act_bwd_finalize_apply(dr)", dr, lddr, C, dtype));
-    VT_REQUIRE(dz != dr, VT_ERR_INVALID, "vt_bn_add_act_bwd_finalize_apply: dz and dr are two outputs");
-    const int Cg = fin_group(C, vt_epc(dtype));
-    if (!Cg || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {  // (no channel group: the two launches)
-        VT_TRY(vt_bn_bwd_finalize(sums, C, count, pscale, scale, mean, invstd, train, dgamma, dbeta, coef, stream));
-        return vt_bn_add_act_bwd_apply(dy, lddy, y, ldy, z, ldz, coef, dz, lddz, dr, lddr, accumulate, M, C, dtype, stream);
-    }
-    const int groups = C / Cg;
-    const RowMap rm = fin_rowmap(Cg, groups, vt_epc(dtype), M);
-    const VtFinBwd f{sums, scale, mean, invstd, dgamma, dbeta, coef, 1.0 / count, pscale, C, train};
-    VT_DISPATCH_T(dtype, "vt_bn_add_act_bwd_finalize_apply",
-                  hipLaunchKernelGGL((bn_add_act_bwd_apply_kernel<T, true>), dim3(rm.blocks(M), groups), dim3(kThreads), 0,
-                                     (hipStream_t)stream, f, (const float*)nullptr, (const T*)dy, lddy, (const T*)y, ldy,
-                                     (const T*)z, ldz, (T*)dz, lddz, (T*)dr, lddr, accumulate ? 1 : 0, (long)M, C, rm, Cg));
-    VT_CHECK_LAUNCH("vt_bn_add_act_bwd_finalize_apply");
-    return VT_OK;
+    return add_act_bwd_finalize_apply("vt_bn_add_act_bwd_finalize_apply", sums, C, count, pscale, scale, mean, invstd, train, dgamma,
+                                      dbeta, coef, dy, lddy, y, ldy, z, ldz, dz, lddz, dr, lddr, accumulate, nullptr, 1, (long)M,
+                                      dtype, stream);
+}
+
+// ---- the same passes with per-image keep factors (stochastic depth of a ResNet block) ----
+int vt_bn_add_act_keep_apply(const void* z, int32_t ldz, const float* scale, const float* shift, const void* r, int32_t ldr, void* y,
+                             int32_t ldy, const float* keep, int32_t HW, int64_t M, int32_t C, int32_t dtype, void* stream) {
+    VT_TRY(check_keep("vt_bn_add_act_keep_apply", keep, HW, (long)M));
+    return add_act_apply("vt_bn_add_act_keep_apply", z, ldz, scale, shift, r, ldr, y, ldy, keep, HW, (long)M, C, dtype, stream);
+}
+
+int vt_bn_add_act_keep_finalize_apply(const float* stats, int32_t C, double count, const float* gamma, const float* beta, float eps,
+                                      float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                                      float* scale, float* shift, float* mean, float* invstd, const void* z, int32_t ldz,
+                                      const void* r, int32_t ldr, void* y, int32_t ldy, const float* keep, int32_t HW, int64_t M,
+                                      int32_t dtype, void* stream) {
+    VT_TRY(check_keep("vt_bn_add_act_keep_finalize_apply", keep, HW, (long)M));
+    return add_act_finalize_apply("vt_bn_add_act_keep_finalize_apply", stats, C, count, gamma, beta, eps, momentum, running_mean,
+                                  running_var, num_batches_tracked, scale, shift, mean, invstd, z, ldz, r, ldr, y, ldy, keep, HW,
+                                  (long)M, dtype, stream);
+}
+
+int vt_bn_add_act_keep_bwd_reduce(const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z, int32_t ldz,
+                                  const float* mean, const float* invstd, const float* keep, int32_t HW, int64_t M, int32_t C,
+                                  int32_t dtype, float* sums, void* stream) {
+    VT_TRY(check_keep("vt_bn_add_act_keep_bwd_reduce", keep, HW, (long)M));
+    return add_act_bwd_reduce("vt_bn_add_act_keep_bwd_reduce", dy, lddy, y, ldy, z, ldz, mean, invstd, keep, HW, (long)M, C, dtype,
+                              sums, stream);
+}
+
+int vt_bn_add_act_keep_bwd_apply(const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z, int32_t ldz,
+                                 const float* coef, void* dz, int32_t lddz, void* dr, int32_t lddr, int32_t accumulate,
+                                 const float* keep, int32_t HW, int64_t M, int32_t C, int32_t dtype, void* stream) {
+    VT_TRY(check_keep("vt_bn_add_act_keep_bwd_apply", keep, HW, (long)M));
+    return add_act_bwd_apply("vt_bn_add_act_keep_bwd_apply", dy, lddy, y, ldy, z, ldz, coef, dz, lddz, dr, lddr, accumulate, keep, HW,
+                             (long)M, C, dtype, stream);
+}
+
+int vt_bn_add_act_keep_bwd_finalize_apply(const float* sums, int32_t C, double count, double pscale, const float* scale,
+                                          const float* mean, const float* invstd, int32_t train, float* dgamma, float* dbeta,
+                                          float* coef, const void* dy, int32_t lddy, const void* y, int32_t ldy, const void* z,
+                                          int32_t ldz, void* dz, int32_t lddz, void* dr, int32_t lddr, int32_t accumulate,
+                                          const float* keep, int32_t HW, int64_t M, int32_t dtype, void* stream) {
+    VT_TRY(check_keep("vt_bn_add_act_keep_bwd_finalize_apply", keep, HW, (long)M));
+    return add_act_bwd_finalize_apply("vt_bn_add_act_keep_bwd_finalize_apply", sums, C, count, pscale, scale, mean, invstd, train,
+                                      dgamma, dbeta, coef, dy, lddy, y, ldy, z, ldz, dz, lddz, dr, lddr, accumulate, keep, HW,
+                                      (long)M, dtype, stream);
 }
 
 int32_t vt_stem7_s2d_channels(int32_t dtype) { return dtype == VT_BF16 ? 16 : 12; }

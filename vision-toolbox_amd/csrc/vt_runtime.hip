@@ -364,6 +364,26 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
                                                     (const float*)P[2], (const float*)P[3], I[1], (float*)P[4], (float*)P[5],
                                                     (float*)P[6], P[7], I[2], P[8], I[3], P[9], I[4], P[10], I[5], P[11], I[6], I[7],
                                                     (int64_t)F[2], I[8], st);
+        // the add-then-ReLU passes with keep factors: the operands of the five cases above, then `keep` and HW
+        case VT_OP_BN_ADD_ACT_KEEP_APPLY:  // ptr: z scale shift r y keep | i: ldz ldr ldy C dtype HW | f: M
+            return vt_bn_add_act_keep_apply(P[0], I[0], (const float*)P[1], (const float*)P[2], P[3], I[1], P[4], I[2],
+                                            (const float*)P[5], I[5], (int64_t)F[0], I[3], I[4], st);
+        case VT_OP_BN_ADD_ACT_KEEP_FIN_APPLY:  // ptr: stats gamma beta rm rv nbt scale shift mean invstd z r y keep | i: C ldz ldr ldy dtype HW | f: count eps momentum M
+            return vt_bn_add_act_keep_finalize_apply((const float*)P[0], I[0], F[0], (const float*)P[1], (const float*)P[2],
+                                                     (float)F[1], (float)F[2], (float*)P[3], (float*)P[4], (int64_t*)P[5],
+                                                     (float*)P[6], (float*)P[7], (float*)P[8], (float*)P[9], P[10], I[1], P[11], I[2],
+                                                     P[12], I[3], (const float*)P[13], I[5], (int64_t)F[3], I[4], st);
+        case VT_OP_BN_ADD_ACT_KEEP_BWD_REDUCE:  // ptr: dy y z mean invstd sums keep | i: lddy ldy ldz C dtype HW | f: M
+            return vt_bn_add_act_keep_bwd_reduce(P[0], I[0], P[1], I[1], P[2], I[2], (const float*)P[3], (const float*)P[4],
+                                                 (const float*)P[6], I[5], (int64_t)F[0], I[3], I[4], (float*)P[5], st);
+        case VT_OP_BN_ADD_ACT_KEEP_BWD_APPLY:  // ptr: dy y z coef dz dr keep | i: lddy ldy ldz lddz lddr accumulate C dtype HW | f: M
+            return vt_bn_add_act_keep_bwd_apply(P[0], I[0], P[1], I[1], P[2], I[2], (const float*)P[3], P[4], I[3], P[5], I[4], I[5],
+                                                (const float*)P[6], I[8], (int64_t)F[0], I[6], I[7], st);
+        case VT_OP_BN_ADD_ACT_KEEP_BWD_FIN_APPLY:  // ptr: sums scale mean invstd dgamma dbeta coef dy y z dz dr keep | i: C train lddy ldy ldz lddz lddr accumulate dtype HW | f: count pscale(0 = 1) M
+            return vt_bn_add_act_keep_bwd_finalize_apply((const float*)P[0], I[0], F[0], F[1] == 0.0 ? 1.0 : F[1], (const float*)P[1],
+                                                         (const float*)P[2], (const float*)P[3], I[1], (float*)P[4], (float*)P[5],
+                                                         (float*)P[6], P[7], I[2], P[8], I[3], P[9], I[4], P[10], I[5], P[11], I[6],
+                                                         I[7], (const float*)P[12], I[9], (int64_t)F[2], I[8], st);
         case VT_OP_STEM7_S2D:  // ptr: x out | i: ldx ldo B H W dtype
             return vt_stem7_s2d(P[0], I[0], P[1], I[1], I[2], I[3], I[4], I[5], st);
         case VT_OP_STEM7_PACK_FILTER:  // ptr: w out | i: src_dtype dst_dtype Cout
@@ -501,6 +521,9 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
         case VT_OP_LAMB_APPLY:  // ptr: p m v mirror table partials hyper | i: mirror_dtype n_segs flags | f: n_items n_total eps
             return vt_lamb_apply((float*)P[0], (const float*)P[1], (const float*)P[2], P[3], I[0], (const int32_t*)P[4], I[1],
                                  (int64_t)F[0], (int64_t)F[1], (const double*)P[5], (float)F[2], I[2], (const float*)P[6], st);
+        case VT_OP_BCE:  // ptr: logits labels loss dlogits [mix] rows | i: ldl lddl B N dtype flags | f: eps grad_scale threshold
+            return vt_sigmoid_bce(P[0], I[0], (const int64_t*)P[1], (float)F[0], (float)F[1], (float*)P[2], P[3], I[1], I[2],
+                                  I[3], I[4], (const float*)P[4], I[5], (float)F[2], (double*)P[5], st);
         case VT_OP_COPY2D:  // ptr: src dst | i: src_dtype dst_dtype cols accumulate | f: lds ldd rows
             return vt_copy2d(P[0], I[0], (int64_t)F[0], P[1], I[1], (int64_t)F[1], (int64_t)F[2], I[2], I[3], st);
         case VT_OP_NCHW_TO_NHWC:  // ptr: x y [mix] | i: B C H W Cpad dtype

@@ -23,6 +23,7 @@ VT_STAT_REPLICAS = 16
 VT_OPT_ITEM = 4096
 VT_CTL_CLIP, VT_CTL_LAMB_MAX, VT_CTL_FACTOR, VT_CTL_NORM = 0, 1, 2, 3
 VT_LAMB_TRUST_CLIP, VT_LAMB_ALWAYS_ADAPT = 1, 2
+VT_BCE_SUM_CLASSES, VT_BCE_THRESHOLD = 1, 2  # flags of vt_sigmoid_bce
 # a statistics buffer is int64[VT_STAT_REPLICAS][2][C][2]: value = hi * 2^12 + lo / 2^33 (vt_amd.h)
 STAT_MARKER = 1 << 40  # what a non-finite or |v| >= 2^50 contribution adds to the hi limb instead of its value
 
@@ -207,7 +208,13 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_ADAMW_CLIP,
     OP_LAMB_MOMENTS,
     OP_LAMB_APPLY,
-) = range(1, 122)
+    OP_BCE,
+    OP_BN_ADD_ACT_KEEP_APPLY,
+    OP_BN_ADD_ACT_KEEP_FIN_APPLY,
+    OP_BN_ADD_ACT_KEEP_BWD_REDUCE,
+    OP_BN_ADD_ACT_KEEP_BWD_APPLY,
+    OP_BN_ADD_ACT_KEEP_BWD_FIN_APPLY,
+) = range(1, 128)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -313,6 +320,12 @@ OP_NAMES = {
     OP_ADAMW_CLIP: "adamw_clip",
     OP_LAMB_MOMENTS: "lamb_moments",
     OP_LAMB_APPLY: "lamb_apply",
+    OP_BCE: "bce",
+    OP_BN_ADD_ACT_KEEP_APPLY: "bn_add_act_keep_apply",
+    OP_BN_ADD_ACT_KEEP_FIN_APPLY: "bn_add_act_keep_fin_apply",
+    OP_BN_ADD_ACT_KEEP_BWD_REDUCE: "bn_add_act_keep_bwd_reduce",
+    OP_BN_ADD_ACT_KEEP_BWD_APPLY: "bn_add_act_keep_bwd_apply",
+    OP_BN_ADD_ACT_KEEP_BWD_FIN_APPLY: "bn_add_act_keep_bwd_fin_apply",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -481,6 +494,14 @@ SYMBOLS = {
     "vt_bn_add_act_apply": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i32, _i32, _vp]),
     "vt_bn_add_act_finalize_apply": (_i32, [_vp, _i32, _f64, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp,
                                             _i32, _vp, _i32, _i64, _i32, _vp]),
+    "vt_bn_add_act_keep_apply": (_i32, [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i64, _i32, _i32, _vp]),
+    "vt_bn_add_act_keep_finalize_apply": (_i32, [_vp, _i32, _f64, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
+                                                 _vp, _i32, _vp, _i32, _vp, _i32, _i64, _i32, _vp]),
+    "vt_bn_add_act_keep_bwd_reduce": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp]),
+    "vt_bn_add_act_keep_bwd_apply": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _i32,
+                                            _i32, _vp]),
+    "vt_bn_add_act_keep_bwd_finalize_apply": (_i32, [_vp, _i32, _f64, _f64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32,
+                                                     _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _i32, _vp]),
     "vt_bn_add_act_bwd_reduce": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "vt_bn_add_act_bwd_apply": (_i32, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i64, _i32, _i32, _vp]),
     "vt_bn_add_act_bwd_finalize_apply": (_i32, [_vp, _i32, _f64, _f64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp,
@@ -589,6 +610,7 @@ SYMBOLS = {
     "vt_softmax_xent": (_i32, [_vp, _i32, _vp, _f32, _f32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "vt_softmax_xent_mix": (_i32, [_vp, _i32, _vp, _f32, _f32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "vt_softmax_xent_eval": (_i32, [_vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vt_sigmoid_bce": (_i32, [_vp, _i32, _vp, _f32, _f32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _f32, _vp, _vp]),
     "vt_mix_nchw_to_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "vt_sgd_momentum": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _f32, _f32, _f32, _f32, _vp, _vp]),
     "vt_adam_tick": (_i32, [_vp, _f64, _f64, _vp]),

@@ -16,6 +16,14 @@ list (`_vt_emit_maps`):
 * a block ends in `relu(bn(conv(h)) + identity)`: the residual joins BEFORE the activation, which is the
   `residual_pre_act` mode of Builder.conv_unit on the add-then-ReLU BatchNorm passes of vt_resnet.hip.
 
+Stochastic depth (`stochastic_depth=` of the extractor, the "ResNet strikes back" recipes) is timm's ResNet's: block i of n
+in network order drops its branch with p_i = stochastic_depth * i / (n - 1), behind the last BatchNorm and in front of the
+shortcut -- y = relu(keep[b] * bn(conv(h)) + identity) in training mode, keep[b] = bernoulli(1 - p_i) / (1 - p_i) per image,
+downsample blocks included.  The factor rides on the unit that closes the block (Builder.conv_unit(..., residual_pre_act=True,
+keep=row): the keep forms of the passes of vt_resnet.hip); the factors of a forward are one float[n_sites][B] table
+(Builder.keep_table) drawn outside the launch list, or the values of `set_keep_factors` -- on the eager path too.  Eval mode,
+stochastic_depth = 0 and blocks with p_i = 0 emit what they always emitted.  No parameter or buffer is added.
+
 The ResNeXt names run on CPU tensors only: their grouped 3x3 convolutions have 4 or 8 channels per group, below or at
 one 16-byte chunk, and a 32- or 64-way split of every block into per-group launches is no hot path.  GPU tensors refuse
 them by name.
@@ -44,11 +52,16 @@ class _Block(HipModule):
     """conv-bn-relu units, then relu(bn(conv(h)) + identity); `_units()` lists (conv, bn) in order"""
 
     expansion = 1
+    drop_prob = 0.0  # stochastic depth of this block (a plain attribute: no state_dict entry), set by ResNetExtractor
 
     def _units(self):  # pragma: no cover - abstract
         raise NotImplementedError
 
-    def _vt_emit(self, b, x, out=None, name: str = "block"):
+    def drops(self) -> bool:
+        """does this block multiply its branch by a per-image keep factor in the current mode?"""
+        return self.training and self.drop_prob > 0.0
+
+    def _vt_emit(self, b, x, out=None, name: str = "block", keep=None):
         identity = x
         if self.downsample is not None:
             identity = b.conv_unit(x, self.downsample[0], self.downsample[1], 0, name=name + ".downsample")
@@ -57,19 +70,24 @@ class _Block(HipModule):
         for k, (conv, bn) in enumerate(units[:-1], start=1):
             h = b.conv_unit(h, conv, bn, 1, name=f"{name}.conv{k}")
         conv, bn = units[-1]
-        return b.conv_unit(h, conv, bn, 1, residual=identity, out=out, name=f"{name}.conv{len(units)}", residual_pre_act=True)
+        return b.conv_unit(h, conv, bn, 1, residual=identity, out=out, name=f"{name}.conv{len(units)}", residual_pre_act=True,
+                           keep=keep)
 
     def _vt_emit_maps(self, b, x):
         return [self._vt_emit(b, x)]
 
-    def _eager_maps(self, x: Tensor) -> "list[Tensor]":
+    def _eager_maps(self, x: Tensor, keep: Optional[Tensor] = None) -> "list[Tensor]":
+        """`keep`: float[B] factors of the branch (None: no stochastic depth)"""
         identity = x if self.downsample is None else self.downsample(x)
         units = self._units()
         h = x
         for conv, bn in units[:-1]:
             h = self.relu(bn(conv(h)))
         conv, bn = units[-1]
-        return [self.relu(bn(conv(h)) + identity)]
+        h = bn(conv(h))
+        if keep is not None:
+            h = h * keep.to(h.dtype).view(-1, 1, 1, 1)
+        return [self.relu(h + identity)]
 
 
 class BasicBlock(_Block):
@@ -154,7 +172,7 @@ _VARIANTS = {
 class ResNetExtractor(BaseBackbone):
     """`ResNetExtractor(name)`: five feature maps -- the output of `relu` at stride 2, then `layer1 .. layer4`."""
 
-    def __init__(self, name: str, pretrained: bool = False) -> None:
+    def __init__(self, name: str, pretrained: bool = False, stochastic_depth: float = 0.0) -> None:
         if name not in _VARIANTS:
             raise ValueError(f"ResNetExtractor: unknown model {name!r} (one of {', '.join(_VARIANTS)})")
         if pretrained:
@@ -167,6 +185,47 @@ class ResNetExtractor(BaseBackbone):
         e = block.expansion
         self.out_channels_list = (64, 64 * e, 128 * e, 256 * e, 512 * e)
         self.stride = 32
+        stochastic_depth = float(stochastic_depth)
+        if not 0.0 <= stochastic_depth < 1.0:
+            raise ValueError(f"stochastic_depth must lie in [0, 1), got {stochastic_depth}")
+        self.stochastic_depth = stochastic_depth
+        blocks = self.blocks()
+        for i, blk in enumerate(blocks):
+            blk.drop_prob = stochastic_depth * i / (len(blocks) - 1)
+        self._keep_override: Optional[Tensor] = None
+
+    # -- stochastic depth ----------------------------------------------------------------
+    def blocks(self) -> "list[_Block]":
+        return [blk for layer in self.feat_extractor.layers() for blk in layer]
+
+    def drop_rates(self) -> "tuple[float, ...]":
+        """p_i = stochastic_depth * i / (n - 1) of every block of the net, in order"""
+        return tuple(blk.drop_prob for blk in self.blocks())
+
+    def _sites(self) -> "list[_Block]":
+        """the blocks that take a keep factor in the current mode: those with p_i > 0, in training mode"""
+        return [blk for blk in self.blocks() if blk.drops()]
+
+    def _vt_keep_rates(self) -> "tuple[float, ...]":
+        """the drop probability of every site of the keep table (empty: this mode has no table); part of the program cache key"""
+        return tuple(blk.drop_prob for blk in self._sites())
+
+    @property
+    def n_keep_sites(self) -> int:
+        """rows of the keep table in training mode: the blocks with p_i > 0"""
+        return sum(blk.drop_prob > 0.0 for blk in self.blocks())
+
+    def set_keep_factors(self, t: Optional[Tensor]) -> None:
+        """Fix the stochastic-depth keep factors of the following forwards: a float[n_keep_sites][B] tensor, one row per block
+        with p_i > 0 in order and one factor per image (0 drops the image's branch, 1 / (1 - p_i) is what a kept one gets in
+        training; any value is taken), used by the eager path and the launch-list engine alike instead of drawing.  None:
+        draw again.  Eval mode ignores it."""
+        if t is not None:
+            if t.dim() != 2 or t.shape[0] != self.n_keep_sites:
+                raise ValueError(f"keep factors of shape {tuple(t.shape)}: {self.model_name} with stochastic_depth="
+                                 f"{self.stochastic_depth} has {self.n_keep_sites} dropping blocks (rows), one column per image")
+            t = t.detach().to(torch.float32).clone()
+        self._keep_override = t
 
     # -- launch-list emission ----------------------------------------------------------
     def _vt_emit_maps(self, b, x):
@@ -179,10 +238,12 @@ class ResNetExtractor(BaseBackbone):
         Hs, Ws = (x.H + 1) // 2, (x.W + 1) // 2
         pooled = b.act(x.B, (Hs - 1) // 2 + 1, (Ws - 1) // 2 + 1, fe.conv1.out_channels, "maxpool")
         maps = [b.stem7_unit(x, fe.conv1, fe.bn1, 1, pool_out=pooled, name="conv1")]
+        sites = self._sites()
+        rows = dict(zip(map(id, sites), b.keep_table([blk.drop_prob for blk in sites], x.B))) if sites else {}
         o = pooled
         for i, layer in enumerate(fe.layers(), start=1):
             for k, blk in enumerate(layer):
-                o = blk._vt_emit(b, o, name=f"layer{i}.{k}")
+                o = blk._vt_emit(b, o, name=f"layer{i}.{k}", keep=rows.get(id(blk)))
             maps.append(o)
         return maps
 
@@ -190,9 +251,16 @@ class ResNetExtractor(BaseBackbone):
         fe = self.feat_extractor
         maps = [fe.relu(fe.bn1(fe.conv1(x)))]
         h = fe.maxpool(maps[0])
+        sites = self._sites()
+        keep = {}
+        if sites:
+            from ..program import draw_keep_factors
+
+            table = draw_keep_factors([blk.drop_prob for blk in sites], x.shape[0], x.device, self._keep_override)
+            keep = {id(blk): table[r] for r, blk in enumerate(sites)}
         for layer in fe.layers():
             for blk in layer:
-                h = blk._eager(h)
+                h = blk._eager_maps(h, keep.get(id(blk)))[-1]
             maps.append(h)
         return maps
 

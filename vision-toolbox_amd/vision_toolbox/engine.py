@@ -905,6 +905,9 @@ class Builder:
         residual with one factor per image: the normalise pass and the BatchNorm backward are the keep passes of vt_mbconv.hip
         (any activation code; the residual's gradient stays d(y)).  As with residual_pre_act, the pointwise fold, the fused
         inference epilogue and a deferred normalise pass are not taken.  keep=None emits what it always emitted.
+        `keep` with `residual_pre_act`: y = relu(keep[b] * bn(conv(x)) + residual) -- stochastic depth of a ResNet block, the drop
+        behind the last BatchNorm and in front of the shortcut -- on the keep forms of the add-then-ReLU passes (vt_resnet.hip):
+        the identity's gradient stays the masked d(y), the BatchNorm side sees keep[b] times it.
         Validation and dispatch: grouped -> depthwise -> pointwise -> the general kernels."""
         conv, bn_spec = self._specs(conv, norm)
         relu = int(relu)  # activation code: 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 SiLU, 4 GELU, 5 ReLU6, 6 Hardswish (include/vt_amd.h)
@@ -912,7 +915,9 @@ class Builder:
         if pre_act and (residual is None or bn_spec is None or relu != 1 or conv.groups != 1 or pool_out is not None):
             raise NotImplementedError(f"{name}: residual_pre_act is relu(bn(conv(x)) + residual): it needs a residual, a "
                                       "BatchNorm, ReLU, groups = 1 and no fused pool")
-        if keep is not None and (residual is None or bn_spec is None or conv.groups != 1 or pool_out is not None or pre_act):
+        # (keep with residual_pre_act: relu(keep[b] * bn(conv(x)) + residual), the keep forms of the add-then-ReLU passes;
+        #  the checks of residual_pre_act above are the ones it needs)
+        if keep is not None and not pre_act and (residual is None or bn_spec is None or conv.groups != 1 or pool_out is not None):
             raise NotImplementedError(f"{name}: keep is keep[b] * act(bn(conv(x))) + residual: it needs a residual, a BatchNorm, "
                                       "groups = 1, no fused pool and no residual_pre_act")
         if conv.groups != 1:
@@ -1056,6 +1061,13 @@ class Builder:
             u.pool_out, u.pool_am = pool_out, self.alloc(y.B * pool_out.H * pool_out.W * y.C, "argmax")
             self._act_apply(z, bn.cp[0], bn.cp[1], res, y, relu, [pool_out.addr(), self.bp(u.pool_am)],
                             [pool_out.ld, y.B, y.H, y.W])
+        elif u.pre_act and u.keep is not None and fin_fwd:
+            ptrs, flts = bn.finalize_operands(stats, y.M)
+            self.emit(N.OP_BN_ADD_ACT_KEEP_FIN_APPLY, ptrs + [z.addr(), res.addr(), y.addr(), u.keep],
+                      [y.C, z.ld, res.ld, y.ld, self.dtype, y.H * y.W], flts + [y.M])
+        elif u.pre_act and u.keep is not None:
+            self.emit(N.OP_BN_ADD_ACT_KEEP_APPLY, [z.addr(), bn.cp[0], bn.cp[1], res.addr(), y.addr(), u.keep],
+                      [z.ld, res.ld, y.ld, y.C, self.dtype, y.H * y.W], [y.M])
         elif u.keep is not None and fin_fwd:
             ptrs, flts = bn.finalize_operands(stats, y.M)
             self.emit(N.OP_BN_KEEP_FIN_APPLY, ptrs + [z.addr(), res.addr(), y.addr(), u.keep],
@@ -1209,17 +1221,23 @@ class Builder:
             dr, acc = self.grad_accum_target(r)
         else:  # (nothing reads it: the pass has two outputs)
             dr, acc = self.act(r.B, r.H, r.W, r.C, u.name + ".dr"), 0
-        self.emit(N.OP_BN_ADD_ACT_BWD_REDUCE, [dy.addr(), y.addr(), z.addr(), bn.cp[2], bn.cp[3], self.bp(sums)],
-                  [dy.ld, y.ld, z.ld, y.C, dt], [M])
+        # (u.keep: the keep forms take the plain forms' operands, then the row of the keep table and HW)
+        kp, khw = ([u.keep], [y.H * y.W]) if u.keep is not None else ([], [])
+        red, fin, app = ((N.OP_BN_ADD_ACT_KEEP_BWD_REDUCE, N.OP_BN_ADD_ACT_KEEP_BWD_FIN_APPLY, N.OP_BN_ADD_ACT_KEEP_BWD_APPLY)
+                         if u.keep is not None else
+                         (N.OP_BN_ADD_ACT_BWD_REDUCE, N.OP_BN_ADD_ACT_BWD_FIN_APPLY, N.OP_BN_ADD_ACT_BWD_APPLY))
+        self.emit(red, [dy.addr(), y.addr(), z.addr(), bn.cp[2], bn.cp[3], self.bp(sums)] + kp,
+                  [dy.ld, y.ld, z.ld, y.C, dt] + khw, [M])
         if self.bn_fin_apply and not self.bn_sync:
-            self.emit(N.OP_BN_ADD_ACT_BWD_FIN_APPLY,
+            self.emit(fin,
                       [self.bp(sums), bn.cp[0], bn.cp[2], bn.cp[3], *bn.grads(), self.bp(bcoef), dy.addr(), y.addr(), z.addr(),
-                       dz.addr(), dr.addr()],
-                      [y.C, int(bn.spec.training), dy.ld, y.ld, z.ld, dz.ld, dr.ld, acc, dt], [M * self.bn_world, 1.0 / self.bn_world, M])
+                       dz.addr(), dr.addr()] + kp,
+                      [y.C, int(bn.spec.training), dy.ld, y.ld, z.ld, dz.ld, dr.ld, acc, dt] + khw,
+                      [M * self.bn_world, 1.0 / self.bn_world, M])
         else:
             bn.bwd_finalize(sums, bcoef, M)
-            self.emit(N.OP_BN_ADD_ACT_BWD_APPLY, [dy.addr(), y.addr(), z.addr(), self.bp(bcoef), dz.addr(), dr.addr()],
-                      [dy.ld, y.ld, z.ld, dz.ld, dr.ld, acc, y.C, dt], [M])
+            self.emit(app, [dy.addr(), y.addr(), z.addr(), self.bp(bcoef), dz.addr(), dr.addr()] + kp,
+                      [dy.ld, y.ld, z.ld, dz.ld, dr.ld, acc, y.C, dt] + khw, [M])
         if r.needs_grad:
             self.grad_written(r)
         return dz
@@ -2931,6 +2949,32 @@ class Builder:
         self.emit(N.OP_XENT, [logits.addr(), (LABELS, 0), self.bp(loss), g.addr() if g else None,
                               (HYPER, self.MIX_OFF) if mix else None],
                   [logits.ld, g.ld if g else 0, Bn, Ncls, self.dtype], [label_smoothing, grad_scale])
+        return loss
+
+    def bce(self, logits: TRef, label_smoothing: float, grad_scale: float, mix: bool = False,
+            num_classes: Optional[int] = None, target_threshold: Optional[float] = None, sum_classes: bool = False) -> Buf:
+        """binary cross-entropy against the smoothed (mixed, thresholded) one-hot target in the place of `xent`
+        (vt_sigmoid_bce, include/vt_amd.h): the same operands, plus one double per row of scratch from which the loss is
+        added in row order.  `target_threshold=None`: soft targets; `sum_classes`: the loss is summed over the classes and
+        averaged over the batch, and the gradient loses its 1 / N.  A widened head as in `xent`."""
+        self.tag += 1
+        loss = self.zeroed_f32(64, "loss")
+        Bn, Ncls = logits.B, logits.C if num_classes is None else num_classes
+        assert 0 < Ncls <= logits.C
+        g = None
+        if self.need_grad:
+            gs = self._gs(logits)
+            g = self._gref(logits)
+            gs.init.append((logits.coff, logits.coff + logits.C))
+            if Ncls < logits.C:
+                assert g.coff == 0 and g.ld == g.C, "a widened head is a dense map of its own"
+                self.emit(N.OP_MEMSET, [g.addr()], [0], [g.M * g.C * g.esize])
+        rows = self.f32(2 * Bn, "bce.rows")  # double[B]
+        flags = (N.VT_BCE_SUM_CLASSES if sum_classes else 0) | (N.VT_BCE_THRESHOLD if target_threshold is not None else 0)
+        self.emit(N.OP_BCE, [logits.addr(), (LABELS, 0), self.bp(loss), g.addr() if g else None,
+                             (HYPER, self.MIX_OFF) if mix else None, self.bp(rows)],
+                  [logits.ld, g.ld if g else 0, Bn, Ncls, self.dtype, flags],
+                  [label_smoothing, grad_scale, 0.0 if target_threshold is None else target_threshold])
         return loss
 
     def xent_eval(self, logits: TRef, num_classes: Optional[int] = None) -> Buf:

@@ -47,6 +47,8 @@ _NORMS = (nn.modules.batchnorm._BatchNorm, nn.modules.instancenorm._InstanceNorm
 GROUP_NORM, GROUP_BIAS, GROUP_OTHER = 0, 1, 2  # flat-buffer order: small, late-produced groups first
 # classifier.py:46,157-169 takes the name.  RMSprop is not built; of the timm names (classifier.py:165) only Lamb is
 OPTIMIZERS = ("SGD", "AdamW", "Adam", "Lamb")
+# the training loss: softmax cross-entropy (classifier.py:92), or binary cross-entropy on the same targets (vt_sigmoid_bce)
+LOSSES = ("ce", "bce")
 # HYPER buffer (16 floats): [0..3] learning rate; [4] optimiser step count t (int32 bits), [5] 1 - beta1^t,
 # [6] sqrt(1 - beta2^t), [7] free (vt_adam_tick / vt_adamw); [8..15] MixUp / CutMix block
 HYPER_STEP = 4
@@ -164,6 +166,9 @@ class TrainStep:
         lamb_max_grad_norm: Optional[float] = 1.0,
         trust_clip: bool = False,
         always_adapt: bool = False,
+        loss: str = "ce",
+        bce_target_threshold: Optional[float] = None,
+        bce_sum_classes: bool = False,
     ):
         """optimizer="Lamb": LAMB in the form of timm.optim.Lamb(bias_correction=True, grad_averaging=True) as
         include/vt_amd.h states it (timm is no dependency; that statement is the definition).  `lamb_max_grad_norm`,
@@ -173,8 +178,19 @@ class TrainStep:
         clip_grad_norm=C (any optimiser): the averaged gradient is scaled by min(1, C / (norm + 1e-6)) before the optimiser
         sees it, as torch.nn.utils.clip_grad_norm_ (Lightning's gradient_clip_val, "norm" algorithm) does.  None builds
         today's launch lists; float("inf") builds the clipping ops with a factor of exactly 1 / world.  The thresholds
-        live on the device: set_clip_grad_norm changes C under a captured graph, last_grad_norm reads the norm back."""
+        live on the device: set_clip_grad_norm changes C under a captured graph, last_grad_norm reads the norm back.
+        loss="bce": binary cross-entropy against the smoothed (and, with `mix`, mixed) one-hot target, as include/vt_amd.h
+        states it (timm.loss.BinaryCrossEntropy behind timm's Mixup; that statement is the definition).
+        `bce_target_threshold` and `bce_sum_classes` are timm's `target_threshold` and `sum_classes`.  The loss is a
+        fixed-order sum: loss() is bit-identical from run to run.  validate() keeps plain cross-entropy."""
         N.lib()
+        if loss not in LOSSES:
+            raise ValueError(f"loss={loss!r}: supported are {', '.join(LOSSES)}")
+        if loss != "bce" and (bce_target_threshold is not None or bce_sum_classes):
+            raise ValueError(f"bce_target_threshold / bce_sum_classes belong to loss='bce', not to loss={loss!r}")
+        if bce_target_threshold is not None and not math.isfinite(float(bce_target_threshold)):
+            raise ValueError(f"bce_target_threshold={bce_target_threshold!r}: None or a finite number")
+        self.loss_name = loss
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer={optimizer!r}: supported are {', '.join(OPTIMIZERS)}")
         self.optimizer, self._betas, self._eps = optimizer, (float(betas[0]), float(betas[1])), float(eps)
@@ -361,15 +377,20 @@ class TrainStep:
         # (include_pool=False: the last entry IS the backbone's forward output, [B,1,1,C] -- no pooling launch)
         pooled = b.global_avgpool(fmap, "head.pool") if self.include_pool else fmap
         logits = b.conv_unit(pooled, E.ConvSpec.from_linear(head, self._head_rows), None, False, name="head.linear")
-        self._loss_buf = b.xent(logits, label_smoothing, 1.0 / batch_size, mix=self.mix, num_classes=num_classes)
+        if loss == "bce":
+            self._loss_buf = b.bce(logits, label_smoothing, 1.0 / batch_size, mix=self.mix, num_classes=num_classes,
+                                   target_threshold=bce_target_threshold, sum_classes=bool(bce_sum_classes))
+        else:
+            self._loss_buf = b.xent(logits, label_smoothing, 1.0 / batch_size, mix=self.mix, num_classes=num_classes)
         self._logits = logits
         b.build_backward()
         self.prog = Program(b, [logits], [])
         self.n_units = b.n_units
-        # stochastic depth (an EfficientNet's residual blocks): the keep table float[n_sites][B] of the training program lives
-        # in the arena and is written before every step, outside the launch lists -- drawn from a generator this object owns
-        # (seeded with drop_seed, plus the rank under data parallelism: every rank drops its own images), or the values of
-        # set_keep_factors.  validate() compiles an eval-mode program, which has no table.
+        # stochastic depth (an EfficientNet's residual blocks, the blocks of a ResNetExtractor(stochastic_depth=...)): the keep
+        # table float[n_sites][B] of the training program lives in the arena and is written before every step, outside the
+        # launch lists -- drawn from a generator this object owns (seeded with drop_seed, plus the rank under data
+        # parallelism: every rank drops its own images), or the values of set_keep_factors.  validate() compiles an eval-mode
+        # program, which has no table.
         self._keep_buf, self._keep_rates = b.keep_buf, b.keep_rates
         self._keep_override: Optional[torch.Tensor] = None
         self.drop_seed = int(drop_seed) + (torch.distributed.get_rank(process_group) if self.dp else 0)
