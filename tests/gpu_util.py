@@ -1,6 +1,7 @@
 """Helpers for the GPU parity tests: raw C-ABI calls on torch device tensors."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 
@@ -72,3 +73,19 @@ def rel_err(a: torch.Tensor, b: torch.Tensor) -> float:
 
 def tol(dtype: int, f32: float = 2e-5, bf16: float = 6e-3) -> float:
     return f32 if dtype == N.VT_F32 else bf16
+
+
+@contextlib.contextmanager
+def short_grids(on: bool = True):
+    """Two workgroups per channel group in the BatchNorm passes that finalize for themselves (VT_BN_FIN_APPLY_WGS) and in the
+    backward reductions (VT_BN_RED_BLOCKS), so that a few hundred rows already give every thread several trips of its row
+    loop, a partial last trip and a ragged last row block.  The defaults come back on the way out."""
+    if on:
+        N.set_knob("VT_BN_FIN_APPLY_WGS", 2)
+        N.set_knob("VT_BN_RED_BLOCKS", 2)
+    try:
+        yield
+    finally:
+        if on:
+            N.set_knob("VT_BN_FIN_APPLY_WGS", 1536)
+            N.set_knob("VT_BN_RED_BLOCKS", 1024)

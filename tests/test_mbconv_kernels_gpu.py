@@ -23,22 +23,37 @@ import torch.nn.functional as F
 from oracle import filler
 from vision_toolbox import _native as N
 
-from gpu_util import DNAME, DTYPES, TD, rel_err, rounded, stream, tol, vp
+from gpu_util import DNAME, DTYPES, TD, rel_err, rounded, short_grids, stream, tol, vp
 
 pytestmark = pytest.mark.gpu
 
 EPS, MOM = 1e-5, 0.1
 # (B, HW, C).  (3, 25, 136): channel groups with a remainder, image boundaries inside a row block; (5, 1, 64): one pixel per
 # image; (2, 700, 24): more rows than one workgroup walks in a sweep; (2, 9, 256): the reduction's channel groups of 64 and two
-# finalize groups in both dtypes
-KEEP_SHAPES = [(3, 25, 8), (3, 25, 136), (5, 1, 64), (2, 700, 24), (2, 9, 256)]
+# finalize groups in both dtypes; (2, 25, 1032): 258 chunks per row in f32, more than a block has threads -- a second pass of
+# the column loop with two live columns -- and no finalize group, the two launches
+KEEP_SHAPES = [(3, 25, 8), (3, 25, 136), (5, 1, 64), (2, 700, 24), (2, 9, 256), (2, 25, 1032)]
+# on a grid of two row blocks per channel group: several trips of every thread's row loop, the last one partial (7 / 14 at 72
+# channels, 25 with two finalize groups and 13 with the reduction's four groups at 256), 194 live rows in the last block, and
+# the image boundary at row 130 inside the first block's band -- with a dropped, a kept and a rescaled image
+SHORT_GRIDS = [(3, 130, 72), (3, 130, 256)]
+KEEP_SHAPES += SHORT_GRIDS
 KEEP_ROWS = {"ones": lambda B: [1.0] * B, "zeros": lambda B: [0.0] * B,
              "alternate": lambda B: [0.0 if b % 2 == 0 else 1.25 for b in range(B)],
              "fractions": lambda B: [0.5 if b % 2 == 0 else 2.0 for b in range(B)]}
+SHORT_GRID_ROWS = {"mixed": lambda B: [(0.0, 1.0, 1.25)[b % 3] for b in range(B)]}
 ACTS = {0: lambda u: u, 3: F.silu}
 POOL_SHAPES = [(3, 49, 96), (3, 1, 8), (2, 130, 200), (4, 9, 672), (2, 2000, 64)]
 SE_SHAPES = [(3, 96, 4), (2, 144, 6), (2, 40, 1), (3, 1152, 48)]
 _ids = lambda shapes: [f"{a}x{b}x{c}" for a, b, c in shapes]
+
+
+@pytest.fixture(autouse=True)
+def _grid_of_the_case(request):
+    """the SHORT_GRIDS cases run with two row blocks per channel group (gpu_util.short_grids)"""
+    params = getattr(request.node, "callspec", None)
+    with short_grids(params is not None and params.params.get("shape") in SHORT_GRIDS):
+        yield
 
 
 def _place(t, dtype, sliced):
@@ -99,7 +114,7 @@ def _reference(shape, dtype, kind, act, train, with_add=False):
     if key not in _REFS:
         B, HW, Cc = shape
         z, r, dy, gamma, beta, rm, rv = _inputs(shape, dtype)
-        keep = torch.tensor(KEEP_ROWS[kind](B) if kind else [1.0] * B, dtype=torch.float64)
+        keep = torch.tensor({**KEEP_ROWS, **SHORT_GRID_ROWS}[kind](B) if kind else [1.0] * B, dtype=torch.float64)
         add = rounded(filler.tensor(f"mbconv{shape}add", (B, Cc)) * HW ** 0.5, dtype) if with_add else torch.zeros(B, Cc)
         zd = z.double().requires_grad_(True)
         g, b = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
@@ -138,7 +153,7 @@ def test_keep_forward(shape, dtype):
     M, lib = B * HW, N.lib()
     z, r, dy, gamma, beta, rm, rv = _inputs(shape, dtype)
     gd, bd = gamma.cuda(), beta.cuda()
-    for kind in KEEP_ROWS:
+    for kind in (SHORT_GRID_ROWS if shape in SHORT_GRIDS else KEEP_ROWS):
         for act in ACTS:
             for fin in (False, True):
                 ref = _reference(shape, dtype, kind, act, 1 if fin else 0)  # (ready coefficients: the eval-mode ones)
@@ -194,7 +209,8 @@ def test_keep_backward(shape, dtype):
     z, r, dy, gamma, beta, rm, rv = _inputs(shape, dtype)
     # every keep row without an addend; then the addend (the gradient of a per-image average pool of act(bn(z))) with no keep
     # row at all (factor 1: the depthwise unit of an MBConv block) and beside a row that drops images
-    for kind, with_add in [(k, False) for k in KEEP_ROWS] + [(None, True), ("alternate", True)]:
+    rows, both = (SHORT_GRID_ROWS, "mixed") if shape in SHORT_GRIDS else (KEEP_ROWS, "alternate")
+    for kind, with_add in [(k, False) for k in rows] + [(None, True), (both, True)]:
         for act in ACTS:
             for train in (1, 0):
                 ref = _reference(shape, dtype, kind, act, train, with_add)

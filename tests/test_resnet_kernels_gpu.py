@@ -17,7 +17,7 @@ import torch.nn.functional as F
 from oracle import filler
 from vision_toolbox import _native as N
 
-from gpu_util import DNAME, DTYPES, TD, krsc, nhwc, rel_err, rounded, stream, to_nchw, tol, vp
+from gpu_util import DNAME, DTYPES, TD, krsc, nhwc, rel_err, rounded, short_grids, stream, to_nchw, tol, vp
 
 pytestmark = pytest.mark.gpu
 
@@ -25,7 +25,20 @@ pytestmark = pytest.mark.gpu
 # groups, the reduction's channel split, more chunks per row than threads (f32); (1031, 72): a ragged row count and a
 # channel count with no divisor in [32, 128] but itself
 SHAPES = [(98, 64), (392, 256), (50, 2048), (1031, 72)]
+# on a grid of two row blocks per channel group: 7 (bf16) / 14 (f32) trips of the row loop in one group of 72 channels, 25 in
+# two finalize groups of 128 and 13 in the reduction's four groups of 64 -- never a multiple of the rows in flight, the last
+# trip partial, 194 live rows in the last block, idle row lanes at 72 channels
+SHORT_GRIDS = [(390, 72), (390, 256)]
+SHAPES += SHORT_GRIDS
 EPS, MOM = 1e-5, 0.1
+
+
+@pytest.fixture(autouse=True)
+def _grid_of_the_case(request):
+    """the SHORT_GRIDS cases run with two row blocks per channel group (gpu_util.short_grids)"""
+    params = getattr(request.node, "callspec", None)
+    with short_grids(params is not None and params.params.get("shape") in SHORT_GRIDS):
+        yield
 
 
 def _inputs(M, Cc, dtype):

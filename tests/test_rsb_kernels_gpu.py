@@ -16,7 +16,7 @@ from oracle import filler
 from vision_toolbox import _native as N
 
 import rsb_util as RU
-from gpu_util import DNAME, DTYPES, TD, rel_err, rounded, stream, tol, vp
+from gpu_util import DNAME, DTYPES, TD, rel_err, rounded, short_grids, stream, tol, vp
 
 pytestmark = pytest.mark.gpu
 
@@ -25,11 +25,25 @@ NAN = float("nan")
 # map with a channel count that is no power of two; 45 rows per image
 CASES = [(2, 1, 8, None), (7, 3, 24, 40), (3, 49, 136, None), (5, 45, 72, None)]
 KEEPS = {"ones": (1.0,), "zeros": (0.0,), "drop_first": (0.0, 1.25), "scaled": (0.5, 2.0)}
+# on a grid of two row blocks per channel group: several trips of every thread's row loop, the last one partial (7 / 14 at 72
+# channels, 25 with two finalize groups and 13 with the reduction's four groups at 256), 194 live rows in the last block, and
+# the image boundary at row 130 inside the first block's band -- with a dropped, a kept and a rescaled image
+SHORT_GRIDS = [(3, 130, 72, None), (3, 130, 256, None)]
+CASES += SHORT_GRIDS
+SHORT_GRID_KEEPS = {"ones": (1.0,), "mixed": (0.0, 1.0, 1.25)}
 EPS, MOM = RU.EPS, RU.MOM
 
 
+@pytest.fixture(autouse=True)
+def _grid_of_the_case(request):
+    """the SHORT_GRIDS cases run with two row blocks per channel group (gpu_util.short_grids)"""
+    params = getattr(request.node, "callspec", None)
+    with short_grids(params is not None and params.params.get("case") in SHORT_GRIDS):
+        yield
+
+
 def _keep(name, B):
-    pat = KEEPS[name]
+    pat = {**KEEPS, **SHORT_GRID_KEEPS}[name]
     return torch.tensor([pat[b % len(pat)] for b in range(B)], dtype=torch.float32)
 
 
@@ -118,7 +132,7 @@ def test_keep_forward(case, dtype):
     z, r, gamma, beta, dy, dr0, rm, rv = _inputs(B, HW, Cc, dtype)
     lib = N.lib()
     gd, bd = gamma.cuda(), beta.cuda()
-    for kname in KEEPS:
+    for kname in (SHORT_GRID_KEEPS if case in SHORT_GRIDS else KEEPS):
         keep = _keep(kname, B)
         kd = keep.cuda()
         dropped = _rows(keep, HW, 0.0)
@@ -164,7 +178,7 @@ def test_keep_backward(case, dtype):
     M = B * HW
     z, r, gamma, beta, dy, dr0, rm, rv = _inputs(B, HW, Cc, dtype)
     lib = N.lib()
-    for kname in KEEPS:
+    for kname in (SHORT_GRID_KEEPS if case in SHORT_GRIDS else KEEPS):
         keep = _keep(kname, B)
         kd = keep.cuda()
         dropped = _rows(keep, HW, 0.0)

@@ -45,6 +45,17 @@ struct VtFinBwd {  // the arguments of vt_bn_bwd_finalize
     double inv_count, pscale;
     int C, train;
 };
+// (arguments in the order of the C entry points; `count` elements per channel went into the sums)
+inline VtFinFwd make_fin_fwd(const float* stats, int C, double count, const float* gamma, const float* beta, float eps, float momentum,
+                             float* running_mean, float* running_var, int64_t* nbt, float* scale, float* shift, float* mean,
+                             float* invstd) {
+    return VtFinFwd{stats, gamma, beta, running_mean, running_var, nbt, scale, shift, mean, invstd,
+                    1.0 / count, count > 1.0 ? count / (count - 1.0) : 1.0, eps, momentum, C};
+}
+inline VtFinBwd make_fin_bwd(const float* sums, int C, double count, double pscale, const float* scale, const float* mean,
+                             const float* invstd, int train, float* dgamma, float* dbeta, float* coef) {
+    return VtFinBwd{sums, scale, mean, invstd, dgamma, dbeta, coef, 1.0 / count, pscale, C, train};
+}
 
 #ifdef __HIPCC__
 // ---- the finalize arithmetic of one channel (bn_finalize_kernel / bn_bwd_finalize_kernel call these too) ----------------

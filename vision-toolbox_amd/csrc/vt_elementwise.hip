@@ -133,43 +133,31 @@ bn_act_apply_kernel(const VtFinFwd f, const T* __restrict__ z, int ldz, const fl
     }
     const int r = t / rm.CT;
     if (r >= rm.RT) return;
-    const long row0 = (long)(rm.rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * rm.RT * rm.iters + r;
+    const long row0 = rm.row0(r);
     for (int col = t % rm.CT; col < rm.CPR; col += rm.CT) {
         float sc[EPC], sf[EPC];
         if constexpr (kFin) {
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) sc[e] = s_sc[col * EPC + e], sf[e] = s_sf[col * EPC + e];
+            chunk_coef(sc, s_sc, col);
+            chunk_coef(sf, s_sf, col);
         } else {
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) sc[e] = 1.f, sf[e] = 0.f;
-            if (scale) {
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) sc[e] = scale[col * EPC + e];
-            }
-            if (shift) {
-#pragma unroll
-                for (int e = 0; e < EPC; ++e) sf[e] = shift[col * EPC + e];
-            }
+            chunk_coef(sc, scale, col, 1.f);
+            chunk_coef(sf, shift, col, 0.f);
         }
         const T* pz = z + row0 * ldz + col * EPC;
         const T* pr = kRes ? res + row0 * ldr + col * EPC : nullptr;
         T* py = y + row0 * ldy + col * EPC;
         const long sz = (long)rm.RT * ldz, sr = (long)rm.RT * ldr, sy = (long)rm.RT * ldy;
-        // kUnroll rows per trip: all loads are issued before the first use (bytes in flight)
-        for (int it = 0; it < rm.iters; it += kUnroll) {
-            uint4 vz[kUnroll], vr[kUnroll];
-            bool ok[kUnroll];
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                ok[u] = (it + u < rm.iters) && (row0 + (long)(it + u) * rm.RT < M);
+        uint4 vz[kUnroll], vr[kUnroll];
+        rowmap_trips(
+            rm, row0, M,
+            [&](int u, int i, bool ok) VT_TRIP_LAMBDA {
                 vz[u] = vr[u] = make_uint4(0, 0, 0, 0);
-                if (ok[u]) {
-                    vz[u] = ld16(pz + (it + u) * sz);
-                    if (kRes) vr[u] = ld16(pr + (it + u) * sr);
+                if (ok) {
+                    vz[u] = ld16(pz + i * sz);
+                    if (kRes) vr[u] = ld16(pr + i * sr);
                 }
-            }
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
+            },
+            [&](int u, int i, bool ok) VT_TRIP_LAMBDA {
                 float v[EPC];
                 VecIO<T>::unpack(vz[u], v);
 #pragma unroll
@@ -184,9 +172,8 @@ bn_act_apply_kernel(const VtFinFwd f, const T* __restrict__ z, int ldz, const fl
 #pragma unroll
                     for (int e = 0; e < EPC; ++e) v[e] += rr[e];
                 }
-                if (ok[u]) st16(py + (it + u) * sy, VecIO<T>::pack(v));
-            }
-        }
+                if (ok) st16(py + i * sy, VecIO<T>::pack(v));
+            });
     }
 }
 
@@ -419,7 +406,7 @@ bn_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ z
     const int t = threadIdx.x;
     const int r = t / rm.CT;
     const int tc = t % rm.CT;
-    const long row0 = (long)(rm.rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * rm.RT * rm.iters + r;
+    const long row0 = rm.row0(r);
     const int rep = blockIdx.x % kStatReplicas;
     // blockIdx.y: channel group (C channels each of Ctot; round 4).  On the small maps a block's 2 * C fixed-point atomics
     // were half of the launch (C = 512 @7x7: 242 blocks x 1024 atomics, 14.6 us of which ~7 in that tail; twice the blocks:
@@ -436,28 +423,23 @@ bn_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ z
         for (int e = 0; e < EPC; ++e) s1[e] = s2[e] = 0.f;
         if (active) {
             float sc[EPC], sf[EPC], mu[EPC];
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) {
-                sc[e] = scale[col * EPC + e];
-                sf[e] = shift[col * EPC + e];
-                mu[e] = mean[col * EPC + e];
-            }
+            chunk_coef(sc, scale, col);
+            chunk_coef(sf, shift, col);
+            chunk_coef(mu, mean, col);
             const T* pg = dy + row0 * lddy + col * EPC;
             const T* pz = z + row0 * ldz + col * EPC;
             const long sg = (long)rm.RT * lddy, sz = (long)rm.RT * ldz;
-            for (int it = 0; it < rm.iters; it += kUnroll) {
-                uint4 vg[kUnroll], vz[kUnroll];
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u) {
-                    const long row = row0 + (long)(it + u) * rm.RT;
+            uint4 vg[kUnroll], vz[kUnroll];
+            rowmap_trips(
+                rm, row0, M,
+                [&](int u, int i, bool ok) VT_TRIP_LAMBDA {
                     vg[u] = vz[u] = make_uint4(0, 0, 0, 0);  // zero dy contributes nothing
-                    if ((it + u < rm.iters) && row < M) {
-                        vg[u] = ld16(pg + (it + u) * sg);
-                        vz[u] = ld16(pz + (it + u) * sz);
+                    if (ok) {
+                        vg[u] = ld16(pg + i * sg);
+                        vz[u] = ld16(pz + i * sz);
                     }
-                }
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u) {
+                },
+                [&](int u, int, bool) VT_TRIP_LAMBDA {
                     float g[EPC], zz[EPC];
                     VecIO<T>::unpack(vg[u], g);
                     VecIO<T>::unpack(vz[u], zz);
@@ -469,14 +451,10 @@ bn_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restrict__ z
                         s1[e] += gg;
                         s2[e] = fmaf(gg, zz[e] - mu[e], s2[e]);  // invstd applied once, below
                     }
-                }
-            }
+                });
         }
         rowlane_fold(sred, s, rm.CT, rm.RT, [&](int which, int lc, float acc) {
-            const int c = cbase * EPC + lc;
-            if (c >= C) return;
-            if (which) acc *= invstd[c];
-            vt_stat_add(sums, ((long)rep * 2 + which) * Ctot + cg0 * EPC + c, acc);
+            bn_sums_emit(sums, rep, Ctot, cg0 * EPC, invstd, C, which, cbase * EPC + lc, acc);
         });
     }
 }
@@ -511,47 +489,34 @@ bn_bwd_apply_kernel(const VtFinBwd f, const T* __restrict__ dy, int lddy, const 
     }
     const int r = t / rm.CT;
     if (r >= rm.RT) return;
-    const long row0 = (long)(rm.rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * rm.RT * rm.iters + r;
+    const long row0 = rm.row0(r);
     for (int col = t % rm.CT; col < rm.CPR; col += rm.CT) {
         float sc[EPC], sf[EPC], ca[EPC], cb[EPC], cd[EPC];
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-            const int c = col * EPC + e;
-            if constexpr (kFin) {
-                sc[e] = scale[c];
-                sf[e] = shift[c];
-                ca[e] = s_a[c], cb[e] = s_b[c], cd[e] = s_d[c];
-            } else if constexpr (GEN) {  // (no coefficients: dz = dy * act'(z), the unit without a BatchNorm)
-                sc[e] = scale ? scale[c] : 1.f;
-                sf[e] = shift ? shift[c] : 0.f;
-                ca[e] = coef ? coef[c] : 1.f;
-                cb[e] = coef ? coef[C + c] : 0.f;
-                cd[e] = coef ? coef[2 * C + c] : 0.f;
-            } else {
-                sc[e] = scale[c];
-                sf[e] = shift[c];
-                ca[e] = coef[c];
-                cb[e] = coef[C + c];
-                cd[e] = coef[2 * C + c];
-            }
+        if constexpr (kFin) {
+            chunk_coef(sc, scale, col), chunk_coef(sf, shift, col);
+            chunk_coef(ca, s_a, col), chunk_coef(cb, s_b, col), chunk_coef(cd, s_d, col);
+        } else if constexpr (GEN) {  // (no coefficients: dz = dy * act'(z), the unit without a BatchNorm)
+            chunk_coef(sc, scale, col, 1.f), chunk_coef(sf, shift, col, 0.f);
+            chunk_coef(ca, coef, col, 1.f);
+            chunk_coef(cb, coef ? coef + C : nullptr, col, 0.f), chunk_coef(cd, coef ? coef + 2 * C : nullptr, col, 0.f);
+        } else {
+            chunk_coef(sc, scale, col), chunk_coef(sf, shift, col);
+            chunk_coef(ca, coef, col), chunk_coef(cb, coef + C, col), chunk_coef(cd, coef + 2 * C, col);
         }
-        for (int it = 0; it < rm.iters; it += kUnroll) {
-            uint4 vg[kUnroll], vz[kUnroll];
-            bool ok[kUnroll];
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                const long row = row0 + (long)(it + u) * rm.RT;
-                ok[u] = (it + u < rm.iters) && row < M;
+        uint4 vg[kUnroll], vz[kUnroll];
+        rowmap_trips(
+            rm, row0, M,
+            [&](int u, int i, bool ok) VT_TRIP_LAMBDA {
+                const long row = row0 + (long)i * rm.RT;
                 vg[u] = vz[u] = make_uint4(0, 0, 0, 0);
-                if (ok[u]) {
+                if (ok) {
                     vg[u] = ld16(dy + row * lddy + col * EPC);
                     vz[u] = ld16(z + row * ldz + col * EPC);
                 }
-            }
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                if (!ok[u]) continue;
-                const long row = row0 + (long)(it + u) * rm.RT;
+            },
+            [&](int u, int i, bool ok) VT_TRIP_LAMBDA {
+                if (!ok) return;
+                const long row = row0 + (long)i * rm.RT;
                 float g[EPC], zz[EPC];
                 VecIO<T>::unpack(vg[u], g);
                 VecIO<T>::unpack(vz[u], zz);
@@ -563,8 +528,7 @@ bn_bwd_apply_kernel(const VtFinBwd f, const T* __restrict__ dy, int lddy, const 
                     g[e] = fmaf(ca[e], gg, fmaf(-cb[e], zz[e], cd[e]));
                 }
                 st16(dz + row * lddz + col * EPC, VecIO<T>::pack(g));
-            }
-        }
+            });
     }
 }
 
@@ -1417,16 +1381,6 @@ __global__ void __launch_bounds__(kThreads) pack_dgrad_batch_kernel(const PackBa
     }
 }
 
-// Walking order of the three BatchNorm passes over their rows (bit 0: bn_act_apply, 1: bn_bwd_reduce, 2: bn_bwd_apply;
-// set = last row block first).  A pass that follows a kernel which just streamed the same tensor front to back finds
-// that tensor's TAIL in the memory-side cache (256 MB), not its head: walking backwards would turn those into hits.
-// Measured on the full step, every combination: 23.14 .. 23.25 ms against 23.23 .. 23.25 for the default (0) -- no
-// effect beyond noise; the knob stays for experiments.
-inline int vt_bn_order() {
-    const int v = (0);
-    return v;
-}
-
 __global__ void __launch_bounds__(kThreads)
 fixed_to_f32_kernel(const long long* __restrict__ q, float* __restrict__ dst, long n, int accumulate) {
     for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads) {
@@ -1506,9 +1460,8 @@ int vt_bn_finalize(const float* stats, int32_t C, double count, const float* gam
                "vt_bn_finalize: bad argument");
     VT_REQUIRE((running_mean == nullptr) == (running_var == nullptr), VT_ERR_INVALID,
                "vt_bn_finalize: running_mean/var must both be given or both NULL");
-    const double unbias = count > 1.0 ? count / (count - 1.0) : 1.0;
-    VtFinFwd f{stats, gamma, beta, running_mean, running_var, num_batches_tracked, scale, shift, mean, invstd,
-               1.0 / count, unbias, eps, momentum, C};
+    const VtFinFwd f = make_fin_fwd(stats, C, count, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, scale,
+                                    shift, mean, invstd);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, f);
     VT_CHECK_LAUNCH("vt_bn_finalize");
     return VT_OK;
@@ -1561,8 +1514,7 @@ int vt_bn_act_apply(const void* z, int32_t ldz, const float* scale, const float*
     VT_TRY(check_mat("vt_bn_act_apply(z)", z, ldz, C, dtype));
     VT_TRY(check_mat("vt_bn_act_apply(y)", y, ldy, C, dtype));
     if (residual) VT_TRY(check_mat("vt_bn_act_apply(residual)", residual, ldr, C, dtype));
-    RowMap rm = RowMap::make(C, vt_epc(dtype), M);
-    rm.rev = (vt_bn_order() >> 0) & 1;
+    const RowMap rm = RowMap::make(C, vt_epc(dtype), M);
     VT_REQUIRE(relu >= 0 && relu <= 6, VT_ERR_INVALID, "vt_bn_act_apply: activation code %d", relu);
     const VtFinFwd f{};
     if (relu >= 2) {  // LeakyReLU(0.2) / SiLU / GELU: the generic instantiation (off the Darknet / VoVNet path)
@@ -1608,7 +1560,7 @@ int vt_bn_finalize_apply(const float* stats, int32_t C, double count, const floa
                "vt_bn_finalize_apply: running_mean/var must both be given or both NULL");
     VT_REQUIRE(relu >= 0 && relu <= 6, VT_ERR_INVALID, "vt_bn_finalize_apply: activation code %d", relu);
     const int Cg = fin_group(C, vt_epc(dtype));
-    if (relu >= 2 || !Cg || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {
+    if (relu >= 2 || !fin_in_launch(Cg)) {
         const int rc = vt_bn_finalize(stats, C, count, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked,
                                       scale, shift, mean, invstd, stream);
         if (rc != VT_OK) return rc;
@@ -1617,11 +1569,10 @@ int vt_bn_finalize_apply(const float* stats, int32_t C, double count, const floa
     VT_TRY(check_mat("vt_bn_finalize_apply(z)", z, ldz, C, dtype));
     VT_TRY(check_mat("vt_bn_finalize_apply(y)", y, ldy, C, dtype));
     if (residual) VT_TRY(check_mat("vt_bn_finalize_apply(residual)", residual, ldr, C, dtype));
-    const int groups = C / Cg, wgs = VT_KNOB("VT_BN_FIN_APPLY_WGS", 1536);
-    RowMap rm = RowMap::make(Cg, vt_epc(dtype), M, wgs / groups > 0 ? wgs / groups : 1);
-    rm.rev = (vt_bn_order() >> 0) & 1;
-    const VtFinFwd f{stats, gamma, beta, running_mean, running_var, num_batches_tracked, scale, shift, mean, invstd,
-                     1.0 / count, count > 1.0 ? count / (count - 1.0) : 1.0, eps, momentum, C};
+    const int groups = C / Cg;
+    const RowMap rm = fin_rowmap(Cg, groups, vt_epc(dtype), M);
+    const VtFinFwd f = make_fin_fwd(stats, C, count, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, scale,
+                                    shift, mean, invstd);
     const dim3 grid(rm.blocks(M), groups);
     if (residual) {
         VT_DISPATCH_T(dtype, "vt_bn_finalize_apply",
@@ -1647,7 +1598,7 @@ int vt_bn_bwd_finalize_apply(const float* sums, int32_t C, double count, double 
                "vt_bn_bwd_finalize_apply: bad argument");
     VT_REQUIRE(relu >= 0 && relu <= 6, VT_ERR_INVALID, "vt_bn_bwd_finalize_apply: activation code %d", relu);
     const int Cg = fin_group(C, vt_epc(dtype));
-    if (relu >= 2 || !Cg || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {
+    if (relu >= 2 || !fin_in_launch(Cg)) {
         const int rc = vt_bn_bwd_finalize(sums, C, count, pscale, scale, mean, invstd, train, dgamma, dbeta, coef, stream);
         if (rc != VT_OK) return rc;
         return vt_bn_act_bwd_apply(dy, lddy, z, ldz, scale, shift, coef, dz, lddz, M, C, relu, dtype, stream);
@@ -1655,10 +1606,9 @@ int vt_bn_bwd_finalize_apply(const float* sums, int32_t C, double count, double 
     VT_TRY(check_mat("vt_bn_bwd_finalize_apply(dy)", dy, lddy, C, dtype));
     VT_TRY(check_mat("vt_bn_bwd_finalize_apply(z)", z, ldz, C, dtype));
     VT_TRY(check_mat("vt_bn_bwd_finalize_apply(dz)", dz, lddz, C, dtype));
-    const int groups = C / Cg, wgs = VT_KNOB("VT_BN_FIN_APPLY_WGS", 1536);
-    RowMap rm = RowMap::make(Cg, vt_epc(dtype), M, wgs / groups > 0 ? wgs / groups : 1);
-    rm.rev = (vt_bn_order() >> 2) & 1;
-    const VtFinBwd f{sums, scale, mean, invstd, dgamma, dbeta, coef, 1.0 / count, pscale, C, train};
+    const int groups = C / Cg;
+    const RowMap rm = fin_rowmap(Cg, groups, vt_epc(dtype), M);
+    const VtFinBwd f = make_fin_bwd(sums, C, count, pscale, scale, mean, invstd, train, dgamma, dbeta, coef);
     VT_DISPATCH_T(dtype, "vt_bn_bwd_finalize_apply",
                   VT_LAUNCH_STOP((bn_bwd_apply_kernel<T, false, true>), dim3(rm.blocks(M), groups), dim3(kThreads), 0, (hipStream_t)stream, f,
                                  (const T*)dy, lddy, (const T*)z, ldz, scale, shift, (const float*)nullptr, (T*)dz, lddz, (long)M, C,
@@ -1677,32 +1627,20 @@ int vt_bn_act_bwd_reduce(const void* dy, int32_t lddy, const void* z, int32_t ld
                "vt_bn_act_bwd_reduce: bad argument");
     VT_TRY(check_mat("vt_bn_act_bwd_reduce(dy)", dy, lddy, C, dtype));
     VT_TRY(check_mat("vt_bn_act_bwd_reduce(z)", z, ldz, C, dtype));
-    const int epc = vt_epc(dtype);
-    // every block ends with 2*C 64-bit atomics into one of the statistics replicas: ~100 ns each when they queue on the same address,
-    // so fewer, longer blocks win over grid-filling ones (measured per step: 1024 -> 23.53, 512 -> 23.36, 256 -> 23.27 ms)
-    // channel groups of 64 on the small maps with many channels (see the kernel): the row splits shrink by the same factor
-    const int cgroups = (M <= 65536 && C >= 256 && C % 64 == 0) ? C / 64 : 1;
-    const int Cg = C / cgroups;
-    // (round 6, beside the CU-owning filter-gradient kernels of the side stream: 128 -> 19.74, 256 -> 19.49, 512 / 1024 -> 19.45,
-    //  2048 -> 19.55 ms per step)
-    const int blocks_knob = VT_KNOB("VT_BN_RED_BLOCKS", 1024);
-    const int target = blocks_knob / cgroups > 0 ? blocks_knob / cgroups : 1;
-    RowMap rm = RowMap::make(Cg, epc, M, target);
-    rm.rev = (vt_bn_order() >> 1) & 1;
-    const int smem = rowlane_fold_bytes(2, rm.CT, rm.RT, epc);
+    const BnReducePlan p = bn_reduce_plan(M, C, vt_epc(dtype));
     VT_REQUIRE(relu >= 0 && relu <= 6, VT_ERR_INVALID, "vt_bn_act_bwd_reduce: activation code %d", relu);
     if (relu >= 2) {
         VT_DISPATCH_T(dtype, "vt_bn_act_bwd_reduce",
-                      hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true>), dim3(rm.blocks(M), cgroups), dim3(kThreads), smem,
+                      hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true>), dim3(p.rm.blocks(M), p.cgroups), dim3(kThreads), p.smem,
                                          (hipStream_t)stream, (const T*)dy, lddy, (const T*)z, ldz, scale, shift, mean,
-                                         invstd, (long)M, Cg, rm, relu << 4, sums, C));
+                                         invstd, (long)M, p.Cg, p.rm, relu << 4, sums, C));
         VT_CHECK_LAUNCH("vt_bn_act_bwd_reduce");
         return VT_OK;
     }
     VT_DISPATCH_T(dtype, "vt_bn_act_bwd_reduce",
-                  hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, dim3(rm.blocks(M), cgroups), dim3(kThreads), smem,
+                  hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, dim3(p.rm.blocks(M), p.cgroups), dim3(kThreads), p.smem,
                                      (hipStream_t)stream, (const T*)dy, lddy, (const T*)z, ldz, scale, shift,
-                                     mean, invstd, (long)M, Cg, rm, relu ? 1 : 0, sums, C));
+                                     mean, invstd, (long)M, p.Cg, p.rm, relu ? 1 : 0, sums, C));
     VT_CHECK_LAUNCH("vt_bn_act_bwd_reduce");
     return VT_OK;
 }
@@ -1712,7 +1650,7 @@ int vt_bn_bwd_finalize(const float* sums, int32_t C, double count, double pscale
                        void* stream) {
     VT_REQUIRE(sums && scale && mean && invstd && coef && C > 0 && count > 0, VT_ERR_INVALID,
                "vt_bn_bwd_finalize: bad argument");
-    VtFinBwd f{sums, scale, mean, invstd, dgamma, dbeta, coef, 1.0 / count, pscale, C, train};
+    const VtFinBwd f = make_fin_bwd(sums, C, count, pscale, scale, mean, invstd, train, dgamma, dbeta, coef);
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, f);
     VT_CHECK_LAUNCH("vt_bn_bwd_finalize");
     return VT_OK;
@@ -1727,8 +1665,7 @@ int vt_bn_act_bwd_apply(const void* dy, int32_t lddy, const void* z, int32_t ldz
     VT_TRY(check_mat("vt_bn_act_bwd_apply(dy)", dy, lddy, C, dtype));
     VT_TRY(check_mat("vt_bn_act_bwd_apply(z)", z, ldz, C, dtype));
     VT_TRY(check_mat("vt_bn_act_bwd_apply(dz)", dz, lddz, C, dtype));
-    RowMap rm = RowMap::make(C, vt_epc(dtype), M);
-    rm.rev = (vt_bn_order() >> 2) & 1;
+    const RowMap rm = RowMap::make(C, vt_epc(dtype), M);
     VT_REQUIRE(relu >= 0 && relu <= 6, VT_ERR_INVALID, "vt_bn_act_bwd_apply: activation code %d", relu);
     const VtFinBwd f{};
     if (relu >= 2 || act_only) {

@@ -47,49 +47,41 @@ bn_keep_apply_kernel(const VtFinFwd f, const float* __restrict__ scale, const fl
     z += cg0, y += cg0, r += cg0;
     const int rl = t / rm.CT;
     if (rl >= rm.RT) return;
-    const long row0 = (long)blockIdx.x * rm.RT * rm.iters + rl;
+    const long row0 = rm.row0(rl);
     for (int col = t % rm.CT; col < rm.CPR; col += rm.CT) {
         float sc[EPC], sf[EPC];
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-            if constexpr (kFin) sc[e] = s_sc[col * EPC + e], sf[e] = s_sf[col * EPC + e];
-            else sc[e] = scale[col * EPC + e], sf[e] = shift[col * EPC + e];
-        }
+        chunk_coef(sc, kFin ? s_sc : scale, col);
+        chunk_coef(sf, kFin ? s_sf : shift, col);
         const T* pz = z + row0 * ldz + col * EPC;
         const T* pr = r + row0 * ldr + col * EPC;
         T* py = y + row0 * ldy + col * EPC;
         const long sz = (long)rm.RT * ldz, sr = (long)rm.RT * ldr, sy = (long)rm.RT * ldy;
-        for (int it = 0; it < rm.iters; it += kUnroll) {
-            uint4 vz[kUnroll], vr[kUnroll];
-            float kp[kUnroll];
-            bool ok[kUnroll];
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                const long row = row0 + (long)(it + u) * rm.RT;
-                ok[u] = (it + u < rm.iters) && row < M;
+        uint4 vz[kUnroll], vr[kUnroll];
+        float kp[kUnroll];
+        rowmap_trips(
+            rm, row0, M,
+            [&](int u, int i, bool ok) VT_TRIP_LAMBDA {
                 vz[u] = vr[u] = make_uint4(0, 0, 0, 0);
                 kp[u] = 0.f;
-                if (ok[u]) {
-                    kp[u] = keep[(unsigned)row / HW];
-                    vr[u] = ld16(pr + (it + u) * sr);
-                    if (kp[u] != 0.f) vz[u] = ld16(pz + (it + u) * sz);  // (a dropped image's z is never read)
+                if (ok) {
+                    kp[u] = keep[(unsigned)(row0 + (long)i * rm.RT) / HW];
+                    vr[u] = ld16(pr + i * sr);
+                    if (kp[u] != 0.f) vz[u] = ld16(pz + i * sz);  // (a dropped image's z is never read)
                 }
-            }
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                if (!ok[u]) continue;
+            },
+            [&](int u, int i, bool ok) VT_TRIP_LAMBDA {
+                if (!ok) return;
                 if (kp[u] == 0.f) {  // y = r, bit for bit
-                    st16(py + (it + u) * sy, vr[u]);
-                    continue;
+                    st16(py + i * sy, vr[u]);
+                    return;
                 }
                 float v[EPC], rr[EPC];
                 VecIO<T>::unpack(vz[u], v);
                 VecIO<T>::unpack(vr[u], rr);
 #pragma unroll
                 for (int e = 0; e < EPC; ++e) v[e] = fmaf(kp[u], act_fwd(act, fmaf(v[e], sc[e], sf[e])), rr[e]);
-                st16(py + (it + u) * sy, VecIO<T>::pack(v));
-            }
-        }
+                st16(py + i * sy, VecIO<T>::pack(v));
+            });
     }
 }
 
@@ -109,7 +101,7 @@ bn_keep_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restric
     const int t = threadIdx.x;
     const int r = t / rm.CT;
     const int tc = t % rm.CT;
-    const long row0 = (long)blockIdx.x * rm.RT * rm.iters + r;
+    const long row0 = rm.row0(r);
     const int rep = blockIdx.x % kStatReplicas;
     const int cg0 = blockIdx.y * rm.CPR;  // first 16-byte chunk of this channel group
     dy += (long)cg0 * EPC, z += (long)cg0 * EPC;
@@ -125,37 +117,32 @@ bn_keep_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restric
         for (int e = 0; e < EPC; ++e) s1[e] = s2[e] = 0.f;
         if (active) {
             float sc[EPC], sf[EPC], mu[EPC];
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) {
-                sc[e] = scale[col * EPC + e];
-                sf[e] = shift[col * EPC + e];
-                mu[e] = mean[col * EPC + e];
-            }
+            chunk_coef(sc, scale, col);
+            chunk_coef(sf, shift, col);
+            chunk_coef(mu, mean, col);
             const T* pg = dy + row0 * lddy + col * EPC;
             const T* pz = z + row0 * ldz + col * EPC;
             const long sg = (long)rm.RT * lddy, sz = (long)rm.RT * ldz;
-            for (int it = 0; it < rm.iters; it += kUnroll) {
-                uint4 vg[kUnroll], vz[kUnroll], va[kUnroll];
-                float kp[kUnroll];
-                bool on[kUnroll];
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u) {
-                    const long row = row0 + (long)(it + u) * rm.RT;
+            uint4 vg[kUnroll], vz[kUnroll], va[kUnroll];
+            float kp[kUnroll];
+            bool on[kUnroll];
+            rowmap_trips(
+                rm, row0, M,
+                [&](int u, int i, bool ok) VT_TRIP_LAMBDA {
                     vg[u] = vz[u] = va[u] = make_uint4(0, 0, 0, 0);
                     kp[u] = 0.f;
                     on[u] = false;
-                    if ((it + u < rm.iters) && row < M) {
-                        const unsigned b = (unsigned)row / HW;
+                    if (ok) {
+                        const unsigned b = (unsigned)(row0 + (long)i * rm.RT) / HW;
                         kp[u] = keep ? keep[b] : 1.f;
                         if constexpr (kAdd) va[u] = ld16(add + (long)b * lda + col * EPC);
                         on[u] = kAdd || kp[u] != 0.f;
-                        if (kp[u] != 0.f) vg[u] = ld16(pg + (it + u) * sg);
-                        if (on[u]) vz[u] = ld16(pz + (it + u) * sz);  // (a dropped image without an addend: neither is read)
+                        if (kp[u] != 0.f) vg[u] = ld16(pg + i * sg);
+                        if (on[u]) vz[u] = ld16(pz + i * sz);  // (a dropped image without an addend: neither is read)
                     }
-                }
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u) {
-                    if (!on[u]) continue;
+                },
+                [&](int u, int, bool) VT_TRIP_LAMBDA {
+                    if (!on[u]) return;
                     float g[EPC], zz[EPC], aa[EPC];
                     VecIO<T>::unpack(vg[u], g);
                     VecIO<T>::unpack(vz[u], zz);
@@ -168,14 +155,10 @@ bn_keep_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __restric
                         s1[e] += gg;
                         s2[e] = fmaf(gg, zz[e] - mu[e], s2[e]);  // invstd applied once, below
                     }
-                }
-            }
+                });
         }
         rowlane_fold(sred, s, rm.CT, rm.RT, [&](int which, int lc, float acc) {
-            const int c = cbase * EPC + lc;
-            if (c >= C) return;
-            if (which) acc *= invstd[c];
-            vt_stat_add(sums, ((long)rep * 2 + which) * Ctot + cg0 * EPC + c, acc);
+            bn_sums_emit(sums, rep, Ctot, cg0 * EPC, invstd, C, which, cbase * EPC + lc, acc);
         });
     }
 }
@@ -202,38 +185,32 @@ bn_keep_bwd_apply_kernel(const VtFinBwd f, const float* __restrict__ coef, const
     const float ascale = 1.f / (float)HW;
     const int r = t / rm.CT;
     if (r >= rm.RT) return;
-    const long row0 = (long)blockIdx.x * rm.RT * rm.iters + r;
+    const long row0 = rm.row0(r);
     for (int col = t % rm.CT; col < rm.CPR; col += rm.CT) {
         float ca[EPC], cb[EPC], cd[EPC], sf[EPC];
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-            const int c = col * EPC + e;
-            if constexpr (kFin) ca[e] = s_a[c], cb[e] = s_b[c], cd[e] = s_d[c];
-            else ca[e] = coef[c], cb[e] = coef[C + c], cd[e] = coef[2 * C + c];
-            sf[e] = shift[c];
-        }
-        for (int it = 0; it < rm.iters; it += kUnroll) {
-            uint4 vg[kUnroll], vz[kUnroll], va[kUnroll];
-            float kp[kUnroll];
-            bool ok[kUnroll];
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                const long row = row0 + (long)(it + u) * rm.RT;
-                ok[u] = (it + u < rm.iters) && row < M;
+        chunk_coef(ca, kFin ? s_a : coef, col);
+        chunk_coef(cb, kFin ? s_b : coef + C, col);
+        chunk_coef(cd, kFin ? s_d : coef + 2 * C, col);
+        chunk_coef(sf, shift, col);
+        uint4 vg[kUnroll], vz[kUnroll], va[kUnroll];
+        float kp[kUnroll];
+        rowmap_trips(
+            rm, row0, M,
+            [&](int u, int i, bool ok) VT_TRIP_LAMBDA {
+                const long row = row0 + (long)i * rm.RT;
                 vg[u] = vz[u] = va[u] = make_uint4(0, 0, 0, 0);
                 kp[u] = 0.f;
-                if (ok[u]) {
+                if (ok) {
                     const unsigned b = (unsigned)row / HW;
                     kp[u] = keep ? keep[b] : 1.f;
                     if constexpr (kAdd) va[u] = ld16(add + (long)b * lda + col * EPC);
                     vz[u] = ld16(z + row * ldz + col * EPC);
                     if (kp[u] != 0.f) vg[u] = ld16(dy + row * lddy + col * EPC);
                 }
-            }
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                if (!ok[u]) continue;
-                const long row = row0 + (long)(it + u) * rm.RT;
+            },
+            [&](int u, int i, bool ok) VT_TRIP_LAMBDA {
+                if (!ok) return;
+                const long row = row0 + (long)i * rm.RT;
                 float g[EPC], zz[EPC], aa[EPC], o[EPC];
                 VecIO<T>::unpack(vg[u], g);
                 VecIO<T>::unpack(vz[u], zz);
@@ -250,8 +227,7 @@ bn_keep_bwd_apply_kernel(const VtFinBwd f, const float* __restrict__ coef, const
                     o[e] = fmaf(ca[e], gg, fmaf(-cb[e], zz[e], cd[e]));
                 }
                 st16(dz + row * lddz + col * EPC, VecIO<T>::pack(o));
-            }
-        }
+            });
     }
 }
 
@@ -341,22 +317,10 @@ pool_finish_kernel(const float* __restrict__ scratch, T* __restrict__ pooled, in
     pooled[(i / C) * ldp + i % C] = from_float<T>((float)v * inv);
 }
 
-// the grid of a pass: as vt_bn_finalize_apply cuts it (VT_BN_FIN_APPLY_WGS workgroups over the channel groups)
-inline RowMap fin_rowmap(int Cg, int groups, int epc, long M) {
-    const int wgs = VT_KNOB("VT_BN_FIN_APPLY_WGS", 1536);
-    return RowMap::make(Cg, epc, M, wgs / groups > 0 ? wgs / groups : 1);
-}
-
-inline int check_keep(const char* who, const float* keep, int HW, long M) {
-    VT_REQUIRE(keep && HW > 0 && M > 0 && M % HW == 0 && M <= 0x7fffffffL, VT_ERR_INVALID,
-               "%s: keep is a float[M / HW] row, M=%ld a multiple of HW=%d below 2^31", who, M, HW);
-    return VT_OK;
-}
-
 // backward: keep may be NULL (factor 1) where the addend row [M / HW][C] is given
 inline int check_keep_add(const char* who, const float* keep, const void* add, int lda, int HW, long M, int C, int dtype) {
-    VT_REQUIRE((keep || add) && HW > 0 && M > 0 && M % HW == 0 && M <= 0x7fffffffL, VT_ERR_INVALID,
-               "%s: a keep row float[M / HW] or an addend [M / HW][C] (or both), M=%ld a multiple of HW=%d below 2^31", who, M, HW);
+    VT_REQUIRE(keep || add, VT_ERR_INVALID, "%s: a keep row float[M / HW] or an addend [M / HW][C] (or both)", who);
+    VT_TRY(check_image_rows(who, HW, M));
     if (add) VT_TRY(check_mat(who, add, lda, C, dtype));
     return VT_OK;
 }
@@ -446,15 +410,15 @@ int vt_bn_keep_finalize_apply(const float* stats, int32_t C, double count, const
     VT_TRY(check_mat("vt_bn_keep_finalize_apply(r)", r, ldr, C, dtype));
     VT_TRY(check_mat("vt_bn_keep_finalize_apply(y)", y, ldy, C, dtype));
     const int Cg = fin_group(C, vt_epc(dtype));
-    if (!Cg || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {  // (no channel group: the two launches)
+    if (!fin_in_launch(Cg)) {
         VT_TRY(vt_bn_finalize(stats, C, count, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, scale,
                               shift, mean, invstd, stream));
         return vt_bn_keep_apply(z, ldz, scale, shift, r, ldr, y, ldy, keep, HW, M, C, act, dtype, stream);
     }
     const int groups = C / Cg;
     const RowMap rm = fin_rowmap(Cg, groups, vt_epc(dtype), M);
-    const VtFinFwd f{stats, gamma, beta, running_mean, running_var, num_batches_tracked, scale, shift, mean, invstd,
-                     1.0 / count, count > 1.0 ? count / (count - 1.0) : 1.0, eps, momentum, C};
+    const VtFinFwd f = make_fin_fwd(stats, C, count, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, scale,
+                                    shift, mean, invstd);
     VT_DISPATCH_T(dtype, "vt_bn_keep_finalize_apply",
                   hipLaunchKernelGGL((bn_keep_apply_kernel<T, true>), dim3(rm.blocks(M), groups), dim3(kThreads), 0,
                                      (hipStream_t)stream, f, (const float*)nullptr, (const float*)nullptr, (const T*)z, ldz,
@@ -471,19 +435,12 @@ int vt_bn_keep_bwd_reduce(const void* dy, int32_t lddy, const void* z, int32_t l
     VT_TRY(check_keep_add("vt_bn_keep_bwd_reduce", keep, add, lda, HW, (long)M, C, dtype));
     VT_TRY(check_mat("vt_bn_keep_bwd_reduce(dy)", dy, lddy, C, dtype));
     VT_TRY(check_mat("vt_bn_keep_bwd_reduce(z)", z, ldz, C, dtype));
-    const int epc = vt_epc(dtype);
-    // the grid of vt_bn_act_bwd_reduce: few, long blocks (each ends with 2*C 64-bit atomics), channel groups of 64 on the
-    // small maps with many channels
-    const int cgroups = (M <= 65536 && C >= 256 && C % 64 == 0) ? C / 64 : 1;
-    const int Cg = C / cgroups;
-    const int blocks_knob = VT_KNOB("VT_BN_RED_BLOCKS", 1024);
-    const RowMap rm = RowMap::make(Cg, epc, M, blocks_knob / cgroups > 0 ? blocks_knob / cgroups : 1);
-    const int smem = rowlane_fold_bytes(2, rm.CT, rm.RT, epc);
-#define VT_KEEP_RED(ADD)                                                                                                       \
-    VT_DISPATCH_T(dtype, "vt_bn_keep_bwd_reduce",                                                                               \
-                  hipLaunchKernelGGL((bn_keep_bwd_reduce_kernel<T, ADD>), dim3(rm.blocks(M), cgroups), dim3(kThreads), smem,     \
-                                     (hipStream_t)stream, (const T*)dy, lddy, (const T*)z, ldz, scale, shift, mean, invstd, keep, \
-                                     (const T*)add, lda, (unsigned)HW, (long)M, Cg, rm, act, sums, C))
+    const BnReducePlan p = bn_reduce_plan(M, C, vt_epc(dtype));
+#define VT_KEEP_RED(ADD)                                                                                                          \
+    VT_DISPATCH_T(dtype, "vt_bn_keep_bwd_reduce",                                                                                  \
+                  hipLaunchKernelGGL((bn_keep_bwd_reduce_kernel<T, ADD>), dim3(p.rm.blocks(M), p.cgroups), dim3(kThreads), p.smem,  \
+                                     (hipStream_t)stream, (const T*)dy, lddy, (const T*)z, ldz, scale, shift, mean, invstd, keep,  \
+                                     (const T*)add, lda, (unsigned)HW, (long)M, p.Cg, p.rm, act, sums, C))
     if (add) VT_KEEP_RED(true);
     else VT_KEEP_RED(false);
 #undef VT_KEEP_RED
@@ -525,13 +482,13 @@ int vt_bn_keep_bwd_finalize_apply(const float* sums, int32_t C, double count, do
     VT_TRY(check_mat("vt_bn_keep_bwd_finalize_apply(z)", z, ldz, C, dtype));
     VT_TRY(check_mat("vt_bn_keep_bwd_finalize_apply(dz)", dz, lddz, C, dtype));
     const int Cg = fin_group(C, vt_epc(dtype));
-    if (!Cg || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {  // (no channel group: the two launches)
+    if (!fin_in_launch(Cg)) {
         VT_TRY(vt_bn_bwd_finalize(sums, C, count, pscale, scale, mean, invstd, train, dgamma, dbeta, coef, stream));
         return vt_bn_keep_bwd_apply(dy, lddy, z, ldz, shift, coef, keep, add, lda, HW, dz, lddz, M, C, act, dtype, stream);
     }
     const int groups = C / Cg;
     const RowMap rm = fin_rowmap(Cg, groups, vt_epc(dtype), M);
-    const VtFinBwd f{sums, scale, mean, invstd, dgamma, dbeta, coef, 1.0 / count, pscale, C, train};
+    const VtFinBwd f = make_fin_bwd(sums, C, count, pscale, scale, mean, invstd, train, dgamma, dbeta, coef);
 #define VT_KEEP_FIN_APPLY(ADD)                                                                                                        \
     VT_DISPATCH_T(dtype, "vt_bn_keep_bwd_finalize_apply",                                                                             \
                   hipLaunchKernelGGL((bn_keep_bwd_apply_kernel<T, true, ADD>), dim3(rm.blocks(M), groups), dim3(kThreads), 0,           \
@@ -569,13 +526,13 @@ int vt_bn_act_avgpool_finalize_apply(const float* stats, int32_t C, double count
     VT_REQUIRE((running_mean == nullptr) == (running_var == nullptr), VT_ERR_INVALID,
                "vt_bn_act_avgpool_finalize_apply: running_mean/var must both be given or both NULL");
     VT_TRY(check_pool("vt_bn_act_avgpool_finalize_apply", z, ldz, y, ldy, pooled, ldp, B, HW, C, act, dtype));
-    if (!fin_group(C, vt_epc(dtype)) || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {  // (no channel group: the two launches)
+    if (!fin_in_launch(fin_group(C, vt_epc(dtype)))) {
         VT_TRY(vt_bn_finalize(stats, C, count, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, scale,
                               shift, mean, invstd, stream));
         return vt_bn_act_avgpool_apply(z, ldz, scale, shift, y, ldy, pooled, ldp, scratch, B, HW, C, act, dtype, stream);
     }
-    const VtFinFwd f{stats, gamma, beta, running_mean, running_var, num_batches_tracked, scale, shift, mean, invstd,
-                     1.0 / count, count > 1.0 ? count / (count - 1.0) : 1.0, eps, momentum, C};
+    const VtFinFwd f = make_fin_fwd(stats, C, count, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, scale,
+                                    shift, mean, invstd);
     return launch_pool<true>("vt_bn_act_avgpool_finalize_apply", f, nullptr, nullptr, z, ldz, y, ldy, pooled, ldp, scratch, B, HW, C,
                              act, dtype, (hipStream_t)stream);
 }

@@ -48,40 +48,33 @@ bn_add_act_kernel(const VtFinFwd f, const float* __restrict__ scale, const float
     z += cg0, y += cg0, r += cg0;
     const int rl = t / rm.CT;
     if (rl >= rm.RT) return;
-    const long row0 = (long)blockIdx.x * rm.RT * rm.iters + rl;
+    const long row0 = rm.row0(rl);
     for (int col = t % rm.CT; col < rm.CPR; col += rm.CT) {
         float sc[EPC], sf[EPC];
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-            if constexpr (kFin) sc[e] = s_sc[col * EPC + e], sf[e] = s_sf[col * EPC + e];
-            else sc[e] = scale[col * EPC + e], sf[e] = shift[col * EPC + e];
-        }
+        chunk_coef(sc, kFin ? s_sc : scale, col);
+        chunk_coef(sf, kFin ? s_sf : shift, col);
         const T* pz = z + row0 * ldz + col * EPC;
         const T* pr = r + row0 * ldr + col * EPC;
         T* py = y + row0 * ldy + col * EPC;
         const long sz = (long)rm.RT * ldz, sr = (long)rm.RT * ldr, sy = (long)rm.RT * ldy;
-        // kUnroll rows per trip: all loads are issued before the first use (bytes in flight)
-        for (int it = 0; it < rm.iters; it += kUnroll) {
-            uint4 vz[kUnroll], vr[kUnroll];
-            bool ok[kUnroll];
-            float kf[kUnroll];
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                ok[u] = (it + u < rm.iters) && (row0 + (long)(it + u) * rm.RT < M);
+        uint4 vz[kUnroll], vr[kUnroll];
+        float kf[kUnroll];
+        rowmap_trips(
+            rm, row0, M,
+            [&](int u, int i, bool ok) VT_TRIP_LAMBDA {
                 vz[u] = vr[u] = make_uint4(0, 0, 0, 0);
                 kf[u] = 0.f;
-                if (ok[u]) {
+                if (ok) {
                     if constexpr (kKeep) {
-                        kf[u] = keep[(unsigned)(row0 + (long)(it + u) * rm.RT) / (unsigned)HW];  // (M < 2^31 rows: check_keep)
-                        if (kf[u] != 0.f) vz[u] = ld16(pz + (it + u) * sz);
+                        kf[u] = keep[(unsigned)(row0 + (long)i * rm.RT) / (unsigned)HW];  // (M < 2^31 rows: check_keep)
+                        if (kf[u] != 0.f) vz[u] = ld16(pz + i * sz);
                     } else {
-                        vz[u] = ld16(pz + (it + u) * sz);
+                        vz[u] = ld16(pz + i * sz);
                     }
-                    vr[u] = ld16(pr + (it + u) * sr);
+                    vr[u] = ld16(pr + i * sr);
                 }
-            }
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
+            },
+            [&](int u, int i, bool ok) VT_TRIP_LAMBDA {
                 float v[EPC], rr[EPC];
                 VecIO<T>::unpack(vz[u], v);
                 VecIO<T>::unpack(vr[u], rr);
@@ -92,9 +85,8 @@ bn_add_act_kernel(const VtFinFwd f, const float* __restrict__ scale, const float
                     else
                         v[e] = fmaxf(fmaf(v[e], sc[e], sf[e]) + rr[e], 0.f);
                 }
-                if (ok[u]) st16(py + (it + u) * sy, VecIO<T>::pack(v));
-            }
-        }
+                if (ok) st16(py + i * sy, VecIO<T>::pack(v));
+            });
     }
 }
 
@@ -112,7 +104,7 @@ bn_add_act_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __rest
     const int t = threadIdx.x;
     const int r = t / rm.CT;
     const int tc = t % rm.CT;
-    const long row0 = (long)blockIdx.x * rm.RT * rm.iters + r;
+    const long row0 = rm.row0(r);
     const int rep = blockIdx.x % kStatReplicas;
     const int cg0 = blockIdx.y * rm.CPR;  // first 16-byte chunk of this channel group (C channels each of Ctot)
     dy += (long)cg0 * EPC, y += (long)cg0 * EPC, z += (long)cg0 * EPC;
@@ -126,32 +118,29 @@ bn_add_act_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __rest
         for (int e = 0; e < EPC; ++e) s1[e] = s2[e] = 0.f;
         if (active) {
             float mu[EPC];
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) mu[e] = mean[col * EPC + e];
+            chunk_coef(mu, mean, col);
             const T* pg = dy + row0 * lddy + col * EPC;
             const T* py = y + row0 * ldy + col * EPC;
             const T* pz = z + row0 * ldz + col * EPC;
             const long sg = (long)rm.RT * lddy, sy = (long)rm.RT * ldy, sz = (long)rm.RT * ldz;
-            for (int it = 0; it < rm.iters; it += kUnroll) {
-                uint4 vg[kUnroll], vy[kUnroll], vz[kUnroll];
-                float kf[kUnroll];
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u) {
-                    const long row = row0 + (long)(it + u) * rm.RT;
+            uint4 vg[kUnroll], vy[kUnroll], vz[kUnroll];
+            float kf[kUnroll];
+            rowmap_trips(
+                rm, row0, M,
+                [&](int u, int i, bool ok) VT_TRIP_LAMBDA {
                     vg[u] = vy[u] = vz[u] = make_uint4(0, 0, 0, 0);  // y = 0 masks the row out
                     kf[u] = 0.f;
-                    if ((it + u < rm.iters) && row < M) {
+                    if (ok) {
                         if constexpr (kKeep) {
-                            kf[u] = keep[(unsigned)row / (unsigned)HW];
-                            if (kf[u] == 0.f) continue;  // (y stays 0: the row contributes nothing)
+                            kf[u] = keep[(unsigned)(row0 + (long)i * rm.RT) / (unsigned)HW];
+                            if (kf[u] == 0.f) return;  // (y stays 0: the row contributes nothing)
                         }
-                        vg[u] = ld16(pg + (it + u) * sg);
-                        vy[u] = ld16(py + (it + u) * sy);
-                        vz[u] = ld16(pz + (it + u) * sz);
+                        vg[u] = ld16(pg + i * sg);
+                        vy[u] = ld16(py + i * sy);
+                        vz[u] = ld16(pz + i * sz);
                     }
-                }
-#pragma unroll
-                for (int u = 0; u < kUnroll; ++u) {
+                },
+                [&](int u, int, bool) VT_TRIP_LAMBDA {
                     float g[EPC], yy[EPC], zz[EPC];
                     VecIO<T>::unpack(vg[u], g);
                     VecIO<T>::unpack(vy[u], yy);
@@ -163,14 +152,10 @@ bn_add_act_bwd_reduce_kernel(const T* __restrict__ dy, int lddy, const T* __rest
                         s1[e] += gg;
                         s2[e] = fmaf(gg, zz[e] - mu[e], s2[e]);  // invstd applied once, below
                     }
-                }
-            }
+                });
         }
         rowlane_fold(sred, s, rm.CT, rm.RT, [&](int which, int lc, float acc) {
-            const int c = cbase * EPC + lc;
-            if (c >= C) return;
-            if (which) acc *= invstd[c];
-            vt_stat_add(sums, ((long)rep * 2 + which) * Ctot + cg0 * EPC + c, acc);
+            bn_sums_emit(sums, rep, Ctot, cg0 * EPC, invstd, C, which, cbase * EPC + lc, acc);
         });
     }
 }
@@ -197,34 +182,28 @@ bn_add_act_bwd_apply_kernel(const VtFinBwd f, const float* __restrict__ coef, co
     dy += cg0, y += cg0, z += cg0, dz += cg0, dr += cg0;
     const int r = t / rm.CT;
     if (r >= rm.RT) return;
-    const long row0 = (long)blockIdx.x * rm.RT * rm.iters + r;
+    const long row0 = rm.row0(r);
     for (int col = t % rm.CT; col < rm.CPR; col += rm.CT) {
         float ca[EPC], cb[EPC], cd[EPC];
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-            const int c = col * EPC + e;
-            if constexpr (kFin) ca[e] = s_a[c], cb[e] = s_b[c], cd[e] = s_d[c];
-            else ca[e] = coef[c], cb[e] = coef[C + c], cd[e] = coef[2 * C + c];
-        }
-        for (int it = 0; it < rm.iters; it += kUnroll) {
-            uint4 vg[kUnroll], vy[kUnroll], vz[kUnroll], va[kUnroll];
-            bool ok[kUnroll];
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                const long row = row0 + (long)(it + u) * rm.RT;
-                ok[u] = (it + u < rm.iters) && row < M;
+        chunk_coef(ca, kFin ? s_a : coef, col);
+        chunk_coef(cb, kFin ? s_b : coef + C, col);
+        chunk_coef(cd, kFin ? s_d : coef + 2 * C, col);
+        uint4 vg[kUnroll], vy[kUnroll], vz[kUnroll], va[kUnroll];
+        rowmap_trips(
+            rm, row0, M,
+            [&](int u, int i, bool ok) VT_TRIP_LAMBDA {
+                const long row = row0 + (long)i * rm.RT;
                 vg[u] = vy[u] = vz[u] = va[u] = make_uint4(0, 0, 0, 0);
-                if (ok[u]) {
+                if (ok) {
                     vg[u] = ld16(dy + row * lddy + col * EPC);
                     vy[u] = ld16(y + row * ldy + col * EPC);
                     vz[u] = ld16(z + row * ldz + col * EPC);
                     if (acc) va[u] = ld16(dr + row * lddr + col * EPC);
                 }
-            }
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                if (!ok[u]) continue;
-                const long row = row0 + (long)(it + u) * rm.RT;
+            },
+            [&](int u, int i, bool ok) VT_TRIP_LAMBDA {
+                if (!ok) return;
+                const long row = row0 + (long)i * rm.RT;
                 float g[EPC], yy[EPC], zz[EPC], aa[EPC], o[EPC];
                 VecIO<T>::unpack(vg[u], g);
                 VecIO<T>::unpack(vy[u], yy);
@@ -241,8 +220,7 @@ bn_add_act_bwd_apply_kernel(const VtFinBwd f, const float* __restrict__ coef, co
                 }
                 st16(dz + row * lddz + col * EPC, VecIO<T>::pack(o));
                 st16(dr + row * lddr + col * EPC, VecIO<T>::pack(aa));
-            }
-        }
+            });
     }
 }
 
@@ -310,12 +288,6 @@ stem7_unpack_wgrad_kernel(const float* __restrict__ dws, int Cs, float* __restri
     dw[i] += dws[(o * 16 + a * 4 + b) * Cs + py * 6 + px * 3 + c];
 }
 
-// the grid of a pass: as vt_bn_finalize_apply cuts it (VT_BN_FIN_APPLY_WGS workgroups over the channel groups)
-inline RowMap fin_rowmap(int Cg, int groups, int epc, long M) {
-    const int wgs = VT_KNOB("VT_BN_FIN_APPLY_WGS", 1536);
-    return RowMap::make(Cg, epc, M, wgs / groups > 0 ? wgs / groups : 1);
-}
-
 // ---------------------------------------------------------------------------------
 // the five add-then-ReLU passes, plain (keep == nullptr: the kKeep = false instances) or with per-image keep factors
 // ---------------------------------------------------------------------------------
@@ -325,12 +297,6 @@ inline RowMap fin_rowmap(int Cg, int groups, int epc, long M) {
         snprintf(nm__, sizeof nm__, "%s(%s)", who, what);   \
         VT_TRY(check_mat(nm__, p, ld, C, dtype));           \
     } while (0)
-
-int check_keep(const char* who, const float* keep, int HW, long M) {
-    VT_REQUIRE(keep && HW > 0 && M % HW == 0 && M < (1L << 31), VT_ERR_INVALID,
-               "%s: keep is a float[M / HW] row: HW=%d must divide M=%ld, M below 2^31", who, HW, M);
-    return VT_OK;
-}
 
 int add_act_apply(const char* who, const void* z, int ldz, const float* scale, const float* shift, const void* r, int ldr, void* y,
                   int ldy, const float* keep, int HW, long M, int C, int dtype, void* stream) {
@@ -364,15 +330,15 @@ int add_act_finalize_apply(const char* who, const float* stats, int C, double co
     ADD_ACT_MAT("r", r, ldr);
     ADD_ACT_MAT("y", y, ldy);
     const int Cg = fin_group(C, vt_epc(dtype));
-    if (!Cg || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {  // (no channel group: the two launches)
+    if (!fin_in_launch(Cg)) {
         VT_TRY(vt_bn_finalize(stats, C, count, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, scale,
                               shift, mean, invstd, stream));
         return add_act_apply(who, z, ldz, scale, shift, r, ldr, y, ldy, keep, HW, M, C, dtype, stream);
     }
     const int groups = C / Cg;
     const RowMap rm = fin_rowmap(Cg, groups, vt_epc(dtype), M);
-    const VtFinFwd f{stats, gamma, beta, running_mean, running_var, num_batches_tracked, scale, shift, mean, invstd,
-                     1.0 / count, count > 1.0 ? count / (count - 1.0) : 1.0, eps, momentum, C};
+    const VtFinFwd f = make_fin_fwd(stats, C, count, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, scale,
+                                    shift, mean, invstd);
     if (keep)
         VT_DISPATCH_T(dtype, who,
                       hipLaunchKernelGGL((bn_add_act_kernel<T, true, true>), dim3(rm.blocks(M), groups), dim3(kThreads), 0,
@@ -393,24 +359,17 @@ int add_act_bwd_reduce(const char* who, const void* dy, int lddy, const void* y,
     ADD_ACT_MAT("dy", dy, lddy);
     ADD_ACT_MAT("y", y, ldy);
     ADD_ACT_MAT("z", z, ldz);
-    const int epc = vt_epc(dtype);
-    // the grid of vt_bn_act_bwd_reduce: few, long blocks (each ends with 2*C 64-bit atomics), channel groups of 64 on the
-    // small maps with many channels
-    const int cgroups = (M <= 65536 && C >= 256 && C % 64 == 0) ? C / 64 : 1;
-    const int Cg = C / cgroups;
-    const int blocks_knob = VT_KNOB("VT_BN_RED_BLOCKS", 1024);
-    const RowMap rm = RowMap::make(Cg, epc, M, blocks_knob / cgroups > 0 ? blocks_knob / cgroups : 1);
+    const BnReducePlan p = bn_reduce_plan(M, C, vt_epc(dtype));
     if (keep)
         VT_DISPATCH_T(dtype, who,
-                      hipLaunchKernelGGL((bn_add_act_bwd_reduce_kernel<T, true>), dim3(rm.blocks(M), cgroups), dim3(kThreads),
-                                         rowlane_fold_bytes(2, rm.CT, rm.RT, epc), (hipStream_t)stream, (const T*)dy, lddy,
-                                         (const T*)y, ldy, (const T*)z, ldz, mean, invstd, M, Cg, rm, sums, C, keep, HW));
+                      hipLaunchKernelGGL((bn_add_act_bwd_reduce_kernel<T, true>), dim3(p.rm.blocks(M), p.cgroups), dim3(kThreads), p.smem,
+                                         (hipStream_t)stream, (const T*)dy, lddy, (const T*)y, ldy, (const T*)z, ldz, mean, invstd, M,
+                                         p.Cg, p.rm, sums, C, keep, HW));
     else
         VT_DISPATCH_T(dtype, who,
-                      hipLaunchKernelGGL(bn_add_act_bwd_reduce_kernel<T>, dim3(rm.blocks(M), cgroups), dim3(kThreads),
-                                         rowlane_fold_bytes(2, rm.CT, rm.RT, epc),
-                                         (hipStream_t)stream, (const T*)dy, lddy, (const T*)y, ldy, (const T*)z, ldz, mean, invstd,
-                                         M, Cg, rm, sums, C));
+                      hipLaunchKernelGGL(bn_add_act_bwd_reduce_kernel<T>, dim3(p.rm.blocks(M), p.cgroups), dim3(kThreads), p.smem,
+                                         (hipStream_t)stream, (const T*)dy, lddy, (const T*)y, ldy, (const T*)z, ldz, mean, invstd, M,
+                                         p.Cg, p.rm, sums, C));
     VT_CHECK_LAUNCH(who);
     return VT_OK;
 }
@@ -453,13 +412,13 @@ int add_act_bwd_finalize_apply(const char* who, const float* sums, int C, double
     ADD_ACT_MAT("dr", dr, lddr);
     VT_REQUIRE(dz != dr, VT_ERR_INVALID, "%s: dz and dr are two outputs", who);
     const int Cg = fin_group(C, vt_epc(dtype));
-    if (!Cg || !VT_KNOB("VT_BN_FIN_APPLY", 1)) {  // (no channel group: the two launches)
+    if (!fin_in_launch(Cg)) {
         VT_TRY(vt_bn_bwd_finalize(sums, C, count, pscale, scale, mean, invstd, train, dgamma, dbeta, coef, stream));
         return add_act_bwd_apply(who, dy, lddy, y, ldy, z, ldz, coef, dz, lddz, dr, lddr, accumulate, keep, HW, M, C, dtype, stream);
     }
     const int groups = C / Cg;
     const RowMap rm = fin_rowmap(Cg, groups, vt_epc(dtype), M);
-    const VtFinBwd f{sums, scale, mean, invstd, dgamma, dbeta, coef, 1.0 / count, pscale, C, train};
+    const VtFinBwd f = make_fin_bwd(sums, C, count, pscale, scale, mean, invstd, train, dgamma, dbeta, coef);
     if (keep)
         VT_DISPATCH_T(dtype, who,
                       hipLaunchKernelGGL((bn_add_act_bwd_apply_kernel<T, true, true>), dim3(rm.blocks(M), groups), dim3(kThreads), 0,
