@@ -1265,6 +1265,49 @@ int vt_lamb_apply(float* p, const float* m, const float* v, void* mirror, int32_
                   int32_t n_segs, int64_t n_items, int64_t n_total, const double* partials, float eps, int32_t flags,
                   const float* hyper, void* stream);
 
+/* ---- exponential moving average of the weights ------------------------------------------------------------------------
+ * The shadow copy e of a flat f32 buffer p that torch.optim.swa_utils.AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(d),
+ * use_buffers=True) (torchvision's ExponentialMovingAverage) and timm.utils.ModelEmaV2 keep.  Neither package is a
+ * dependency; the statement below is the definition for this library.
+ *
+ * Optimiser steps are numbered s = 0, 1, 2, ..; updates of the average are numbered u = 0, 1, 2, ..  With the period k
+ * (torchvision's --model-ema-steps; 1 = every step) step s updates the average iff s % k == 0, as the reference loop's
+ * `if i % model_ema_steps == 0` does.  Update 0 is a copy, every later one a blend:
+ *     u == 0:  e <- p
+ *     u >= 1:  e <- e + alpha * (p - e)          one subtraction, one fused multiply-add, both in f32
+ * alpha = 1 - decay is formed in DOUBLE on the host and handed over as an f32; the decay itself never exists as an f32
+ * (for decay = 0.99998, rounding the decay to f32 first moves alpha by 3e-3 of its value).  On a step that does not
+ * update, e keeps its bits.  Floating-point buffers (parameters, BatchNorm running statistics) are averaged; integer
+ * buffers (num_batches_tracked) are copied on the steps that update.
+ *
+ * ctl is a device buffer of 8 four-byte words, 16-byte aligned:
+ *     ctl[VT_EMA_ALPHA]   float  alpha                                  (in)
+ *     ctl[VT_EMA_MODE]    int32  VT_EMA_SKIP / _COPY / _BLEND           (out of vt_ema_tick, in of the others)
+ *     ctl[VT_EMA_COUNT]   int32  updates made so far, u                 (in / out of vt_ema_tick)
+ *     ctl[VT_EMA_PERIOD]  int32  k; a value < 1 counts as 1             (in)
+ *     ctl[VT_EMA_STEP]    int32  optimiser steps seen so far, s         (in / out of vt_ema_tick)
+ * vt_ema_tick:   one thread.  Leaves this step's mode, then advances s (and u where the step updates).  It runs ONCE per
+ *   optimiser step in front of that step's vt_ema_update / vt_ema_copy launches, which only read the mode and alpha: the
+ *   launch list is the same on every step, and a replayed hipGraph counts by itself.
+ * vt_ema_update: one streaming pass, 16-byte accesses, any n > 0.  Reads e and p, writes e, and where ema_mirror is given
+ *   the bf16 (round-to-nearest-even) cast of the NEW e in the same pass: 14 bytes per element (12 without a mirror; a copy
+ *   does not read e).  In skip mode every workgroup returns behind its read of ctl: neither e nor p is touched.
+ * vt_ema_copy:   dst <- src for `bytes` (a multiple of 16) unless the mode is skip.
+ * vt_ema_grid_cap: the element count above which every workgroup of vt_ema_update takes more than one round.
+ * VT_ERR_INVALID: a null or misaligned ema / p / dst / src / ctl (16 bytes; the mirror: 8), ema == p, n or bytes <= 0. */
+#define VT_EMA_ALPHA 0
+#define VT_EMA_MODE 1
+#define VT_EMA_COUNT 2
+#define VT_EMA_PERIOD 3
+#define VT_EMA_STEP 4
+#define VT_EMA_SKIP 0
+#define VT_EMA_COPY 1
+#define VT_EMA_BLEND 2
+int64_t vt_ema_grid_cap(void);
+int vt_ema_tick(float* ctl, void* stream);
+int vt_ema_update(float* ema, const float* p, void* ema_mirror, int64_t n, const float* ctl, void* stream);
+int vt_ema_copy(void* dst, const void* src, int64_t bytes, const float* ctl, void* stream);
+
 /* ---- layout / precision plumbing ---------------------------------------- */
 /* rows x cols block copy with dtype conversion: dst (=|+=) src */
 int vt_copy2d(const void* src, int32_t src_dtype, int64_t lds, void* dst, int32_t dst_dtype,
@@ -1416,6 +1459,9 @@ enum vt_op_kind {
     VT_OP_BN_ADD_ACT_KEEP_BWD_REDUCE,    /* vt_bn_add_act_keep_bwd_reduce */
     VT_OP_BN_ADD_ACT_KEEP_BWD_APPLY,     /* vt_bn_add_act_keep_bwd_apply */
     VT_OP_BN_ADD_ACT_KEEP_BWD_FIN_APPLY, /* vt_bn_add_act_keep_bwd_finalize_apply */
+    VT_OP_EMA_TICK,                 /* vt_ema_tick (the EMA step mode, once per optimiser step) */
+    VT_OP_EMA_UPDATE,               /* vt_ema_update */
+    VT_OP_EMA_COPY,                 /* vt_ema_copy */
     VT_OP_KIND_END
 };
 

@@ -521,6 +521,12 @@ int run_one(const vt_op& op, void* const* bases, int nbases, void* st) {
         case VT_OP_LAMB_APPLY:  // ptr: p m v mirror table partials hyper | i: mirror_dtype n_segs flags | f: n_items n_total eps
             return vt_lamb_apply((float*)P[0], (const float*)P[1], (const float*)P[2], P[3], I[0], (const int32_t*)P[4], I[1],
                                  (int64_t)F[0], (int64_t)F[1], (const double*)P[5], (float)F[2], I[2], (const float*)P[6], st);
+        case VT_OP_EMA_TICK:  // ptr: ctl
+            return vt_ema_tick((float*)P[0], st);
+        case VT_OP_EMA_UPDATE:  // ptr: ema p mirror ctl | f: n
+            return vt_ema_update((float*)P[0], (const float*)P[1], P[2], (int64_t)F[0], (const float*)P[3], st);
+        case VT_OP_EMA_COPY:  // ptr: dst src ctl | f: bytes
+            return vt_ema_copy(P[0], P[1], (int64_t)F[0], (const float*)P[2], st);
         case VT_OP_BCE:  // ptr: logits labels loss dlogits [mix] rows | i: ldl lddl B N dtype flags | f: eps grad_scale threshold
             return vt_sigmoid_bce(P[0], I[0], (const int64_t*)P[1], (float)F[0], (float)F[1], (float*)P[2], P[3], I[1], I[2],
                                   I[3], I[4], (const float*)P[4], I[5], (float)F[2], (double*)P[5], st);

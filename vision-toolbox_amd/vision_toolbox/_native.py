@@ -24,6 +24,9 @@ VT_OPT_ITEM = 4096
 VT_CTL_CLIP, VT_CTL_LAMB_MAX, VT_CTL_FACTOR, VT_CTL_NORM = 0, 1, 2, 3
 VT_LAMB_TRUST_CLIP, VT_LAMB_ALWAYS_ADAPT = 1, 2
 VT_BCE_SUM_CLASSES, VT_BCE_THRESHOLD = 1, 2  # flags of vt_sigmoid_bce
+# weight EMA (vt_amd.h): the words of its control buffer (alpha is a float, the others int32) and the modes vt_ema_tick leaves
+VT_EMA_ALPHA, VT_EMA_MODE, VT_EMA_COUNT, VT_EMA_PERIOD, VT_EMA_STEP = 0, 1, 2, 3, 4
+VT_EMA_SKIP, VT_EMA_COPY, VT_EMA_BLEND = 0, 1, 2
 # a statistics buffer is int64[VT_STAT_REPLICAS][2][C][2]: value = hi * 2^12 + lo / 2^33 (vt_amd.h)
 STAT_MARKER = 1 << 40  # what a non-finite or |v| >= 2^50 contribution adds to the hi limb instead of its value
 
@@ -214,7 +217,10 @@ VT_OP_MAX_PTR, VT_OP_MAX_INT, VT_OP_MAX_FLT, VT_MAX_BASES = 24, 110, 8, 16
     OP_BN_ADD_ACT_KEEP_BWD_REDUCE,
     OP_BN_ADD_ACT_KEEP_BWD_APPLY,
     OP_BN_ADD_ACT_KEEP_BWD_FIN_APPLY,
-) = range(1, 128)
+    OP_EMA_TICK,
+    OP_EMA_UPDATE,
+    OP_EMA_COPY,
+) = range(1, 131)
 OP_SIDE_STREAM = 0x10000  # OR-ed into Op.kind: enqueue on the side stream
 
 OP_NAMES = {
@@ -326,6 +332,9 @@ OP_NAMES = {
     OP_BN_ADD_ACT_KEEP_BWD_REDUCE: "bn_add_act_keep_bwd_reduce",
     OP_BN_ADD_ACT_KEEP_BWD_APPLY: "bn_add_act_keep_bwd_apply",
     OP_BN_ADD_ACT_KEEP_BWD_FIN_APPLY: "bn_add_act_keep_bwd_fin_apply",
+    OP_EMA_TICK: "ema_tick",
+    OP_EMA_UPDATE: "ema_update",
+    OP_EMA_COPY: "ema_copy",
     OP_COPY2D: "copy2d",
     OP_NCHW_TO_NHWC: "nchw_to_nhwc",
     OP_NHWC_TO_NCHW: "nhwc_to_nchw",
@@ -622,6 +631,10 @@ SYMBOLS = {
     "vt_adamw_clip": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _f64, _f64, _f32, _f32, _vp, _i32, _vp, _vp]),
     "vt_lamb_moments": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _vp, _vp, _f64, _f64, _f32, _i32, _vp, _vp]),
     "vt_lamb_apply": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i64, _vp, _f32, _i32, _vp, _vp]),
+    "vt_ema_grid_cap": (_i64, []),
+    "vt_ema_tick": (_i32, [_vp, _vp]),
+    "vt_ema_update": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "vt_ema_copy": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "vt_copy2d": (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _i64, _i32, _i32, _vp]),
     "vt_nchw_to_nhwc": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vt_nhwc_to_nchw": (_i32, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -29,8 +29,8 @@ from . import _native as N
 ALIGN = 256
 
 # base ids (index into the `bases` array handed to vt_run_ops)
-ARENA, PARAMS, GRADS, STATE, MIRROR, INPUT, COUNTERS, LABELS, MOMENTUM, HYPER, ZERO_F, ZERO_B, MOMENT2, OPTWS = range(14)
-NUM_BASES = 14
+ARENA, PARAMS, GRADS, STATE, MIRROR, INPUT, COUNTERS, LABELS, MOMENTUM, HYPER, ZERO_F, ZERO_B, MOMENT2, OPTWS, EMA = range(15)
+NUM_BASES = 15
 
 _TORCH_DTYPE = {N.VT_F32: torch.float32, N.VT_BF16: torch.bfloat16}
 _ESIZE = {N.VT_F32: 4, N.VT_BF16: 2}

@@ -169,6 +169,9 @@ class TrainStep:
         loss: str = "ce",
         bce_target_threshold: Optional[float] = None,
         bce_sum_classes: bool = False,
+        ema_decay: Optional[float] = None,
+        ema_steps: int = 1,
+        accumulate_grad_batches: int = 1,
     ):
         """optimizer="Lamb": LAMB in the form of timm.optim.Lamb(bias_correction=True, grad_averaging=True) as
         include/vt_amd.h states it (timm is no dependency; that statement is the definition).  `lamb_max_grad_norm`,
@@ -182,8 +185,31 @@ class TrainStep:
         loss="bce": binary cross-entropy against the smoothed (and, with `mix`, mixed) one-hot target, as include/vt_amd.h
         states it (timm.loss.BinaryCrossEntropy behind timm's Mixup; that statement is the definition).
         `bce_target_threshold` and `bce_sum_classes` are timm's `target_threshold` and `sum_classes`.  The loss is a
-        fixed-order sum: loss() is bit-identical from run to run.  validate() keeps plain cross-entropy."""
+        fixed-order sum: loss() is bit-identical from run to run.  validate() keeps plain cross-entropy.
+        ema_decay=d: an exponential moving average of the weights and BatchNorm statistics as include/vt_amd.h states it
+        (torchvision's ExponentialMovingAverage / timm's ModelEmaV2; that statement is the definition), kept in shadow
+        buffers by launches at the end of the optimiser list: optimiser steps 0, ema_steps, 2 * ema_steps, .. update it
+        (the first update is a copy).  validate(ema=True) scores the average, ema_state_dict() exports it.  Warm-up
+        schedules of the decay are the caller's: set_ema_decay changes it under a captured graph.
+        accumulate_grad_batches=k: step() stays one forward + backward over one micro-batch of `batch_size`; the gradient
+        exchange and the optimiser run on every k-th call, over the mean of the k micro-batch gradients (Lightning's
+        accumulate_grad_batches; the calls in between are DDP's no_sync).  steps_done, opt_steps(), the Adam step count
+        and the EMA count are optimiser steps; micro_steps_done counts calls."""
         N.lib()
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay={ema_decay!r}: None or a decay in [0, 1)")
+        if isinstance(ema_steps, bool) or int(ema_steps) != ema_steps or ema_steps < 1:
+            raise ValueError(f"ema_steps={ema_steps!r}: a whole number of optimiser steps >= 1")
+        if isinstance(accumulate_grad_batches, bool) or int(accumulate_grad_batches) != accumulate_grad_batches \
+                or accumulate_grad_batches < 1:
+            raise ValueError(f"accumulate_grad_batches={accumulate_grad_batches!r}: a whole number of micro-batches >= 1")
+        if exchange == "sharded" and ema_decay is not None:
+            raise NotImplementedError("exchange='sharded' with ema_decay: a rank owns slices of the flat parameter buffer, the "
+                                      "average would be formed from stale slices unless the weights were gathered in f32 first; "
+                                      "use exchange='allreduce'")
+        self._ema_on, self._ema_steps = ema_decay is not None, int(ema_steps)
+        self.ema_decay = None  # (set_ema_decay keeps the current value here)
+        self._accum = int(accumulate_grad_batches)
         if loss not in LOSSES:
             raise ValueError(f"loss={loss!r}: supported are {', '.join(LOSSES)}")
         if loss != "bce" and (bce_target_threshold is not None or bce_sum_classes):
@@ -354,6 +380,9 @@ class TrainStep:
             if self._clip:
                 self._alloc_optws(clip_grad_norm, lamb_max_grad_norm if self._lamb else None, weight_decay, norm_weight_decay,
                                   bias_weight_decay, groups)
+            self._ema = None
+            if self._ema_on:
+                self._alloc_ema(ema_decay)
             self.images = torch.zeros(batch_size, 3, image_size, image_size, device=self.device)
             self.labels = torch.zeros(batch_size, dtype=torch.int64, device=self.device)
         self.lr = lr
@@ -470,13 +499,15 @@ class TrainStep:
             STATE=st.sflat.data_ptr(), MIRROR=st.mirror.data_ptr(), COUNTERS=st.nflat.data_ptr(),
             INPUT=self.images.data_ptr(), LABELS=self.labels.data_ptr(), MOMENTUM=self.mflat.data_ptr(),
             HYPER=self.lr_dev.data_ptr(), **({"MOMENT2": self.vflat.data_ptr()} if self._adam else {}),
-            **({"OPTWS": self._optws.data_ptr()} if self._clip else {}))
+            **({"OPTWS": self._optws.data_ptr()} if self._clip else {}),
+            **({"EMA": self._ema.data_ptr()} if self._ema_on else {}))
         self.use_graphs = use_graphs
         self._master_stale = False
         self.model.register_state_dict_pre_hook(self._refuse_stale_export)
         self._side = None  # side stream for the filter gradients (eager mode; graphs fork internally)
         self._graphs = None
-        self.steps_done = 0
+        self.steps_done = 0  # optimiser steps
+        self.micro_steps_done = 0  # calls of step(): accumulate_grad_batches of them make one optimiser step
 
     def _alloc_optws(self, clip, lamb_max, wd, norm_wd, bias_wd, groups):
         """the device buffer behind clip_grad_norm / Lamb (OPTWS_CTL_BYTES): control floats | sum-of-squares partials of the
@@ -502,6 +533,37 @@ class TrainStep:
             self.lamb_table = torch.from_numpy(table)  # (host copy: what the plan tests read)
             self._optws[self._lamb_table_off: self._lamb_table_off + 4 * len(table)].view(torch.int32).copy_(self.lamb_table)
 
+    def _alloc_ema(self, decay):
+        """the device buffer behind ema_decay: control words (N.VT_EMA_*, 64 bytes) | shadow of pflat | shadow of sflat |
+        shadow of nflat | bf16 mirror of the shadow parameters (bf16 programs only).  One allocation, one base (E.EMA)."""
+        st = self.store
+        n_p, n_s, n_n = st.pflat.numel(), st.sflat.numel(), st.nflat.numel()
+        self._ema_p_off = 64
+        self._ema_s_off = self._ema_p_off + 4 * n_p
+        self._ema_n_off = E._round_up(self._ema_s_off + 4 * n_s, 16)
+        self._ema_m_off = E._round_up(self._ema_n_off + 8 * n_n, 16)
+        nbytes = self._ema_m_off + (2 * n_p if self.dtype == N.VT_BF16 else 0)
+        self._ema = torch.zeros(E._round_up(nbytes, 16), dtype=torch.uint8, device=self.device)
+        self._ema_ctl_f = self._ema[:32].view(torch.float32)
+        self._ema_ctl_i = self._ema[:32].view(torch.int32)
+        self.ema_pflat = self._ema[self._ema_p_off: self._ema_p_off + 4 * n_p].view(torch.float32)
+        self.ema_sflat = self._ema[self._ema_s_off: self._ema_s_off + 4 * n_s].view(torch.float32)
+        self.ema_nflat = self._ema[self._ema_n_off: self._ema_n_off + 8 * n_n].view(torch.int64)
+        self.ema_mirror = (self._ema[self._ema_m_off: self._ema_m_off + 2 * n_p].view(torch.bfloat16)
+                           if self.dtype == N.VT_BF16 else None)
+        self._ema_ctl_i[N.VT_EMA_PERIOD] = self._ema_steps
+        self.set_ema_decay(decay)
+
+    def _emit_ema(self, ob):
+        """behind the optimiser launches: the tick (this step's mode: skip / copy / blend), the average of the parameters
+        (with its bf16 mirror in the same pass), of the BatchNorm statistics, and the copy of the batch counters"""
+        st, ctl = self.store, (E.EMA, 0)
+        ob.emit(N.OP_EMA_TICK, [ctl])
+        ob.emit(N.OP_EMA_UPDATE, [(E.EMA, self._ema_p_off), (E.PARAMS, 0),
+                                  (E.EMA, self._ema_m_off) if self.dtype == N.VT_BF16 else None, ctl], [], [st.pflat.numel()])
+        ob.emit(N.OP_EMA_UPDATE, [(E.EMA, self._ema_s_off), (E.STATE, 0), None, ctl], [], [st.sflat.numel()])
+        ob.emit(N.OP_EMA_COPY, [(E.EMA, self._ema_n_off), (E.COUNTERS, 0), ctl], [], [8 * st.nflat.numel()])
+
     def _emit_opt(self, ranges):
         """optimiser launch list: one launch of the chosen optimiser per (element range, weight-decay segment) overlap.
 
@@ -515,6 +577,8 @@ class TrainStep:
         from there.  The host passes nothing per step, so an eager run and a replayed hipGraph count alike, and a rank
         that updates only its shards still sees the step count every other rank sees."""
         ob = E.Builder(self.store, self.dtype, True, True, grad_base=E.GRADS)
+        # the gradient buffer holds the SUM over the micro-batches of a group: 1 / world becomes 1 / (world * k)
+        gs = 1.0 / (self.world * self._accum)
         if self._adam:
             ob.emit(N.OP_ADAM_TICK, [(E.HYPER, 0)], [], [self._betas[0], self._betas[1]])
         mirror = lambda lo: (E.MIRROR, lo * 2) if self.dtype == N.VT_BF16 else None  # noqa: E731
@@ -523,7 +587,7 @@ class TrainStep:
             total = self.store.pflat.numel()
             assert list(ranges) == [(0, total)], "the gradient norm is global: one range over the whole flat buffer"
             ob.emit(N.OP_GRAD_SUMSQ, [(E.GRADS, 0), (E.OPTWS, self._sumsq_off)], [], [total])
-            ob.emit(N.OP_CLIP_COEF, [(E.OPTWS, self._sumsq_off), (E.OPTWS, 0)], [], [self._sumsq_items, 1.0 / self.world])
+            ob.emit(N.OP_CLIP_COEF, [(E.OPTWS, self._sumsq_off), (E.OPTWS, 0)], [], [self._sumsq_items, gs])
         if self._lamb:
             part, table = (E.OPTWS, self._lamb_part_off), (E.OPTWS, self._lamb_table_off)
             n_segs, total = len(self.store.params), self.store.pflat.numel()
@@ -552,12 +616,14 @@ class TrainStep:
                             [(E.PARAMS, lo * 4), (E.GRADS, lo * 4), (E.MOMENTUM, lo * 4), (E.MOMENT2, lo * 4),
                              (E.MIRROR, lo * 2) if self.dtype == N.VT_BF16 else None, (E.HYPER, 0)],
                             [N.VT_BF16, int(self.optimizer == "AdamW")],
-                            [hi - lo, self._betas[0], self._betas[1], self._eps, wd, 1.0 / self.world])
+                            [hi - lo, self._betas[0], self._betas[1], self._eps, wd, gs])
                 elif hi > lo:
                     ob.emit(N.OP_SGD,
                             [(E.PARAMS, lo * 4), (E.GRADS, lo * 4), (E.MOMENTUM, lo * 4),
                              (E.MIRROR, lo * 2) if self.dtype == N.VT_BF16 else None, (E.HYPER, 0)],
-                            [N.VT_BF16], [hi - lo, self._lr0, self._momentum, wd, 1.0 / self.world])
+                            [N.VT_BF16], [hi - lo, self._lr0, self._momentum, wd, gs])
+        if self._ema_on:
+            self._emit_ema(ob)
         self.opt_ops, self.n_opt = E.ops_array(ob.fwd), len(ob.fwd)
 
     def _gather_weights(self) -> None:
@@ -680,7 +746,7 @@ class TrainStep:
         N.check(N.lib().vt_stat_fold(ctypes.c_void_p(self.arena.data_ptr() + start), C_, ctypes.c_void_p(stream)))
         torch.distributed.all_reduce(self._sync_view(base, off, nbytes), group=self.pg)
 
-    def _run_list(self, ops, n, sync, cuts, cut_buckets, s, side, keep_side_open=True):
+    def _run_list(self, ops, n, sync, cuts, cut_buckets, s, side, keep_side_open=True, exchange=True):
         """run a launch list in segments: a segment ends before every finalize kernel whose statistics
         must be all-reduced first (SyncBatchNorm) and after every op that completes a gradient bucket.
 
@@ -700,7 +766,7 @@ class TrainStep:
                 N.run_ops(sub, hi - lo, self.bases, s, side=side, leave_side_open=keep_side_open and hi != n)
             if hi in marks:  # stream-ordered: NCCL makes the launch stream wait, no host sync
                 self._sync_stats(*marks[hi][1], s)
-            if hi in cut_buckets and cut_buckets[hi] and not self._skip_exchange:
+            if hi in cut_buckets and cut_buckets[hi] and exchange and not self._skip_exchange:
                 if side and self._side is not None:
                     N.stream_wait(side, s)
                     with torch.cuda.stream(self._side):
@@ -722,14 +788,20 @@ class TrainStep:
         WITHOUT issuing the collectives (step time with them minus step time without = what the exchange leaves exposed).
         Steps taken inside update every replica from its own rank's gradients, which would desynchronise the replicas (and
         under the sharded exchange leave non-owned slices stale): the context snapshots parameters, BatchNorm state, the
-        batch counters, momentum and the bf16 mirror on entry and restores them on exit."""
+        batch counters, momentum and the bf16 mirror (with ema_decay: the shadow buffers and their counts too; with
+        accumulate_grad_batches: the gradient buffer, steps_done and micro_steps_done, so a group of micro-steps begun
+        outside continues where it was) on entry and restores them on exit."""
         import contextlib
 
         @contextlib.contextmanager
         def ctx():
             st = self.store
             state = (st.pflat, st.sflat, st.nflat, self.mflat, st.mirror) + ((self.vflat, self.lr_dev) if self._adam else ())
+            if self._ema_on:  # the shadow buffers with their control words (mode, update and step counts)
+                state += (self._ema,)
             keep = [t.clone() for t in state]
+            # (accumulate_grad_batches: the position inside a group of micro-steps and the partly accumulated gradient)
+            counts, gkeep = (self.steps_done, self.micro_steps_done), (self.gflat.clone() if self._accum > 1 else None)
             self._skip_exchange = True
             try:
                 yield self
@@ -738,6 +810,9 @@ class TrainStep:
                 torch.cuda.synchronize(self.device)
                 for dst, src_ in zip(state, keep):
                     dst.copy_(src_)
+                if gkeep is not None:
+                    self.gflat.copy_(gkeep)
+                    self.steps_done, self.micro_steps_done = counts
 
         return ctx()
 
@@ -753,6 +828,8 @@ class TrainStep:
             if self._adam:  # second moment and the step count with its bias corrections
                 torch.distributed.broadcast(self.vflat, src, group=self.pg)
                 torch.distributed.broadcast(self.lr_dev[HYPER_STEP:HYPER_STEP + 4], src, group=self.pg)
+            if self._ema_on:  # the average and its counts: a resumed run keeps averaging alike on every rank
+                torch.distributed.broadcast(self._ema, src, group=self.pg)
             if self.dtype == N.VT_BF16:
                 self.store.mirror.copy_(self.store.pflat)
 
@@ -802,9 +879,71 @@ class TrainStep:
             raise ValueError(f"clip_grad_norm={value!r}: a threshold is >= 0")
         self._ctl[N.VT_CTL_CLIP] = float(value)
 
+    # -- weight EMA ------------------------------------------------------------------------------
+    def _need_ema(self, what: str) -> None:
+        if not self._ema_on:
+            raise RuntimeError(f"{what}: this TrainStep was built without ema_decay and keeps no average of its weights")
+
+    def set_ema_decay(self, decay: float) -> None:
+        """change the decay of the NEXT update(s); like set_lr, a captured graph follows (alpha lives on the device).
+        alpha = 1 - decay is formed in double here and rounded to f32 once (vt_amd.h)."""
+        self._need_ema("set_ema_decay")
+        if not 0.0 <= float(decay) < 1.0:
+            raise ValueError(f"ema_decay={decay!r}: a decay in [0, 1)")
+        self.ema_decay = float(decay)
+        self._ema_ctl_f[N.VT_EMA_ALPHA] = 1.0 - float(decay)
+
+    def ema_updates(self) -> int:
+        """updates of the average made so far, as the DEVICE counts them (vt_ema_tick; synchronises)"""
+        self._need_ema("ema_updates")
+        return int(self._ema_ctl_i[N.VT_EMA_COUNT].item())
+
+    def _ema_views(self):
+        """(state_dict key, shadow tensor in the key's logical shape) for every entry of the model's state_dict"""
+        st = self.store
+        flat = {E.PARAMS: self.ema_pflat, E.STATE: self.ema_sflat, E.COUNTERS: self.ema_nflat}
+        for key, t in self.model.state_dict(keep_vars=True).items():
+            base, off, n = st.where(t)
+            seg = flat[base][off: off + n]
+            if t.dim() == 4:  # held channels_last, [Cout][kh][kw][Cin], like the parameter itself (ParamStore)
+                o, i, kh, kw = t.shape
+                yield key, seg.view(o, kh, kw, i).permute(0, 3, 1, 2)
+            else:
+                yield key, seg.view(t.shape)
+
+    def ema_state_dict(self) -> dict:
+        """the average under the keys and logical shapes of `model.state_dict()` (copies); load it into a model, or a twin
+        TrainStep, with load_state_dict"""
+        self._need_ema("ema_state_dict")
+        if self.ema_updates() == 0:
+            raise RuntimeError("ema_state_dict: no update of the average yet (the first optimiser step makes the first)")
+        return {k: v.clone(memory_format=torch.contiguous_format) for k, v in self._ema_views()}
+
+    def load_ema_state_dict(self, sd: dict, updates: Optional[int] = None, steps: Optional[int] = None) -> None:
+        """the inverse of ema_state_dict, for resuming: writes the shadow buffers (and their bf16 mirror).  The next update
+        blends instead of copying; `updates` also restores the device's update count (default: at least 1) and `steps` its
+        count of optimiser steps, which carries the phase of ema_steps > 1 (default: left as it is -- a fresh TrainStep
+        starts a new period with its first step; pass the saved run's steps_done to continue the old one)."""
+        self._need_ema("load_ema_state_dict")
+        views = dict(self._ema_views())
+        if set(sd) != set(views):
+            raise KeyError(f"load_ema_state_dict: keys differ from the model's state_dict: "
+                           f"{sorted(set(sd) ^ set(views))[:8]}")
+        with torch.no_grad():
+            for k, v in views.items():
+                if tuple(sd[k].shape) != tuple(v.shape):
+                    raise ValueError(f"load_ema_state_dict: {k} has shape {tuple(sd[k].shape)}, expected {tuple(v.shape)}")
+                v.copy_(sd[k])
+            if self.ema_mirror is not None:
+                self.ema_mirror.copy_(self.ema_pflat)
+        self._ema_ctl_i[N.VT_EMA_COUNT] = max(self.ema_updates(), 1) if updates is None else int(updates)
+        if steps is not None:
+            self._ema_ctl_i[N.VT_EMA_STEP] = int(steps)
+
     def last_grad_norm(self) -> float:
         """the norm N = sqrt(sum g^2) / world of the averaged gradient of the last step, before any clipping, as the device
-        formed it (clip_grad_norm or Lamb only; synchronises)"""
+        formed it (clip_grad_norm or Lamb only; synchronises).  With accumulate_grad_batches = k: of the mean over the
+        group's k micro-batches, N = sqrt(sum G^2) / (world * k) for the accumulated G."""
         if not self._clip:
             raise RuntimeError("this TrainStep forms no gradient norm (neither clip_grad_norm nor optimizer='Lamb')")
         return float(self._ctl[N.VT_CTL_NORM].item())
@@ -843,14 +982,21 @@ class TrainStep:
             self._graphs = {
                 "head": N.Graph(E.ops_array(list(self.zero_ops[:1]) + [p.fwd_ops[i] for i in range(p.n_fwd)]),
                                 1 + p.n_fwd, self.bases),
+                # (accumulate_grad_batches: the later micro-steps of a group add to the gradient the first one started)
+                "head_keep": N.Graph(p.fwd_ops, p.n_fwd, self.bases) if self._accum > 1 else None,
                 "bwd": [N.Graph(ops, n, self.bases) for ops, n in self._segment_ops()],
                 "opt": N.Graph(self.opt_ops, self.n_opt, self.bases),
             }
 
     def step(self, images: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None) -> None:
-        """fwd + loss + bwd + gradient all-reduce + optimiser on the resident (or given) batch."""
+        """fwd + loss + bwd + gradient all-reduce + optimiser on the resident (or given) batch.  With
+        accumulate_grad_batches = k: forward + backward of one micro-batch; the first call of a group of k zeroes the
+        gradient buffer, the last one exchanges the accumulated gradient and runs the optimiser."""
         if self.plan_only:
             raise RuntimeError("plan_only TrainStep cannot execute: there is no CPU path")
+        micro = self.micro_steps_done % self._accum
+        first, last = micro == 0, micro == self._accum - 1
+        no_sync = self._skip_exchange or not last  # (micro-steps in front of the last: DDP's no_sync)
         with self._dev_ctx():
             if images is not None:
                 self.images.copy_(images, non_blocking=True)
@@ -860,35 +1006,40 @@ class TrainStep:
             p = self.prog
             if self._keep_buf is not None:
                 self._fill_keep_table()  # (once per step, on the current stream in front of the lists or the graph)
-            if self.use_graphs and not self.sync_bn and self.collectives != "rccl":
+            graphs = self.use_graphs and not self.sync_bn and self.collectives != "rccl"
+            if graphs:
                 if self._graphs is None:
                     self._build_graphs()
-                self._graphs["head"].launch(s)
+                self._graphs["head" if first else "head_keep"].launch(s)
                 for g, bks in zip(self._graphs["bwd"], self.cut_buckets):
                     g.launch(s)
-                    for bi in ([] if self._skip_exchange else bks):
+                    for bi in ([] if no_sync else bks):
                         self.bucketer.reduce_bucket(bi)
             else:
                 if self._side is None:
                     self._side = torch.cuda.Stream(self.device)
                 side = int(self._side.cuda_stream)
-                N.run_ops(self.zero_ops, 1, self.bases, s)
+                if first:
+                    N.run_ops(self.zero_ops, 1, self.bases, s)
                 self._run_list(p.fwd_ops, p.n_fwd, self._fwd_sync, [], {}, s, side, keep_side_open=False)
                 bwd_ops, n_bwd = p.bwd_ops, p.n_bwd
-                if self._skip_exchange and self.collectives == "rccl" and getattr(self, "_bwd_without_exchange", None):
+                if no_sync and self.collectives == "rccl" and getattr(self, "_bwd_without_exchange", None):
                     bwd_ops, n_bwd = self._bwd_without_exchange
                 self._run_list(bwd_ops, n_bwd, self._bwd_sync, [n_bwd] if self.collectives == "rccl" else self.bwd_cuts,
-                               dict(zip(self.bwd_cuts, self.cut_buckets)), s, side)
-            if self.bucketer is not None and not self._skip_exchange:
+                               dict(zip(self.bwd_cuts, self.cut_buckets)), s, side, exchange=not no_sync)
+            if self.bucketer is not None and not no_sync:
                 self.bucketer.finish()
-            if self.use_graphs and not self.sync_bn and self.collectives != "rccl":
-                self._graphs["opt"].launch(s)
-            else:
-                N.run_ops(self.opt_ops, self.n_opt, self.bases, s)
-            if self.exchange == "sharded" and not self._skip_exchange:
-                self._gather_weights()
-                self._master_stale = True
-        self.steps_done += 1
+            if last:
+                if graphs:
+                    self._graphs["opt"].launch(s)
+                else:
+                    N.run_ops(self.opt_ops, self.n_opt, self.bases, s)
+                if self.exchange == "sharded" and not self._skip_exchange:
+                    self._gather_weights()
+                    self._master_stale = True
+        self.micro_steps_done += 1
+        if last:
+            self.steps_done += 1
 
     # ---- validation step (reference classifier.py:97-109) ----------------------------------------------------------
     def _build_eval(self):
@@ -917,13 +1068,19 @@ class TrainStep:
                            COUNTERS=self.store.nflat.data_ptr(), LABELS=self.labels.data_ptr())
         self._eval = (prog, arena, bases, prog.zf_off + sums.offset, logits)
 
-    def validate(self, images: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None) -> dict:
+    def validate(self, images: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, ema: bool = False) -> dict:
         """One validation step on the resident (or given) batch: eval-mode forward, cross entropy WITHOUT label smoothing,
         top-1 accuracy -- `validation_step` of classifier.py:97-109.  Data parallel, the three sums (loss, hits, rows) are
         all-reduced over the ranks (its `sync_dist=True`; collective C4 of SURVEY section 2), so every rank returns the
-        GLOBAL mean loss and accuracy.  Parameters, BatchNorm statistics and optimiser state are not touched."""
+        GLOBAL mean loss and accuracy.  Parameters, BatchNorm statistics and optimiser state are not touched.
+        ema=True scores the averaged weights (TrainStep(ema_decay=...)): the SAME program and arena, with the parameter,
+        statistics, mirror and counter bases pointing at the shadow buffers."""
+        if ema:
+            self._need_ema("validate(ema=True)")
         if self.plan_only:
             raise RuntimeError("plan_only TrainStep cannot execute: there is no CPU path")
+        if ema and self.ema_updates() == 0:
+            raise RuntimeError("validate(ema=True): no update of the average yet (the first optimiser step makes the first)")
         if getattr(self, "_master_stale", False):
             self.gather_master()
         with self._dev_ctx():
@@ -934,6 +1091,8 @@ class TrainStep:
             if getattr(self, "_eval", None) is None:
                 self._build_eval()
             prog, arena, bases, off, _ = self._eval
+            if ema:
+                bases = self._eval_bases_ema()
             s = current_stream_handle()
             if self._side is None:
                 self._side = torch.cuda.Stream(self.device)
@@ -942,6 +1101,17 @@ class TrainStep:
         sums = reduce_validation_sums(sums, self.pg if self.dp else None)
         loss_sum, hits, rows = (float(v) for v in sums.tolist())
         return {"loss": loss_sum / rows, "acc": hits / rows, "correct": int(round(hits)), "count": int(round(rows))}
+
+    def _eval_bases_ema(self) -> list:
+        """the bases of the validation program with PARAMS / STATE / MIRROR / COUNTERS at the shadow buffers (an f32 program
+        reads no mirror: its slot keeps the store's)"""
+        if getattr(self, "_eval_ema", None) is None:
+            prog, arena = self._eval[0], self._eval[1]
+            mirror = self.ema_mirror if self.ema_mirror is not None else self.store.mirror
+            self._eval_ema = prog.bases(arena.data_ptr(), PARAMS=self.ema_pflat.data_ptr(), STATE=self.ema_sflat.data_ptr(),
+                                        MIRROR=mirror.data_ptr(), INPUT=self.images.data_ptr(),
+                                        COUNTERS=self.ema_nflat.data_ptr(), LABELS=self.labels.data_ptr())
+        return self._eval_ema
 
     def eval_logits(self) -> torch.Tensor:
         """logits of the last validate() call"""
